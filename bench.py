@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the PointCloudUDA adversarial train step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`` (RANK / LOCAL_RANK /
 WORLD_SIZE in the environment), or plainly as ``python bench.py --gpus N``: the parent then starts one child process per
@@ -14,10 +14,18 @@ the D's.  img/s = bs * steps/s, bs = the reference's -bs (source images per step
 of target images rides along).  Weak scaling: every rank runs the full per-GPU batch, gradients
 are all-reduced over RCCL before the optimiser kernels.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, runs the settle and warm-up steps, times K steps and prints ONE JSON line (rank 0) with the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step).
+
+--dump-outputs DIR  after the timed steps, what the last of them computed, as DIR/<name>.npy (float32, <= 64 MB): see
+                    dump_outputs.  Same arguments, same inputs (seeded), so two builds can be compared output for output.
+--full              also everything beyond the headline figure, each on extra steps or launches after the timed ones:
+  host_issue_ms_per_step / launches_per_step  host time to issue a step, library launches per step
+  comm_exposed_ms  (N > 1) the same steps with the gradient all-reduces switched off
+  clock_ghz_under_load / img_s_per_ghz        shader clock under an all-SIMD MFMA probe, and value normalised by it
   roofline     the dominant kernel family (implicit-GEMM MFMA convolution: forward + dgrad launches)
-               timed live with HIP events on the launch stream over extra profiled steps
-  cpu_baseline the oracle's CPU restatement of the same step, timed on this host (rank 0, N = 1)
+               timed live with HIP events on the launch stream over extra profiled steps (--no-roofline: left out)
+  cpu_baseline the oracle's CPU restatement of the same step, timed on this host (rank 0, N = 1; --no-cpu-baseline)
 """
 from __future__ import annotations
 
@@ -195,6 +203,33 @@ def pmc_traffic_per_launch():
         os.path.basename(files[-1]), have)
 
 
+DUMP_MAX_ELEMS = 1 << 21      # per flat parameter buffer (8 MB of float32); larger buffers: a seeded sample this size
+
+
+def dump_outputs(path, tr, out):
+    """``--dump-outputs DIR``: what the timed path computed in its last step, as float32 .npy files in DIR.
+
+    * ``step_<key>.npy``: every entry of the dict the step returns (the losses, discriminator hit rates and dice of that
+      step, device scalars as the caller receives them);
+    * ``params_<net>.npy``: the flat parameter buffer of each trained network (gen, dis1, dis2, dis4) after that step's
+      optimiser updates.  A buffer of more than DUMP_MAX_ELEMS elements is written as DUMP_MAX_ELEMS elements at sorted
+      indices drawn with a fixed seed per network: the same indices in every run of the same workload.
+
+    At most 4 x 8 MB in all.  Called before anything else runs on the trainer (``--full``'s extra steps change the
+    parameters)."""
+    os.makedirs(path, exist_ok=True)
+    for k, v in sorted(out.items()):
+        np.save(os.path.join(path, "step_%s.npy" % k), v.detach().float().reshape(-1).cpu().numpy())
+    for seed, (nm, opt) in enumerate((("gen", tr.opt_gen), ("dis1", tr.opt_d1), ("dis2", tr.opt_d2), ("dis4", tr.opt_d4))):
+        if opt is None:
+            continue
+        p = opt.p.detach()
+        if p.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(1000 + seed).choice(p.numel(), size=DUMP_MAX_ELEMS, replace=False))
+            p = p[torch.from_numpy(idx).to(p.device)]
+        np.save(os.path.join(path, "params_%s.npy" % nm), p.float().cpu().numpy())
+
+
 def spawn_ranks(n, argv):
     """``python bench.py --gpus N`` without a launcher: one child process per GPU (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* set), started before this process has made any GPU call (a process that has initialised HIP must not be
@@ -321,11 +356,17 @@ def main():
     ap.add_argument("--workload", default="full_uda", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the workload's)")
     ap.add_argument("--precision", default=os.environ.get("PCUDA_PRECISION", "bf16x3"), choices=["bf16x3", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also host issue time, exposed communication, probe clock, roofline pass and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave the cpu_baseline leg out")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) leave the profiled roofline steps out")
     ap.add_argument("--dry-run", action="store_true", help="launcher + collectives only, on CPU over gloo (tests)")
     ap.add_argument("--cpu-batches", default="2,16", help="batch sizes of the cpu_baseline leg")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # no launcher around us and more than one GPU asked for: become the launcher.  Nothing above this line (and
     # nothing at import time) initialises HIP: torch.cuda.is_available() is first called in the children.
@@ -419,20 +460,25 @@ def main():
     host = tr.to_host(out, tr.cfg)
     if not all(np.isfinite(v) for v in host.values()):
         raise SystemExit("non-finite loss in the benchmark step: %r" % host)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, out)
 
-    # host side of a step: time to ISSUE it (Python + launches, nothing waited for) and the library's launch count.  With
-    # N ranks on one host this, not the GPU, is what has to stay below ms_per_step.
-    n_issue = max(4, min(10, args.steps))
-    K.launch_count(reset=True)
-    t0 = time.perf_counter()
-    for _ in range(n_issue):
-        step(*batch)
-    host_issue_ms = 1000.0 * (time.perf_counter() - t0) / n_issue
-    launches_per_step = K.launch_count(reset=True) / n_issue
-    sync()
+    full = {}
+    if args.full:
+        # host side of a step: time to ISSUE it (Python + launches, nothing waited for) and the library's launch count.  With
+        # N ranks on one host this, not the GPU, is what has to stay below ms_per_step.
+        n_issue = max(4, min(10, args.steps))
+        K.launch_count(reset=True)
+        t0 = time.perf_counter()
+        for _ in range(n_issue):
+            step(*batch)
+        host_issue_ms = 1000.0 * (time.perf_counter() - t0) / n_issue
+        launches_per_step = K.launch_count(reset=True) / n_issue
+        sync()
+        full.update(host_issue_ms_per_step=round(host_issue_ms, 3), launches_per_step=round(launches_per_step, 1))
     # exposed communication: the same steps with the gradient all-reduces switched off on every rank
     comm_exposed_ms = None
-    if dist is not None and not use_graph:
+    if args.full and dist is not None and not use_graph:
         from pointcloududa_amd import optim as O
         n_cmp = max(5, min(30, args.steps))
 
@@ -455,6 +501,8 @@ def main():
             O.set_collectives(None)
         tr.broadcast_parameters()          # the replicas drifted apart while nothing was all-reduced
         comm_exposed_ms = round(with_c - without_c, 3)
+    if args.full:
+        full["comm_exposed_ms"] = comm_exposed_ms
 
     result = {
         "metric": "adversarial train-step images/sec (seg+3 discr) at %dx%d" % (wl.get("hw", 256), wl.get("hw", 256)),
@@ -462,12 +510,11 @@ def main():
         "warmup": args.warmup, "settle": args.settle, "ms_per_step": round(1000.0 * dt / args.steps, 3),
         "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None,
-        "host_issue_ms_per_step": round(host_issue_ms, 3), "launches_per_step": round(launches_per_step, 1),
-        "comm_exposed_ms": comm_exposed_ms,
+        **full,
         "per_rank_img_s": per_rank,
-        # shader clock while every SIMD issues MFMAs back to back, measured AFTER the timed region on this box (rank 0's GPU):
-        # boxes of the pool differ by up to 10 % on one binary; value / clock normalises lines of different rounds
-        "clock_ghz_under_load": round(K.clock_ghz_under_load(dev), 3),
+        # (--full) shader clock while every SIMD issues MFMAs back to back, measured AFTER the timed region on this box (rank 0's
+        # GPU): boxes of the pool differ by up to 10 % on one binary; value / clock normalises lines of different rounds
+        **({"clock_ghz_under_load": round(K.clock_ghz_under_load(dev), 3)} if args.full else {}),
         # launches that ran on a generic fallback kernel (csrc/variants.h: pruned default build): must be 0 for a benchmark line
         "fallback_launches": int(K.L.lib().pcuda_fallback_count()),
         "dtype": "bf16x3 MFMA (split-bf16, fp32 accumulate; fp32 storage)" if args.precision == "bf16x3"
@@ -499,10 +546,11 @@ def main():
     # value / probe clock: what normalises lines from boxes of different clocks (the probe is an all-SIMD MFMA loop on trivial
     # operands: the clock the box GRANTS, not the lower one the convolution kernels hold on real data --
     # profiles/r06_experiment_power_cap.txt)
-    if result["clock_ghz_under_load"]:
+    if result.get("clock_ghz_under_load"):
         result["img_s_per_ghz"] = round(result["value"] / world / result["clock_ghz_under_load"], 1)
 
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         # every rank runs the profiled steps (they hold collectives when world > 1); rank 0 reports its own kernels
         K.prof_reset()
         K.prof_enable(rank == 0)
@@ -532,7 +580,7 @@ def main():
         pms, pbytes, pl_n = K.prof_read(2)
         dms, dflops, dl_n = K.prof_read(3)
         K.prof_reset()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         ach = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
         # the committed PMC passes were taken on the default command (full_uda, batch 32, bf16x3): only that run quotes them
         same_cmd = args.workload == "full_uda" and b == wl["batch"] and args.precision == "bf16x3" and world == 1
@@ -564,7 +612,7 @@ def main():
                               "peak_gbps": 8000.0},
             },
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(wl, batches=tuple(int(v) for v in args.cpu_batches.split(",")))
     if dist is not None:
         dist.barrier()

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do
   for ds in 1 0; do
     for ap in 0 1; do
-      PCUDA_DSTREAMS=$ds PCUDA_AP=$ap python bench.py --steps 60 --warmup 20 --no-cpu-baseline --no-roofline 2>/dev/null | \
+      PCUDA_DSTREAMS=$ds PCUDA_AP=$ap python bench.py --full --steps 60 --warmup 20 --no-cpu-baseline --no-roofline 2>/dev/null | \
         python -c "import sys,json; d=json.loads(sys.stdin.read().strip().split(chr(10))[-1]); print('dstreams $ds ap $ap', d['value'], d['ms_per_step'], d['clock_ghz_under_load'])"
     done
   done
