@@ -375,6 +375,27 @@ int pcuda_label_dice(const uint8_t* pred, const uint8_t* gt, long long numel, in
                      size_t workspace_bytes, pcuda_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * evaluation metrics (utils/metric.py evaluate / metrics2, evaluate_*.py; medpy.metric.binary dc / hd / asd and
+ * utils.py keep_largest_connected_components) on integer label volumes [z][h][w] (ndim 2: z = 1, [h][w]), uint8 or
+ * int32 (labels_i32); every dimension 1..16384, z*h*w < 2^31.
+ * ---------------------------------------------------------------------------------- */
+/* per class value classes[k] (ncls 1..8, host array), A = pred == c, B = gt == c:
+ * out[k][8] (device fp64) = dice 2|A.B|/(|A|+|B|) (0 if both empty), hd, asd(pred->gt), asd(gt->pred), |A|, |B|, |A.B|,
+ * flags (1: A empty, 2: B empty; hd / asd are NaN then).  border(X) = X & ~erode(X) with the footprint of connectivity
+ * 1..ndim, outside = background; sd(X, Y) = Euclidean distance (spacing[ndim] per array axis, host, NULL = 1) from each
+ * border(X) voxel to the nearest border(Y) voxel; hd = max over both directions, asd(X->Y) = mean sd(X, Y).  Exact
+ * integer squared distances at unit spacing; results are the same bits from run to run. */
+size_t pcuda_surface_metrics_workspace_size(int ndim, int z, int h, int w, int ncls, const double* spacing);
+int pcuda_surface_metrics(const void* pred, const void* gt, int labels_i32, int ndim, int z, int h, int w, const int* classes,
+                          int ncls, int connectivity, const double* spacing, double* out, void* workspace,
+                          size_t workspace_bytes, pcuda_stream_t s);
+/* out (uint8) = for each label 1..min(nlabels, 255) of mask the largest face-connected component (among equal sizes
+ * the one whose first voxel comes first in raster order), every other voxel 0 */
+size_t pcuda_largest_components_workspace_size(int ndim, int z, int h, int w);
+int pcuda_largest_components(const void* mask, int mask_i32, int ndim, int z, int h, int w, int nlabels, uint8_t* out,
+                             void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * small dense ops of PointNetCls / the point head (PointNetCls.py; unet.py:86,94-95)
  * ---------------------------------------------------------------------------------- */
 /* y[m][n] = x[m][k] . w[n][k]^T + b[n]   (nn.Linear; also conv1d k=1 seen as [B*L][C]) */

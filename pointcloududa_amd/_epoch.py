@@ -314,11 +314,10 @@ def train_epoch(variant, args, model_gen, model_dis2, model_dis4, model_dis1=Non
 
 # ------------------------------------------------------------------------------------------------ validation
 def valid_model_with_one_dataset(variant, args, seg_model, data_generator, hd: bool = False) -> Dict[str, float]:
-    """train_mscmrseg.py:53-99 / train_mmwhs.py:55-100 over a host-numpy generator; ``hd=True`` (medpy Hausdorff, CPU) is
-    out of scope.  Result keys as in the respective script: dice, loss and ``valid_vert_loss`` (MS-CMRSeg) or
-    ``vert_loss`` (MM-WHS)."""
-    if hd:
-        raise NotImplementedError("Hausdorff distance (medpy, CPU, evaluation only) is out of scope: SURVEY section 2.1 row 7")
+    """train_mscmrseg.py:53-99 / train_mmwhs.py:55-100 over a host-numpy generator.  Result keys as in the respective
+    script: dice, loss and ``valid_vert_loss`` (MS-CMRSeg) or ``vert_loss`` (MM-WHS); ``hd=True`` adds "hd", the mean
+    over the batches of the mean over the classes of medpy's Hausdorff distance (``evaluate`` classes 1..3 /
+    ``metrics2`` classes 1..4, each batch's label maps as one volume), on the HIP kernels with one synchronisation."""
     from . import validate as V
     dev = next(seg_model.parameters()).device
 
@@ -327,7 +326,8 @@ def valid_model_with_one_dataset(variant, args, seg_model, data_generator, hd: b
             yield x, (y if y.dtype == torch.uint8 else y.to(torch.uint8)), z
     ms = variant == "mscmrseg"
     d4 = bool(getattr(args, "d4", False)) or (not ms and bool(getattr(args, "d4aux", False)))
-    r = V.valid_model_with_one_dataset(seg_model, batches(), d4=d4, variant=variant, softmax=bool(getattr(args, "softmax", True)))
+    r = V.valid_model_with_one_dataset(seg_model, batches(), d4=d4, variant=variant, softmax=bool(getattr(args, "softmax", True)),
+                                       hd=hd)
     seg_model.eval()                                   # the reference leaves the model in eval mode (:60)
     if not ms:
         r["vert_loss"] = r.pop("valid_vert_loss")

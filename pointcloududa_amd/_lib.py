@@ -124,6 +124,10 @@ _PROTOS = {
     "pcuda_assemble_batch": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "pcuda_argmax_labels": (i32, [vp, i32, i64, i64, i32, i32, i64, vp, vp]),
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
+    "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),
+    "pcuda_surface_metrics": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "pcuda_largest_components_workspace_size": (sz, [i32, i32, i32, i32]),
+    "pcuda_largest_components": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "pcuda_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "pcuda_linear_bwd_x": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "pcuda_linear_bwd_w_workspace_size": (sz, [i32, i32, i32]),

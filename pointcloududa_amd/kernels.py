@@ -862,6 +862,72 @@ def label_dice(pred_labels, gt_labels, num_classes):
     return out
 
 
+def _label_volume(t, name):
+    """a 2-D / 3-D integer label volume as the library reads it: contiguous uint8 or int32 (wider integers clamped to
+    the int32 range, which no class value lies outside of), and its (ndim, z, h, w)"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("%s: HIP device tensors only (no CPU fallback)" % name)
+    if t.dim() not in (2, 3):
+        raise ValueError("%s: 2-D [H,W] or 3-D [Z,H,W] label volumes (got shape %s)" % (name, tuple(t.shape)))
+    if t.dtype == torch.bool:
+        t = t.to(torch.uint8)
+    elif t.dtype not in (torch.uint8, torch.int32):
+        if t.is_floating_point() or t.is_complex():
+            raise TypeError("%s: integer label volumes only (got %s)" % (name, t.dtype))
+        t = (t.clamp(-2 ** 31, 2 ** 31 - 1) if t.dtype == torch.int64 else t).to(torch.int32)
+    shp = (1,) * (3 - t.dim()) + tuple(t.shape)
+    return t.contiguous(), t.dim(), shp
+
+
+def surface_metrics(pred, gt, classes, spacing=None, connectivity=1):
+    """medpy's dc / hd / asd for every class value of ``classes`` (at most 8) between two label volumes of one shape
+    (2-D or 3-D, uint8 or integer): fp64 ``[len(classes), 8]`` on the device, no host synchronisation.  Columns: dice,
+    hd, asd(pred -> gt), asd(gt -> pred), |pred == c|, |gt == c|, |both|, flags (1: pred empty, 2: gt empty; hd and asd
+    are NaN where a flag is set).  ``spacing``: per-axis voxel spacing (None = 1); ``connectivity``: 1..ndim, the
+    footprint of the erosion that extracts the borders."""
+    pred, nd, shp = _label_volume(pred, "surface_metrics")
+    gt, nd_g, shp_g = _label_volume(gt, "surface_metrics")
+    if shp != shp_g or nd != nd_g:
+        raise ValueError("surface_metrics: shapes differ (%s vs %s)" % (tuple(pred.shape), tuple(gt.shape)))
+    if pred.dtype != gt.dtype:
+        pred, gt = pred.to(torch.int32), gt.to(torch.int32)
+    cls = [int(c) for c in classes]
+    ccls = (C.c_int * max(1, len(cls)))(*cls)
+    sp = None
+    if spacing is not None:
+        spacing = [float(v) for v in (spacing if hasattr(spacing, "__len__") else [spacing] * nd)]
+        if len(spacing) != nd:
+            raise ValueError("surface_metrics: %d spacing values for a %d-D volume" % (len(spacing), nd))
+        sp = (C.c_double * nd)(*spacing)
+    lib = L.lib()
+    wsb = lib.pcuda_surface_metrics_workspace_size(nd, *shp, len(cls), sp)
+    ws = torch.empty(max(1, wsb), dtype=torch.uint8, device=pred.device)
+    out = torch.empty((len(cls), 8), dtype=torch.float64, device=pred.device)
+    check(lib.pcuda_surface_metrics(pred.data_ptr(), gt.data_ptr(), 1 if pred.dtype == torch.int32 else 0, nd, *shp, ccls,
+                                    len(cls), int(connectivity), sp, out.data_ptr(), ws.data_ptr(), wsb, _stream()),
+          "surface_metrics")
+    return out
+
+
+def largest_components(mask):
+    """``keep_largest_connected_components`` (utils.py:43-65) of a 2-D / 3-D label volume on the device: for every label
+    1..mask.shape[1] the largest face-connected component (ties: the one whose first voxel comes first in raster order),
+    every other voxel 0; uint8 of the mask's shape.  Label values >= 256 in that range raise ValueError (the reference
+    would wrap them in uint8)."""
+    nl = int(mask.shape[1]) if mask.dim() >= 2 else 0
+    if mask.is_cuda and mask.dtype not in (torch.uint8, torch.bool) and nl >= 256 and not mask.is_floating_point():
+        if bool(((mask >= 256) & (mask <= nl)).any()):          # (a host synchronisation only for such masks)
+            raise ValueError("largest_components: label values 256..%d do not fit the uint8 output" % nl)
+    m, nd, shp = _label_volume(mask, "largest_components")
+    lib = L.lib()
+    wsb = lib.pcuda_largest_components_workspace_size(nd, *shp)
+    ws = torch.empty(max(1, wsb), dtype=torch.uint8, device=m.device)
+    out = torch.empty(m.shape, dtype=torch.uint8, device=m.device)
+    check(lib.pcuda_largest_components(m.data_ptr(), 1 if m.dtype == torch.int32 else 0, nd, *shp, nl, out.data_ptr(),
+                                       ws.data_ptr(), wsb, _stream()), "largest_components")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # dense
 # ------------------------------------------------------------------------------------------

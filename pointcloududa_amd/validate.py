@@ -2,16 +2,28 @@
 
 Mirrors ``valid_model_with_one_dataset`` (``src/train_mscmrseg.py:53-99``): eval-mode forward (BatchNorm folded
 from its running statistics), BCE + Jaccard (+ point NN) loss, hard labels, per-class Dice -- with every
-per-batch quantity kept on the device (one synchronisation per data set instead of three per batch).
-Hausdorff / average-surface distances (medpy, CPU) are out of scope."""
+per-batch quantity kept on the device (one synchronisation per data set instead of three per batch).  ``hd=True`` adds
+the reference's Hausdorff distance (medpy ``hd`` through ``evaluate`` / ``metrics2``) from the HIP surface-metric kernels;
+``evaluate_volume`` is the device-side core of the evaluate scripts (forward, argmax, largest components, dice / hd /
+asd)."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, Optional
 
+import numpy as np
 import torch
 
+from . import evaluate_mmwhs as EW
+from . import evaluate_mscmrseg as EM
+from . import kernels as K
 from .utils import loss as L
 from .utils import metric as M
+from .utils import utils as U
+
+# the classes of ``evaluate`` (MS-CMRSeg) / ``metrics2`` (MM-WHS), and the order in which the validation loops add their
+# hd values: (lv + myo + rv) / 3 (train_mscmrseg.py:91), (lv + myo + la + aa) / 4 (train_mmwhs.py:90)
+_HD_CLASSES = {"mscmrseg": [1, 2, 3], "mmwhs": [1, 2, 3, 4]}
+_HD_ORDER = {"mscmrseg": [1, 0, 2], "mmwhs": [2, 0, 1, 3]}
 
 
 @torch.no_grad()
@@ -29,11 +41,13 @@ def predict_labels(seg_model, x: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def valid_batch(seg_model, x: torch.Tensor, y_onehot_u8: torch.Tensor, z: Optional[torch.Tensor] = None,
-                d4: bool = True, variant: str = "mscmrseg", softmax: bool = True) -> Dict[str, torch.Tensor]:
+                d4: bool = True, variant: str = "mscmrseg", softmax: bool = True, hd: bool = False) -> Dict[str, torch.Tensor]:
     """One iteration of the reference's validation loop; ``seg_model`` must be in eval mode.  Returns device scalars.
     ``variant="mscmrseg"`` (``train_mscmrseg.py:67-92``): loss = BCE + Jaccard + point NN loss (l1 + l2 + l3), vert_loss
     (l3 or -1), dice = mean of classes 1..3.  ``variant="mmwhs"`` (``train_mmwhs.py:65-90``): l1 = double-softmax CE
-    (``softmax``) or BCE, loss = l1 + l2 WITHOUT the point term (:82), dice = mean of classes 1..4 (``metrics2``)."""
+    (``softmax``) or BCE, loss = l1 + l2 WITHOUT the point term (:82), dice = mean of classes 1..4 (``metrics2``).
+    ``hd``: also "hd_rows", the fp64 ``surface_metrics(gt, pred)`` rows of those classes with the batch's label maps
+    taken as one [B,H,W] volume (column 1: hd, column 7: empty flags)."""
     prediction, _, vert_s = seg_model(x)
     ms = variant == "mscmrseg"
     l1, l2 = L.seg_loss(prediction, y_onehot_u8, "sigmoid" if (ms or not softmax) else "softmax")
@@ -45,25 +59,82 @@ def valid_batch(seg_model, x: torch.Tensor, y_onehot_u8: torch.Tensor, z: Option
     else:
         vert = torch.full((), -1.0, dtype=torch.float32, device=x.device)
     c = prediction.shape[1]
-    dc = M.label_dice(M.argmax_labels(prediction), M.argmax_labels(y_onehot_u8), c)
-    return {"loss": loss, "vert_loss": vert, "dice": dc[1:(4 if ms else 5)].mean(), "dice_per_class": dc}
+    pred_lab, gt_lab = M.argmax_labels(prediction), M.argmax_labels(y_onehot_u8)
+    dc = M.label_dice(pred_lab, gt_lab, c)
+    r = {"loss": loss, "vert_loss": vert, "dice": dc[1:(4 if ms else 5)].mean(), "dice_per_class": dc}
+    if hd:
+        r["hd_rows"] = K.surface_metrics(gt_lab, pred_lab, _HD_CLASSES[variant])
+    return r
 
 
 def valid_model_with_one_dataset(seg_model, batches: Iterable, d4: bool = True, variant: str = "mscmrseg",
-                                 softmax: bool = True) -> Dict[str, float]:
-    """``train_mscmrseg.py:53-99`` without the Hausdorff option: means over the batches of dice / loss /
-    valid_vert_loss.  ``batches`` yields ``(x, y_onehot_u8, z)`` device tensors."""
+                                 softmax: bool = True, hd: bool = False) -> Dict[str, float]:
+    """``train_mscmrseg.py:53-99``: means over the batches of dice / loss / valid_vert_loss.  ``batches`` yields
+    ``(x, y_onehot_u8, z)`` device tensors.  ``hd=True`` adds "hd": the mean over the batches of the mean over the
+    classes of medpy ``hd(gt, pred)``; a class empty on either side of any batch raises medpy's RuntimeError at the
+    data set's one synchronisation (the reference raises at that batch)."""
     was_training = seg_model.training
     seg_model.eval()
     acc = {"dice": [], "loss": [], "vert_loss": []}
+    rows = []
     try:
         for x, y, z in batches:
-            r = valid_batch(seg_model, x, y, z, d4, variant, softmax)
+            r = valid_batch(seg_model, x, y, z, d4, variant, softmax, hd)
             for k in acc:
                 acc[k].append(r[k])
+            if hd:
+                rows.append(r["hd_rows"])
     finally:
         seg_model.train(was_training)
     if not acc["dice"]:
-        return {"dice": float("nan"), "loss": float("nan"), "valid_vert_loss": float("nan")}
-    means = torch.stack([torch.stack(acc[k]).mean() for k in ("dice", "loss", "vert_loss")]).tolist()   # one sync
-    return {"dice": means[0], "loss": means[1], "valid_vert_loss": means[2]}
+        out = {"dice": float("nan"), "loss": float("nan"), "valid_vert_loss": float("nan")}
+        if hd:
+            out["hd"] = float("nan")
+        return out
+    means = torch.stack([torch.stack(acc[k]).mean() for k in ("dice", "loss", "vert_loss")])
+    if not hd:
+        means = means.tolist()   # one sync
+        return {"dice": means[0], "loss": means[1], "valid_vert_loss": means[2]}
+    host = torch.cat([means.double(), torch.stack(rows).flatten()]).tolist()       # one sync
+    ncls = len(_HD_CLASSES[variant])
+    hd_list = []
+    for b in range(len(rows)):
+        cls_rows = [host[3 + (b * ncls + k) * 8:3 + (b * ncls + k + 1) * 8] for k in range(ncls)]
+        for row in cls_rows:
+            M.raise_if_empty(row[7])
+        hd_list.append(sum(cls_rows[k][1] for k in _HD_ORDER[variant]) / float(ncls))
+    return {"dice": host[0], "loss": host[1], "valid_vert_loss": host[2], "hd": float(np.mean(np.array(hd_list)))}
+
+
+@torch.no_grad()
+def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd: bool = True, ifasd: bool = True,
+                    variant: str = "mmwhs"):
+    """The device-side core of ``evaluate_segmentation`` (``evaluate_mmwhs.py:118-132``; ``evaluate_mscmrseg.py:132-169``
+    without its crop / resize): eval forward in batches of ``bs`` -> argmax -> ``keep_largest_connected_components``
+    (``klc``) -> the variant's ``metrics`` list ([dice, hd, asd] per class), with one synchronisation per volume.
+    ``x``: the volume's slices [Z,C,H,W] (fp32, device tensor or numpy); ``gt_labels``: its label volume [Z,H,W] (MM-WHS
+    1..4; MS-CMRSeg codes 200 / 500 / 600, which the predicted labels 1 / 2 / 3 are mapped to after ``klc``)."""
+    if variant not in ("mmwhs", "mscmrseg"):
+        raise ValueError("evaluate_volume: variant 'mmwhs' or 'mscmrseg'")
+    dev = next(seg_model.parameters()).device
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    x = x.to(dev)
+    was_training = seg_model.training
+    seg_model.eval()
+    try:
+        preds = []
+        for i in range(0, x.shape[0], bs):
+            out = seg_model(x[i:i + bs])
+            preds.append(M.argmax_labels(out[0] if isinstance(out, tuple) else out))
+    finally:
+        seg_model.train(was_training)
+    pred = torch.cat(preds)
+    if klc:
+        pred = U.keep_largest_connected_components(pred)
+    mod = EW if variant == "mmwhs" else EM
+    if variant == "mscmrseg":
+        lut = torch.arange(256, dtype=torch.int32, device=dev)
+        lut[1:4] = torch.tensor([200, 500, 600], dtype=torch.int32, device=dev)
+        pred = lut[pred.long()]
+    rows = M.class_metrics(M.to_device(gt_labels, dev), pred, mod.CLASSES).tolist()        # one sync
+    return mod.metrics_from_rows(rows, ifhd, ifasd)
