@@ -60,6 +60,14 @@ def _anc(tag: str, z):
     return z if _ANCHOR is None else _ANCHOR(tag, z)
 
 
+def _pool_anchored(tag: str, x):
+    """2x2 max-pool under an installed anchor: an anchor with a ``pool(tag, x)`` method takes it over (the tests pick
+    the element the other implementation's argmax chose: near-ties between two precisions otherwise route the gradient
+    differently)"""
+    pool = getattr(_ANCHOR, "pool", None)
+    return F.max_pool2d(x, 2) if pool is None else pool(tag, x)
+
+
 # --------------------------------------------------------------------------- #
 # configuration + parameter inventories
 # --------------------------------------------------------------------------- #
@@ -233,6 +241,12 @@ def make_params(shapes: Dict[str, Tuple[int, ...]], seed: int, *, std: float = 0
     return out
 
 
+def params_to(p: Params, dtype: Optional[torch.dtype] = None, device=None) -> Params:
+    """a copy of ``p`` with every floating-point tensor in ``dtype`` (e.g. float64 for a high-precision reference) and
+    every tensor on ``device``; integer buffers (``num_batches_tracked``) keep their type"""
+    return {k: v.to(device=device, dtype=dtype if v.is_floating_point() else None, copy=True) for k, v in p.items()}
+
+
 def is_trainable(key: str) -> bool:
     return not (key.endswith("running_mean") or key.endswith("running_var")
                 or key.endswith("num_batches_tracked"))
@@ -277,7 +291,7 @@ def _encoder(p: Params, x, cfg: SegCfg, training: bool):
         if i > 0:
             out = torch.cat([out, res], 1)
             out = F.leaky_relu(_conv(p, "encoder.conv1_%d.0" % (i + 1), out), 0.01)
-        out = F.max_pool2d(out, 2)
+        out = F.max_pool2d(out, 2) if _ANCHOR is None else _pool_anchored("encoder.pool%d" % (i + 1), out)
         res = out
     return out, skips
 
@@ -403,7 +417,7 @@ def _stn(p: Params, pre: str, x, k: int, training: bool, has_in: bool):
         h = _anc(pre + "fc%d" % i, F.linear(h, p[pre + "fc%d.weight" % i], p[pre + "fc%d.bias" % i]))
         h = F.relu(_norm1d(p, pre + "bn%d" % j, pre + "in%d" % j, h, training, batched))
     h = F.linear(h, p[pre + "fc3.weight"], p[pre + "fc3.bias"])
-    h = _anc(pre + "fc3", h + torch.eye(k, dtype=h.dtype).reshape(1, k * k))
+    h = _anc(pre + "fc3", h + torch.eye(k, dtype=h.dtype, device=h.device).reshape(1, k * k))
     return h.reshape(-1, k, k)
 
 
@@ -457,5 +471,5 @@ def pointnet_cls_forward(p: Params, x, *, feature_transform=False, sample_transf
 def feature_transform_regularizer(trans):
     """PointNetCls.py:217-224: mean Frobenius norm of (T T^T - I)."""
     d = trans.shape[1]
-    eye = torch.eye(d, dtype=trans.dtype)[None]
+    eye = torch.eye(d, dtype=trans.dtype, device=trans.device)[None]
     return torch.mean(torch.norm(torch.bmm(trans, trans.transpose(2, 1)) - eye, dim=(1, 2)))

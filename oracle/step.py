@@ -72,18 +72,29 @@ def _trainables(p: Optional[Params]):
     return [] if p is None else [v for k, v in p.items() if is_trainable(k)]
 
 
+def _host(t) -> np.ndarray:
+    """numpy view of a tensor on any device (a copy off the host), or of an array"""
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
 def _freeze(p: Optional[Params], flag: bool):
     for t in _trainables(p):
         t.requires_grad_(not flag)
 
 
 class OracleTrainer:
-    """Holds G / D1 / D2 / D4 parameter dicts + optimisers and runs reference steps."""
+    """Holds G / D1 / D2 / D4 parameter dicts + optimisers and runs reference steps.
+
+    The step runs in the dtype and on the device of the segmenter's parameters (float32 on the CPU by default; a test
+    may pass float64 parameters, on a GPU as well, through :func:`oracle.nets.params_to`): the inputs are converted to
+    them, the host metrics read the results back."""
 
     def __init__(self, seg_cfg: SegCfg, cfg: StepCfg, gen: Params, dis1: Optional[Params],
                  dis2: Optional[Params], dis4: Optional[Params]):
         self.seg_cfg, self.cfg = seg_cfg, cfg
         self.gen = _leafify(gen)
+        like = next(v for v in self.gen.values() if v.is_floating_point())
+        self._like = dict(dtype=like.dtype, device=like.device)      # where and in what the inputs are taken
         self.dis1 = _leafify(dis1) if (cfg.d1 and dis1 is not None) else None
         self.dis2 = _leafify(dis2) if (cfg.d2 and dis2 is not None) else None
         self.dis4 = _leafify(dis4) if (cfg.d4 and dis4 is not None) else None
@@ -132,8 +143,8 @@ class OracleTrainer:
         _freeze(self.gen, False)
 
         # 1. supervised pass on the source batch (train_mscmrseg.py:200-213)
-        xa = torch.as_tensor(img_a, dtype=torch.float32)
-        ya = torch.as_tensor(mask_a, dtype=torch.float32)
+        xa = torch.as_tensor(img_a, **self._like)
+        ya = torch.as_tensor(mask_a, **self._like)
         o_s, vert_s = seg_forward(self.gen, xa, self.seg_cfg, training=True)
         if ms or not c.softmax:
             l_bce, l_jac = L.seg_loss_sigmoid(o_s, ya)
@@ -141,7 +152,7 @@ class OracleTrainer:
             l_bce, l_jac = L.seg_loss_softmax(o_s, ya)
         l_pt = 0.0
         if c.d4 or (c.d4aux and not ms):
-            l_pt = L.batch_nn_loss(vert_s, torch.as_tensor(vert_a, dtype=torch.float32))
+            l_pt = L.batch_nn_loss(vert_s, torch.as_tensor(vert_a, **self._like))
             out["ver_s_loss"] = float(l_pt.detach())
         loss1 = l_bce + l_jac + c.wp * l_pt
         emap_s = None
@@ -154,8 +165,8 @@ class OracleTrainer:
         out["seg_loss"] = _f(l_bce + l_jac)
         out["loss_bce"], out["loss_jac"] = _f(l_bce), _f(l_jac)
         loss1.backward()
-        hard = M.soft_to_hard_pred(o_s.detach().numpy(), 1)             # :215-216
-        out["seg_dice"] = M.dice_coef_multilabel(np.asarray(mask_a), hard, c.n_class)
+        hard = M.soft_to_hard_pred(_host(o_s), 1)             # :215-216
+        out["seg_dice"] = M.dice_coef_multilabel(_host(mask_a), hard, c.n_class)
         if keep:
             self.kept = {"grad_seg": {k: v.grad.clone() for k, v in self.gen.items()
                                       if is_trainable(k) and v.grad is not None},
@@ -163,7 +174,7 @@ class OracleTrainer:
                          "vertS": None if vert_s is None else vert_s.detach().clone()}
 
         # 2. adversarial pass on the target batch (:218-247)
-        xb = torch.as_tensor(img_b, dtype=torch.float32)
+        xb = torch.as_tensor(img_b, **self._like)
         o_t, vert_t = seg_forward(self.gen, xb, self.seg_cfg, training=True)
         pred_s, pred_t = self._pred(o_s), self._pred(o_t)
         emap_t = self._entropy(o_t) if (c.d2 or not ms) else None
@@ -177,7 +188,7 @@ class OracleTrainer:
         if c.d2:
             a2 = c.dr * L.bce_logits_const(self._d_img(self.dis2, emap_t), 1.0)
         if c.d4 or (c.d4aux and not ms):
-            out["ver_t_loss"] = float(L.batch_nn_loss(vert_t, torch.as_tensor(vert_b, dtype=torch.float32)))
+            out["ver_t_loss"] = float(L.batch_nn_loss(vert_t, torch.as_tensor(vert_b, **self._like)))
         if c.d4:
             a4 = c.dr * L.bce_logits_const(self._d_pts(vert_t), 1.0)
         if c.d1:
@@ -216,17 +227,17 @@ class OracleTrainer:
                 d = self._d_img(self.dis2, e)
                 l = L.bce_logits_const(d, label); l.backward()
                 out["d2_loss_" + tag] = _f(l)
-                out["dis2_acc_" + tag] = M.disc_accuracy(d.detach().numpy(), label == 1.0)
+                out["dis2_acc_" + tag] = M.disc_accuracy(_host(d), label == 1.0)
             if c.d1:
                 d = self._d_img(self.dis1, i1)
                 l = L.bce_logits_const(d, label); l.backward()
                 out["d1_loss_" + tag] = _f(l)
-                out["dis1_acc_" + tag] = M.disc_accuracy(d.detach().numpy(), label == 1.0)
+                out["dis1_acc_" + tag] = M.disc_accuracy(_host(d), label == 1.0)
             if c.d4:
                 d = self._d_pts(v.detach())
                 l = L.bce_logits_const(d, label); l.backward()
                 out["d4_loss_" + tag] = _f(l)
-                out["dis4_acc_" + tag] = M.disc_accuracy(d.detach().numpy(), label == 1.0)
+                out["dis4_acc_" + tag] = M.disc_accuracy(_host(d), label == 1.0)
 
         if c.d1 or c.d2 or c.d4:
             d_phase("src", 1.0, emap_s, in1_s, vert_s)

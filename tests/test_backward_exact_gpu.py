@@ -14,122 +14,18 @@ import numpy as np
 import pytest
 import torch
 
+from anchor_helpers import PRE_TOL, SEG_CHAIN_TOL, TOL, flat_named  # noqa: F401
+from anchor_helpers import anchor_from as _anchor_from, compare_grads as _compare_grads, disc_table as _disc_table
+from anchor_helpers import load as _load, pn_table as _pn_table, random_running_stats as _random_running_stats
+from anchor_helpers import seg_table as _seg_table, unlrelu as _unlrelu  # noqa: F401  (test_boundary_extras_gpu.py)
+
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-4
-# whole-step segmenter gradients: worst-case linear accumulation of 2 x 2^-17 per convolution layer over the 29 + 5 layers
-# between the adversarial loss and the first encoder block (derivation in test_train_step_backward_shared_routing)
-SEG_CHAIN_TOL = 2 * (29 + 5) * 2.0 ** -17
-
-
-def _load(mod, params, dev):
-    mod.load_state_dict({k: v.clone() for k, v in params.items()}, strict=True)
-    return mod.to(dev).train()
-
-
-def _unlrelu(a, slope):
-    """pre-activation with the sign (and, up to one rounding, the value) the HIP kernel saw"""
-    a = a.detach().float().cpu()
-    return a if slope == 1.0 else torch.where(a > 0, a, a / slope)
-
-
-PRE_TOL = 2e-4      # layer-local forward bound (below)
-
-
-def _anchor_from(table, used, worst=None):
-    """With every upstream output anchored, the difference between the restatement's output of a layer and the HIP
-    kernels' BEFORE it is anchored is that layer's own arithmetic error (bf16x3 products, fp32 accumulation order):
-    held to 2e-4 of the tensor's scale; ``worst`` collects the largest one per network for the test's report."""
-    def fn(tag, z):
-        if tag not in table:
-            return z
-        used.add(tag)
-        v = table[tag]
-        if isinstance(v, tuple):          # (post-ReLU value, True): share the mask, keep own value where inactive
-            y = v[0].detach().float().cpu().reshape(z.shape)
-            tgt = torch.where(y > 0, y, torch.clamp(z.detach(), max=0.0))
-        else:
-            tgt = v.reshape(z.shape)
-        e = rel_err(z, tgt)
-        if worst is not None and e > worst.get("e", 0.0):
-            worst["e"], worst["tag"] = e, tag
-        assert e < PRE_TOL, (tag, e)      # the two forward passes agree, layer by layer, before anchoring
-        return z + (tgt - z).detach()
-    return fn
-
-
-def _compare_grads(named_hip, grads_ref, tol=TOL, parts=None):
-    """``parts``: name -> one of two partial gradients whose sum ``grads_ref`` is (the discriminators' source and target
-    passes, which largely cancel at initialisation): the error is then taken relative to the larger PART's scale"""
-    worst = ("", 0.0)
-    total = sum(float(g.double().norm()) ** 2 for g in grads_ref.values() if g is not None) ** 0.5
-    for k, p in named_hip:
-        g = grads_ref.get(k)
-        if g is None:
-            assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
-            continue
-        # (a bias in front of a BatchNorm has an exactly-zero true gradient: both sides hold rounding noise there)
-        if float(g.double().norm()) < 1e-5 * total:
-            assert float(p.grad.double().norm()) < 1e-4 * total, k
-            continue
-        e = rel_err(p.grad, g)
-        if parts is not None:
-            scale = max(float(parts[k].abs().max()), float((g - parts[k]).abs().max()), float(g.abs().max()))
-            e = float((p.grad.detach().double().cpu() - g.double()).abs().max()) / max(scale, 1e-30)
-        if e >= tol and float((p.grad.detach().double().cpu() - g.double()).abs().max()) <= 1e-6 * total:
-            continue      # a near-zero gradient (just above the floor above): rounding noise on both sides
-        if e > worst[1]:
-            worst = (k, e)
-        assert e < tol, (k, e)
-    return worst
-
-
-def _random_running_stats(params, seed):
-    rng = np.random.default_rng(seed + 7)
-    for k in params:
-        if ".in" in k or k.startswith("in"):
-            continue
-        if k.endswith("running_mean"):
-            params[k] = torch.from_numpy(rng.normal(0, 0.2, tuple(params[k].shape)).astype(np.float32))
-        if k.endswith("running_var"):
-            params[k] = torch.from_numpy(rng.uniform(0.5, 1.5, tuple(params[k].shape)).astype(np.float32))
-
-
-def _seg_table(S, cfg, logits, verts):
-    """anchor table of one segmenter forward pass: pre-activation outputs of every convolution the HIP engine kept"""
-    table = {"classifier": logits.detach().float().cpu()}
-    for blk in ["encoder.encoder%d" % (i + 1) for i in range(cfg.n_block)] + \
-               ["decoder.decoder2_%d" % (i + 1) for i in range(cfg.n_block)]:
-        _, _, a0, _, a1, _ = S[blk]
-        table[blk + ".0"], table[blk + (".3" if cfg.batchnorm else ".2")] = _unlrelu(a0, 0.01), _unlrelu(a1, 0.01)
-    for i in range(1, cfg.n_block):
-        c1 = "encoder.conv1_%d.0" % (i + 1)
-        table[c1] = _unlrelu(S[c1][2], 0.01)
-    for j, o in enumerate(S["bott_outs"]):
-        table["bottleneck.bottleneck%d.0" % (j + 1)] = _unlrelu(o, 0.01)
-    if cfg.pointnet:
-        table["pointNet.final_conv"] = _unlrelu(S["head"][1], 0.01)
-        for nm, _, o in S["head_ext"]:
-            table[nm] = _unlrelu(o, 0.01)
-        table["pointNet.final_fc"] = verts.detach().float().cpu()
-    return table
-
-
-def _disc_table(model):
-    names = [n for n, _ in model._chain]
-    acts = model._last_acts
-    return {n: _unlrelu(acts[i + 1], 0.2 if i < len(names) - 1 else 1.0) for i, n in enumerate(names)}
-
-
-def _pn_table(trace):
-    table = {}
-    for k, v in trace.items():
-        table[k] = (v[0], True) if (isinstance(v, tuple) and v[1]) else (v[0] if isinstance(v, tuple) else v)
-        if not isinstance(table[k], tuple):
-            table[k] = table[k].detach().float().cpu()
-    return table
+# TOL, PRE_TOL and SEG_CHAIN_TOL (worst-case linear accumulation of 2 x 2^-17 per convolution layer over the 29 + 5
+# layers between the adversarial loss and the first encoder block, derivation in test_train_step_backward_shared_routing)
+# live in anchor_helpers, with the anchoring helpers this module shares with test_production_grads_gpu.py
 
 
 @pytest.mark.parametrize("cfg_kw,softmax,b,hw,seed", [
@@ -364,20 +260,9 @@ def test_train_step_backward_shared_routing(dev, variant, pn_kw, in_ch, n_class,
         for k in ("entropy_loss", "entropy_loss_T"):
             assert abs(h[k] - q[k]) <= 1e-5 * max(1.0, abs(q[k])), (k, h[k], q[k])
 
-    def flat_named(mod, snap):
-        out_, off = [], 0
-        for k, p in mod.named_parameters():
-            n = p.numel()
-            out_.append((k, snap[off:off + n].view(p.shape)))
-            off += (n + 63) // 64 * 64
-        return out_
-
-    class _G:      # _compare_grads reads ``.grad``
-        def __init__(self, g):
-            self.grad = g
     report = []
     for nm, mod in (("grad_seg", gen), ("grad_total", gen), ("grad_d1", d1), ("grad_d2", d2), ("grad_d4", d4)):
-        named = [(k, _G(g)) for k, g in flat_named(mod, tr.last[nm])]
+        named = flat_named(mod, tr.last[nm])
         ref = orc.kept[nm]
         w = _compare_grads(named, ref, tol=SEG_CHAIN_TOL if mod is gen else TOL, parts=orc.kept.get(nm + "_src"))
         report.append("%s %s %.2e" % (nm, w[0], w[1]))
