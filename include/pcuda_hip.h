@@ -223,9 +223,14 @@ int pcuda_bn_finalize(const float* partials, int ntiles, int c, long long count,
  * returns ntiles written through *ntiles (query with partials == NULL) */
 int pcuda_bn_stats(const float* a, long long sn, long long sc, int n, int c, long long hw,
                    float* partials, int* ntiles, pcuda_stream_t s);
-/* y = a*scale[c] + shift[c]; optional relu (PointNetCls.py:41-43) */
+/* y = a*scale[c] + shift[c]; ``flags``: PCUDA_BN_APPLY_RELU then relu (PointNetCls.py:41-43); PCUDA_BN_APPLY_FMA
+   rounds once, fmaf(a, scale, shift), as the convolutions apply a pending BatchNorm in their load (a sub-module that
+   returns a block output computes what the next layer of the fused network would read); without it a*scale is
+   rounded before the add */
+#define PCUDA_BN_APPLY_RELU 1
+#define PCUDA_BN_APPLY_FMA 2
 int pcuda_bn_apply(const float* a, long long a_sn, long long a_sc, const float* scale, const float* shift,
-                   int relu, float* y, long long y_sn, long long y_sc, int n, int c, long long hw,
+                   int flags, float* y, long long y_sn, long long y_sc, int n, int c, long long hw,
                    pcuda_stream_t s);
 /* backward of [z -> a = lrelu(z, slope) -> y = BN(a)] given dy (optionally dy + dy2):
  * pass 1: per-tile partials of (sum dy, sum dy*xhat) -> red[ntiles][c][2]

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
   }
 }
 
-template <int VEC>
+template <int VEC, bool FMA>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ a, long long a_sn, long long a_sc,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
                                                        int relu, float* __restrict__ y, long long y_sn, long long y_sc,
@@ -131,7 +131,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     vload<VEC>(pa + i, v);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      v[e] = v[e] * sc + sf;
+      // (PCUDA_BN_APPLY_FMA: one rounding, as the convolutions apply a lazy BatchNorm in their load; the default multiply
+      //  then add is what PointNetCls has always computed -- the build contracts nothing on its own, -ffp-contract=off)
+      v[e] = FMA ? fmaf(v[e], sc, sf) : v[e] * sc + sf;
       if (relu) v[e] = v[e] > 0.f ? v[e] : 0.f;
     }
     vstore<VEC>(py + i, v);
@@ -591,16 +593,16 @@ extern "C" int pcuda_bn_finalize(const float* partials, int ntiles, int c, long 
 }
 
 extern "C" int pcuda_bn_apply(const float* a, long long a_sn, long long a_sc, const float* scale, const float* shift,
-                              int relu, float* y, long long y_sn, long long y_sc, int n, int c, long long hw,
+                              int flags, float* y, long long y_sn, long long y_sc, int n, int c, long long hw,
                               pcuda_stream_t s) {
   if (!dims_ok(n, c, hw) || !a || !y || !scale || !shift) PCUDA_FAIL(PCUDA_E_BADARG, "bn_apply: bad arguments");
   ProfScope prof(PCUDA_FAM_POINTWISE, 8.0 * n * c * (double)hw, (hipStream_t)s);
-  if (vec_ok(a, a_sn, a_sc, hw) && vec_ok(y, y_sn, y_sc, hw))
-    hipLaunchKernelGGL(bn_apply_kernel<4>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, a, a_sn, a_sc, scale,
-                       shift, relu, y, y_sn, y_sc, hw);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<1>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, a, a_sn, a_sc, scale,
-                       shift, relu, y, y_sn, y_sc, hw);
+  const bool vec = vec_ok(a, a_sn, a_sc, hw) && vec_ok(y, y_sn, y_sc, hw);
+  const int relu = (flags & PCUDA_BN_APPLY_RELU) ? 1 : 0;
+  auto kern = (flags & PCUDA_BN_APPLY_FMA) ? (vec ? bn_apply_kernel<4, true> : bn_apply_kernel<1, true>)
+                                           : (vec ? bn_apply_kernel<4, false> : bn_apply_kernel<1, false>);
+  hipLaunchKernelGGL(kern, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, a, a_sn, a_sc, scale, shift, relu, y, y_sn,
+                     y_sc, hw);
   PCUDA_CHECK_LAUNCH("bn_apply_kernel");
   return PCUDA_OK;
 }

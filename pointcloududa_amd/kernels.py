@@ -423,12 +423,15 @@ def bn_stats(a: torch.Tensor):
     return partials, nt.value, n * hw
 
 
-def bn_apply(a: torch.Tensor, st: BNState, relu=False, out=None):
+def bn_apply(a: torch.Tensor, st: BNState, relu=False, out=None, fma=False):
+    """a * scale + shift per channel (then relu).  ``fma``: rounded once, as a convolution applies a pending BatchNorm
+    (``TA``) in its load -- the value the fused network's next layer reads"""
     n, c, hw, sn, sc = _planes(a)
     if out is None:
         out = torch.empty_like(a, memory_format=torch.contiguous_format)
     _, _, _, osn, osc = _planes(out)
-    check(L.lib().pcuda_bn_apply(a.data_ptr(), sn, sc, st.scale.data_ptr(), st.shift.data_ptr(), 1 if relu else 0,
+    flags = (1 if relu else 0) | (2 if fma else 0)      # PCUDA_BN_APPLY_RELU | PCUDA_BN_APPLY_FMA
+    check(L.lib().pcuda_bn_apply(a.data_ptr(), sn, sc, st.scale.data_ptr(), st.shift.data_ptr(), flags,
                                  out.data_ptr(), osn, osc, n, c, hw, _stream()), "bn_apply")
     return out
 

@@ -10,6 +10,9 @@ into ``param.grad`` directly.
 Batch size 1 takes the reference down an InstanceNorm path (PointNetCls.py:47-55, 210-212) that raises inside
 the reference itself (InstanceNorm1d on the 2-D output of fc1): the same RuntimeError is raised here, and per-rank
 batches must be >= 2, as SURVEY section 7 notes for data parallelism.
+
+``STN3d``, ``STNkd`` and ``PointNetfeat`` also run on their own, on the same tape over their own parameters; at batch size
+1 they raise or compute as the reference does (STN3d: its InstanceNorm branch; STNkd in training: bn4 on [1, 512]).
 """
 from __future__ import annotations
 
@@ -19,6 +22,17 @@ from torch import nn
 
 from .. import kernels as K
 from ._holders import BatchNorm1d, Conv1d, InstanceNorm1d, Linear, Marker, ensure_grad
+
+
+_eyes = {}
+
+
+def _identity(k, device):
+    """the flattened k x k identity the T-Nets add to fc3's output (PointNetCls.py:59-62, 98-101), one per device"""
+    key = (k, str(device))
+    if key not in _eyes:
+        _eyes[key] = torch.eye(k, dtype=torch.float32, device=device).reshape(k * k).contiguous()
+    return _eyes[key]
 
 
 class _Var:
@@ -36,6 +50,7 @@ class _Tape:
 
     def __init__(self, module, training):
         self.m, self.training, self.steps = module, training, []
+        self.bns = []      # the BatchNorm layers this pass ran
         self.P = dict(module.named_parameters())
         # which parameters want a gradient is decided when the forward pass is recorded, as autograd does
         self.wants = {k for k, p in self.P.items() if p.requires_grad}
@@ -82,9 +97,13 @@ class _Tape:
 
     def _bn(self, a: _Var, bn: str, relu: bool, part=None, nt=0) -> _Var:
         P = self.P
+        self.bns.append(bn)
         n, c = a.t.shape[0], a.t.shape[1]
         cnt = a.t.numel() // c
         if self.training:
+            if cnt == 1:      # a standalone STNkd / PointNetfeat at batch size 1: torch's BatchNorm raises here too
+                raise RuntimeError("Expected more than 1 value per channel when training, got input size %s (%s)"
+                                   % (tuple(a.t.shape), bn))
             if part is None:
                 part, nt, cnt = K.bn_stats(a.t)
             st = K.bn_finalize(part, nt, cnt, P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
@@ -168,7 +187,7 @@ class _Tape:
         g = self.max_points(h)
         g = self.linear_bn(g, pre + "fc1", pre + "bn4")
         g = self.linear_bn(g, pre + "fc2", pre + "bn5")
-        iden = self.m._identity(k, x.t.device)
+        iden = _identity(k, x.t.device)
         t = self.linear(g, pre + "fc3", bias_plus=iden)
         out = _Var(t.t.view(-1, k, k))
 
@@ -178,46 +197,70 @@ class _Tape:
         self.steps.append(bwd)
         return out
 
+    def global_concat(self, g: _Var, pf: _Var) -> _Var:
+        """cat([g repeated over the N points, pf], 1) (PointNetCls.py:166-168): a copy on torch going forward; going back
+        the first channels' gradient is summed over the points on the channel-sum kernel"""
+        b, c = g.t.shape
+        n = pf.t.shape[2]
+        y = _Var(torch.cat([g.t.view(b, c, 1).expand(b, c, n), pf.t], 1))
+
+        def bwd():
+            if y.g is None:
+                return
+            dg = torch.empty(b * c, dtype=torch.float32, device=y.g.device)
+            K.channel_sum(y.g[:, :c].contiguous().view(1, b * c, n), dg, accumulate=False)
+            g.acc(dg.view(b, c))
+            pf.acc(y.g[:, c:].contiguous())
+        self.steps.append(bwd)
+        return y
+
+
+def _bump_tracked(module):
+    """num_batches_tracked += 1 on every BatchNorm layer of ``module`` (the InstanceNorm layers run on no path)"""
+    flat = getattr(module, "_flat_tracked", None)
+    if flat is not None:   # (still the buffers' storage?  module.to() / a re-registered buffer leaves the flat tensor behind)
+        first = next((b for k, b in module.named_buffers() if k.endswith("num_batches_tracked")), None)
+        if first is None or first.data_ptr() != flat.data_ptr():
+            flat = None
+    if flat is not None:
+        # (optim.flatten_module re-seated every num_batches_tracked buffer as a view of ONE int64 tensor, in
+        #  named_buffers() order: one launch with a 0 / 1 mask instead of one per BatchNorm layer -- 32 per step)
+        mask = getattr(module, "_tracked_mask", None)
+        if mask is None or mask.device != flat.device or mask.numel() != flat.numel():
+            names = [k for k, _ in module.named_buffers() if k.endswith("num_batches_tracked")]
+            mask = torch.tensor([1 if (".in" not in k and not k.startswith("in")) else 0 for k in names],
+                                dtype=torch.long, device=flat.device)
+            module._tracked_mask = mask
+        flat.add_(mask)
+    else:
+        for k, b in module.named_buffers():
+            if k.endswith("num_batches_tracked") and ".in" not in k and not k.startswith("in"):
+                b.add_(1)
+
+
+_BATCH1 = ("%s: batch size 1 takes the reference's InstanceNorm1d branch, which fails in the reference too (%sin4 on a "
+           "2-D [1, 512] tensor: running_mean should contain 1 elements not 512); use a per-rank batch of at least 2")
+
 
 class _PointNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x, drop_mask, *params):
-        if x.shape[0] < 2:
+        if x.shape[0] < 2 and module._batch1_at is not None:
             # The reference's batch-1 branch (PointNetCls.py:47-55) hands the 2-D [1, 512] output of fc1 to
             # InstanceNorm1d(512): torch 1.4 (the reference's version) raises "InstanceNorm1d returns 0-filled tensor
             # to 2D tensor", current torch raises "running_mean should contain 1 elements not 512" -- the branch cannot
             # execute in the reference either (pinned in tests/golden/param_counts.npz: pncls_batch1_raises).  Same
             # error behaviour here: a RuntimeError naming the layer.
-            raise RuntimeError("PointNetCls: batch size 1 takes the reference's InstanceNorm1d branch, which fails in "
-                               "the reference too (feat.stn.in4 on a 2-D [1, 512] tensor: running_mean should contain "
-                               "1 elements not 512); use a per-rank batch of at least 2")
+            raise RuntimeError(_BATCH1 % (type(module).__name__, module._batch1_at))
         if not x.is_cuda:
-            raise RuntimeError("PointNetCls runs on HIP devices only (no CPU fallback)")
+            raise RuntimeError("%s runs on HIP devices only (no CPU fallback)" % type(module).__name__)
         tape = _Tape(module, module.training)
         xin = _Var(x.contiguous().float())
         y, trans, trans_feat = module._run(tape, xin, drop_mask)
         if tape.trace is not None:
             module._last_trace = tape.trace
         if module.training:
-            flat = getattr(module, "_flat_tracked", None)
-            if flat is not None:   # (still the buffers' storage?  module.to() / a re-registered buffer leaves the flat tensor behind)
-                first = next((b for k, b in module.named_buffers() if k.endswith("num_batches_tracked")), None)
-                if first is None or first.data_ptr() != flat.data_ptr():
-                    flat = None
-            if flat is not None:
-                # (optim.flatten_module re-seated every num_batches_tracked buffer as a view of ONE int64 tensor, in
-                #  named_buffers() order: one launch with a 0 / 1 mask instead of one per BatchNorm layer -- 32 per step)
-                mask = getattr(module, "_tracked_mask", None)
-                if mask is None or mask.device != flat.device or mask.numel() != flat.numel():
-                    names = [k for k, _ in module.named_buffers() if k.endswith("num_batches_tracked")]
-                    mask = torch.tensor([1 if (".in" not in k and not k.startswith("in")) else 0 for k in names],
-                                        dtype=torch.long, device=flat.device)
-                    module._tracked_mask = mask
-                flat.add_(mask)
-            else:
-                for k, b in module.named_buffers():
-                    if k.endswith("num_batches_tracked") and ".in" not in k and not k.startswith("in"):
-                        b.add_(1)
+            module._bump_tracked(tape)
         ctx.tape, ctx.vars = tape, (xin, y, trans, trans_feat)
         ctx.set_materialize_grads(False)
         outs = (y.t, trans.t if trans is not None else x.new_zeros(()),
@@ -259,27 +302,60 @@ def _stn_members(mod, cin, kout, with_in):
         mod.in5 = InstanceNorm1d(256, track_running_stats=True)
 
 
-class STN3d(nn.Module):
+class _PNStage(nn.Module):
+    """STN3d / STNkd / PointNetfeat called on their own: the same recorded tape as inside PointNetCls, over this
+    module's own parameters (one autograd node per call)"""
+    _batch1_at = None      # prefix of the STN3d whose InstanceNorm branch a batch of 1 reaches (None: it computes)
+
+    def forward(self, x):
+        y, trans, trans_feat = _PointNetFn.apply(self, x, None, *self.parameters())
+        return self._outputs(y, trans, trans_feat)
+
+    def _bump_tracked(self, tape):
+        for bn in tape.bns:      # the layers that ran (PointNetfeat(sample_transform=False) leaves its STN3d's counters alone)
+            tape.P[bn + ".num_batches_tracked"].add_(1)
+
+
+class STN3d(_PNStage):
+    """PointNetCls.py:11-63.  forward(x[B,dim,N]) -> [B,3,3].  Batch size 1 raises as in the reference (in4)."""
+    _batch1_at = ""
+
     def __init__(self, dim=3):
         super().__init__()
         _stn_members(self, dim, 9, with_in=True)
 
+    def _run(self, tape: _Tape, x: _Var, drop_mask):
+        return tape.stn(x, "", 3), None, None
 
-class STNkd(nn.Module):
+    def _outputs(self, y, trans, trans_feat):
+        return y
+
+
+class STNkd(_PNStage):
+    """PointNetCls.py:66-102.  forward(x[B,k,N]) -> [B,k,k].  Batch size 1: raises in training (bn4 on [1, 512]),
+    computes in eval mode, as in the reference."""
+
     def __init__(self, k=64):
         super().__init__()
         _stn_members(self, k, k * k, with_in=False)
         self.k = k
 
+    def _run(self, tape: _Tape, x: _Var, drop_mask):
+        return tape.stn(x, "", self.k), None, None
 
-class PointNetfeat(nn.Module):
+    def _outputs(self, y, trans, trans_feat):
+        return y
+
+
+class PointNetfeat(_PNStage):
+    """PointNetCls.py:104-168.  forward(x[B,3,N]) -> (feat, trans|None, trans_feat|None); feat is the [B,1024] global
+    feature, or with ``global_feat=False`` cat([global feature repeated over the N points, point features], 1), [B,1088,N]"""
+
     def __init__(self, global_feat=True, feature_transform=False, sample_transform=True, kernel_size=1, stride=1,
                  in_channel=3, dim=3, ext=False):
         super().__init__()
         if kernel_size != 1 or stride != 1:
             raise NotImplementedError("PointNetfeat: only kernel_size=1, stride=1 (the reference's defaults)")
-        if not global_feat:
-            raise NotImplementedError("PointNetfeat(global_feat=False) is never used by PointNetCls")
         self.stn = STN3d(dim=dim)
         self._ext = ext
         if ext:
@@ -299,6 +375,39 @@ class PointNetfeat(nn.Module):
         self._sample_transform = sample_transform
         if feature_transform:
             self.fstn = STNkd(k=64)
+
+    @property
+    def _batch1_at(self):
+        return "stn." if self._sample_transform else None
+
+    def _feat(self, tape: _Tape, x: _Var, pre: str):
+        """PointNetCls.py:136-163 -> (global feature [B,1024], point features, trans, trans_feat); ``pre``: this module's
+        prefix in the tape's parameter names"""
+        trans = trans_feat = None
+        if self._sample_transform:
+            trans = tape.stn(x, pre + "stn.", 3)
+            x = tape.transform(x, trans)
+        h = tape.conv_bn(x, pre + "conv1", pre + "bn1", True)
+        if self._ext:
+            h = tape.conv_bn(h, pre + "conv1_1", pre + "bn1_1", True)
+        if self.feature_transform:
+            trans_feat = tape.stn(h, pre + "fstn.", 64)
+            h = tape.transform(h, trans_feat)
+        pointfeat = h
+        h = tape.conv_bn(h, pre + "conv2", pre + "bn2", True)
+        if self._ext:
+            h = tape.conv_bn(h, pre + "conv2_1", pre + "bn2_1", True)
+        h = tape.conv_bn(h, pre + "conv3", pre + "bn3", False)
+        if self._ext:
+            h = tape.conv_bn(h, pre + "conv3_1", pre + "bn3_1", True)
+        return tape.max_points(h), pointfeat, trans, trans_feat
+
+    def _run(self, tape: _Tape, x: _Var, drop_mask):
+        g, pointfeat, trans, trans_feat = self._feat(tape, x, "")
+        return (g if self.global_feat else tape.global_concat(g, pointfeat)), trans, trans_feat
+
+    def _outputs(self, y, trans, trans_feat):
+        return (y, trans if self._sample_transform else None, trans_feat if self.feature_transform else None)
 
 
 class PointNetCls(nn.Module):
@@ -323,33 +432,14 @@ class PointNetCls(nn.Module):
         self.in2 = InstanceNorm1d(256, track_running_stats=True)
         self.relu = Marker("ReLU")
         # heinit / cvinit only touch nn.Conv2d modules in the reference (PointNetCls.py:187-202): none exist here
-        self._eyes = {}
 
-    def _identity(self, k, device):
-        key = (k, str(device))
-        if key not in self._eyes:
-            self._eyes[key] = torch.eye(k, dtype=torch.float32, device=device).reshape(k * k).contiguous()
-        return self._eyes[key]
+    _batch1_at = "feat.stn."      # batch size 1 raises (PointNetCls.py:47-55, 210-212: the reference's InstanceNorm branch)
+
+    def _bump_tracked(self, tape):
+        _bump_tracked(self)
 
     def _run(self, tape: _Tape, x: _Var, drop_mask):
-        f = self.feat
-        trans = trans_feat = None
-        if f._sample_transform:
-            trans = tape.stn(x, "feat.stn.", 3)
-            x = tape.transform(x, trans)
-        h = tape.conv_bn(x, "feat.conv1", "feat.bn1", True)
-        if f._ext:
-            h = tape.conv_bn(h, "feat.conv1_1", "feat.bn1_1", True)
-        if f.feature_transform:
-            trans_feat = tape.stn(h, "feat.fstn.", 64)
-            h = tape.transform(h, trans_feat)
-        h = tape.conv_bn(h, "feat.conv2", "feat.bn2", True)
-        if f._ext:
-            h = tape.conv_bn(h, "feat.conv2_1", "feat.bn2_1", True)
-        h = tape.conv_bn(h, "feat.conv3", "feat.bn3", False)
-        if f._ext:
-            h = tape.conv_bn(h, "feat.conv3_1", "feat.bn3_1", True)
-        g = tape.max_points(h)
+        g, _, trans, trans_feat = self.feat._feat(tape, x, "feat.")
         g = tape.linear_bn(g, "fc1", "bn1")
         g = tape.linear_bn(g, "fc2", "bn2", mask=drop_mask)
         y = tape.linear(g, "fc3")

@@ -9,6 +9,9 @@ channel concatenation folded into the convolution's addressing).
 Gradients of the parameters are accumulated straight into ``param.grad`` (created on first use)
 instead of being returned through autograd: the train step keeps them in one flat buffer per
 network, which is also what gets all-reduced over RCCL.
+
+``Encoder``, ``Bottleneck``, ``PointNet`` and ``Decoder`` also run on their own (the reference's forward signatures and
+return values), one autograd node per call over the engine's stage methods; inside a network they use its engine.
 """
 from __future__ import annotations
 
@@ -32,7 +35,10 @@ class _SegEngine:
     """forward / hand-written backward of Segmentation_model_Point over a name->tensor dict"""
 
     def __init__(self, filters, in_channels, n_block, depth, n_class, pointnet, fc_inch, extpn=False, batchnorm=True,
-                 feature_dis=False):
+                 feature_dis=False, parts=None, head_ch=None, num_points=300):
+        """``parts``: the stages whose layers this engine holds (default: the whole network); a sub-module that runs on its
+        own (``Encoder`` / ``Bottleneck`` / ``PointNet`` / ``Decoder`` outside a network) builds an engine of its one stage.
+        ``head_ch`` / ``num_points``: the point head's input channels (default 512 * filters / 32) and points"""
         f = filters
         self.f, self.cin, self.nb, self.depth, self.ncls, self.pointnet, self.fc_inch = \
             f, in_channels, n_block, depth, n_class, pointnet, fc_inch
@@ -40,36 +46,43 @@ class _SegEngine:
         self.bn = bool(batchnorm)
         self.c2 = ".3" if self.bn else ".2"      # index of a block's second convolution inside its nn.Sequential (unet.py:23-30)
         self.feature_dis = bool(feature_dis)
+        self.head_ch = 512 * f // 32 if head_ch is None else head_ch
+        self.npts = num_points
         self.after_deep_grads = None      # optional hook of the backward pass (see ``backward``)
+        parts = ("encoder", "bottleneck", "pointNet", "decoder", "classifier") if parts is None else parts
         ops = {}
-        for i in range(n_block):
-            co = f * 2 ** i
-            ci = in_channels if i == 0 else f * 2 ** (i - 1)
-            blk = "encoder.encoder%d" % (i + 1)
-            ops[blk + ".0"] = ConvOp(ci, co, 3, pad=1)
-            ops[blk + self.c2] = ConvOp(co, co, 3, pad=1)
-            if i > 0:
-                ops["encoder.conv1_%d.0" % (i + 1)] = ConvOp(ci * 3, co, 1)
-        co, ci = f * 2 ** n_block, f * 2 ** (n_block - 1)
-        for j in range(depth):
-            d = 2 ** j
-            ops["bottleneck.bottleneck%d.0" % (j + 1)] = ConvOp(ci, co, 3, pad=d, dil=d)
-            ci = co
-        if pointnet:
-            ch = 512 * f // 32
+        if "encoder" in parts:
+            for i in range(n_block):
+                co = f * 2 ** i
+                ci = in_channels if i == 0 else f * 2 ** (i - 1)
+                blk = "encoder.encoder%d" % (i + 1)
+                ops[blk + ".0"] = ConvOp(ci, co, 3, pad=1)
+                ops[blk + self.c2] = ConvOp(co, co, 3, pad=1)
+                if i > 0:
+                    ops["encoder.conv1_%d.0" % (i + 1)] = ConvOp(ci * 3, co, 1)
+        if "bottleneck" in parts:
+            co, ci = f * 2 ** n_block, f * 2 ** (n_block - 1)
+            for j in range(depth):
+                d = 2 ** j
+                ops["bottleneck.bottleneck%d.0" % (j + 1)] = ConvOp(ci, co, 3, pad=d, dil=d)
+                ci = co
+        if pointnet and "pointNet" in parts:
+            ch = self.head_ch
             if self.extpn:                                            # unet.py:81-83
                 ops["pointNet.conv1"] = ConvOp(ch, 2 * ch, 3, pad=1)
                 ops["pointNet.conv2"] = ConvOp(2 * ch, ch, 3, pad=1)
-            ops["pointNet.final_conv"] = ConvOp(ch, 300, 6)
-        for i in range(n_block):
-            co = f * 2 ** i
-            ops["decoder.decoder1_%d.1" % (i + 1)] = ConvOp(2 * co, co, 3, pad=1, in_up=True)
-            blk = "decoder.decoder2_%d" % (i + 1)
-            ops[blk + ".0"] = ConvOp(2 * co, co, 3, pad=1)
-            ops[blk + self.c2] = ConvOp(co, co, 3, pad=1)
-        ops["classifier"] = ConvOp(f, n_class, 1)
-        if self.feature_dis:                                          # unet.py:147-148: hard-wired 512 input channels
-            ops["classifier2"] = ConvOp(512, n_class, 1)
+            ops["pointNet.final_conv"] = ConvOp(ch, num_points, 6)
+        if "decoder" in parts:
+            for i in range(n_block):
+                co = f * 2 ** i
+                ops["decoder.decoder1_%d.1" % (i + 1)] = ConvOp(2 * co, co, 3, pad=1, in_up=True)
+                blk = "decoder.decoder2_%d" % (i + 1)
+                ops[blk + ".0"] = ConvOp(2 * co, co, 3, pad=1)
+                ops[blk + self.c2] = ConvOp(co, co, 3, pad=1)
+        if "classifier" in parts:
+            ops["classifier"] = ConvOp(f, n_class, 1)
+            if self.feature_dis:                                      # unet.py:147-148: hard-wired 512 input channels
+                ops["classifier2"] = ConvOp(512, n_class, 1)
         self.ops = ops
 
     # ---------------------------------------------------------------- helpers
@@ -150,16 +163,28 @@ class _SegEngine:
         op0.dgrad(dz0, P[blk + ".0.weight"], h, w, dx=dx1, dx2=dx2)
         return dx1, dx2
 
-    # ---------------------------------------------------------------- forward
-    def forward(self, P, x, training):
-        n, _, H, W = x.shape
-        nb = self.nb
-        if H % (1 << nb) or W % (1 << nb):
-            raise ValueError("input size must be divisible by %d" % (1 << nb))
-        S = {"hw": (H, W), "n": n, "wants": {k for k, p in P.items() if p.requires_grad}, "training": training}
-        cur, h, w, res = x, H, W, None
-        skips = []
-        for i in range(nb):                                           # unet.py:35-51
+    # ---------------------------------------------------------------- forward stages
+    # One method per sub-module of unet.py.  The fused network pass (``forward`` / ``backward``, one autograd node per
+    # network call) chains them with BatchNorm left lazy across the stage boundaries; a sub-module called on its own
+    # (``_StageFn``) runs its one stage and materialises the BatchNorm outputs it returns.
+    @staticmethod
+    def new_state(P, training):
+        # which parameters want a gradient is decided when the forward pass runs, as autograd does
+        return {"wants": {k for k, p in P.items() if p.requires_grad}, "training": training}
+
+    @staticmethod
+    def grad_of(P, S):
+        wants = S["wants"]
+
+        def G(name):
+            return ensure_grad(P[name]) if name in wants else None
+        return G
+
+    def fwd_encoder(self, P, x, training, S):
+        """unet.py:35-51 -> (last pooled map, [block outputs, BatchNorm still pending (TA)])"""
+        _, _, h, w = x.shape
+        cur, res, skips = x, None, []
+        for i in range(self.nb):
             y = self._dc_fwd(P, "encoder.encoder%d" % (i + 1), cur, None, h, w, training, S)
             skips.append(y)
             if i > 0:
@@ -172,7 +197,11 @@ class _SegEngine:
             S["pool%d" % i] = idx
             res = cur = pooled
             h, w = h // 2, w // 2
-        outs, o = [], cur                                             # unet.py:67-73
+        return cur, skips
+
+    def fwd_bottleneck(self, P, x, h, w, S):
+        """unet.py:67-73: the dilated convolutions chained, their outputs summed"""
+        outs, o = [], x
         for j in range(self.depth):
             name = "bottleneck.bottleneck%d.0" % (j + 1)
             S[name] = o
@@ -182,120 +211,125 @@ class _SegEngine:
         for k0 in range(1, len(outs), 3):
             bsum = K.add_n([bsum] + outs[k0:k0 + 3])
         S["bott_outs"] = outs
-        verts = None
-        if self.pointnet:                                             # unet.py:89-96
-            hin, ext_acts = bsum, []
-            if self.extpn:                                            # :90-92: two 3x3 convs + LeakyReLU in front
-                for nm in ("pointNet.conv1", "pointNet.conv2"):
-                    o, _, _ = self.ops[nm].forward(hin, P[nm + ".weight"], P[nm + ".bias"], SLOPE, h, w)
-                    ext_acts.append((nm, hin, o))
-                    hin = o
-            S["head_ext"] = ext_acts
-            hc, _, _ = self.ops["pointNet.final_conv"].forward(hin, P["pointNet.final_conv.weight"],
-                                                               P["pointNet.final_conv.bias"], SLOPE, h, w)
-            flat = hc.view(n * 300, -1)
-            if flat.shape[1] != self.fc_inch:
-                raise ValueError("fc_inch=%d does not match the %dx%d head output" % (self.fc_inch, h - 5, w - 5))
-            verts = K.linear_fwd(flat, P["pointNet.final_fc.weight"], P["pointNet.final_fc.bias"]).view(n, 300, 3)
-            S["head"] = (hin, hc, flat)
-        out2 = None
-        if self.feature_dis:                                          # unet.py:157-158: classifier2(output_bottleneck)
-            S["bsum"] = bsum
-            out2, _, _ = self.ops["classifier2"].forward(bsum, P["classifier2.weight"], P["classifier2.bias"], 1.0, h, w)
-        S["out2"] = out2
-        prev, ph, pw = bsum, h, w
-        for i in reversed(range(nb)):                                 # unet.py:128-136
+        return bsum
+
+    def fwd_head(self, P, x, h, w, S):
+        """unet.py:89-96 -> [n, num_points, 3]"""
+        n = x.shape[0]
+        hin, ext_acts = x, []
+        if self.extpn:                                                # :90-92: two 3x3 convs + LeakyReLU in front
+            for nm in ("pointNet.conv1", "pointNet.conv2"):
+                o, _, _ = self.ops[nm].forward(hin, P[nm + ".weight"], P[nm + ".bias"], SLOPE, h, w)
+                ext_acts.append((nm, hin, o))
+                hin = o
+        S["head_ext"] = ext_acts
+        hc, _, _ = self.ops["pointNet.final_conv"].forward(hin, P["pointNet.final_conv.weight"],
+                                                           P["pointNet.final_conv.bias"], SLOPE, h, w)
+        flat = hc.view(n * self.npts, -1)
+        if flat.shape[1] != self.fc_inch:
+            raise ValueError("fc_inch=%d does not match the %dx%d head output" % (self.fc_inch, h - 5, w - 5))
+        verts = K.linear_fwd(flat, P["pointNet.final_fc.weight"], P["pointNet.final_fc.bias"]).view(n, self.npts, 3)
+        S["head"] = (hin, hc, flat)
+        return verts
+
+    def fwd_decoder(self, P, x, skips, h, w, training, S):
+        """unet.py:128-136 (``skips[i]``: the input of block i + 1, outermost first) -> the last block's output (TA)"""
+        prev, ph, pw = x, h, w
+        for i in reversed(range(self.nb)):
             up = "decoder.decoder1_%d.1" % (i + 1)
             oh, ow = 2 * ph, 2 * pw
             S[up] = prev
             u, _, _ = self.ops[up].forward(prev, P[up + ".weight"], P[up + ".bias"], 1.0, oh, ow)
             prev = self._dc_fwd(P, "decoder.decoder2_%d" % (i + 1), skips[i], u, oh, ow, training, S)
             ph, pw = oh, ow
+        return prev
+
+    # ---------------------------------------------------------------- forward
+    def forward(self, P, x, training):
+        n, _, H, W = x.shape
+        nb = self.nb
+        if H % (1 << nb) or W % (1 << nb):
+            raise ValueError("input size must be divisible by %d" % (1 << nb))
+        S = self.new_state(P, training)
+        S["hw"], S["n"] = (H, W), n
+        cur, skips = self.fwd_encoder(P, x, training, S)
+        h, w = H >> nb, W >> nb
+        bsum = self.fwd_bottleneck(P, cur, h, w, S)
+        verts = self.fwd_head(P, bsum, h, w, S) if self.pointnet else None
+        out2 = None
+        if self.feature_dis:                                          # unet.py:157-158: classifier2(output_bottleneck)
+            S["bsum"] = bsum
+            out2, _, _ = self.ops["classifier2"].forward(bsum, P["classifier2.weight"], P["classifier2.bias"], 1.0, h, w)
+        S["out2"] = out2
+        prev = self.fwd_decoder(P, bsum, skips, h, w, training, S)
         S["cls_in"] = prev
-        logits, _, _ = self.ops["classifier"].forward(prev, P["classifier.weight"], P["classifier.bias"], 1.0, ph, pw)
+        logits, _, _ = self.ops["classifier"].forward(prev, P["classifier.weight"], P["classifier.bias"], 1.0, H, W)
         return logits, verts, S
 
-    # ---------------------------------------------------------------- backward
-    def backward(self, P, S, d_logits, d_verts, need_dx, d_out2=None):
-        wants = S["wants"]       # parameters that required a gradient when the forward pass ran (autograd's rule)
+    # ---------------------------------------------------------------- backward stages
+    @staticmethod
+    def _bn_of(S, i):
+        blk = S["decoder.decoder2_%d" % (i + 1)]
+        return blk[4], blk[5]
 
-        def G(name):
-            return ensure_grad(P[name]) if name in wants else None
-
-        nb, (H, W), n = self.nb, S["hw"], S["n"]
+    def bwd_decoder(self, P, G, S, d_cur, red, H, W, fused):
+        """``d_cur``: gradient of the decoder's output ([n, f, H, W]); ``red``: its last BatchNorm's backward-reduce
+        partials where the producing kernel computed them.  ``fused``: the next block's reduce rides in the epilogue of
+        each up-convolution's folded dgrad (the network pass); on its own the BatchNorm backward computes it.
+        Returns (gradient of the decoder's input, [gradient of each skip input])"""
+        nb = self.nb
         d_skips = [None] * nb
-        d_bsum = None
-        if d_logits is not None:
-            d_logits = d_logits.contiguous()
-            if G("classifier.weight") is not None:
-                self.ops["classifier"].wgrad(S["cls_in"], d_logits, G("classifier.weight"), G("classifier.bias"), H, W)
-            # every decoder block's incoming gradient has ONE producer (the classifier's dgrad, then the 2x2 fold behind
-            # each up-convolution): that kernel also computes the block's second BatchNorm's backward-reduce partials
-            bn_of = lambda i: (S["decoder.decoder2_%d" % (i + 1)][4], S["decoder.decoder2_%d" % (i + 1)][5])
-            if self.bn:
-                d_cur, red = self.ops["classifier"].dgrad(d_logits, P["classifier.weight"], H, W, bnred=bn_of(0))
+        for i in range(nb):
+            oh, ow = H >> i, W >> i
+            d_skips[i], d_u = self._dc_bwd(P, G, "decoder.decoder2_%d" % (i + 1), d_cur, None, oh, ow, S, True, red=red)
+            up = "decoder.decoder1_%d.1" % (i + 1)
+            if G(up + ".weight") is not None:
+                self.ops[up].wgrad(S[up], d_u, G(up + ".weight"), G(up + ".bias"), oh, ow)
+            # the up-convolution's data gradient at the STORED resolution: the 2x2 fold of the nearest-x2 backward (and the
+            # next block's BatchNorm-backward reduce) ride in the dgrad kernel's epilogue where the plan allows
+            if fused and i + 1 < nb and self.bn:
+                d_cur, red = self.ops[up].dgrad_fold(d_u, P[up + ".weight"], oh, ow, bnred=self._bn_of(S, i + 1))
             else:
-                d_cur, red = self.ops["classifier"].dgrad(d_logits, P["classifier.weight"], H, W), None
-            for i in range(nb):
-                oh, ow = H >> i, W >> i
-                d_skips[i], d_u = self._dc_bwd(P, G, "decoder.decoder2_%d" % (i + 1), d_cur, None, oh, ow, S, True, red=red)
-                up = "decoder.decoder1_%d.1" % (i + 1)
-                if G(up + ".weight") is not None:
-                    self.ops[up].wgrad(S[up], d_u, G(up + ".weight"), G(up + ".bias"), oh, ow)
-                # the up-convolution's data gradient at the STORED resolution: the 2x2 fold of the nearest-x2 backward (and the
-                # next block's BatchNorm-backward reduce) ride in the dgrad kernel's epilogue where the plan allows
-                if i + 1 < nb and self.bn:
-                    d_cur, red = self.ops[up].dgrad_fold(d_u, P[up + ".weight"], oh, ow, bnred=bn_of(i + 1))
-                else:
-                    d_cur, red = self.ops[up].dgrad_fold(d_u, P[up + ".weight"], oh, ow), None
-            d_bsum = d_cur
-        h, w = H >> nb, W >> nb
-        if self.feature_dis and d_out2 is not None:
-            d_out2 = d_out2.contiguous()
-            op2 = self.ops["classifier2"]
-            if G("classifier2.weight") is not None:
-                op2.wgrad(S["bsum"], d_out2, G("classifier2.weight"), G("classifier2.bias"), h, w)
-            if d_bsum is None:
-                d_bsum = op2.dgrad(d_out2, P["classifier2.weight"], h, w)
-            else:
-                op2.dgrad(d_out2, P["classifier2.weight"], h, w, dx=d_bsum, accumulate=True)
-        if self.pointnet and d_verts is not None:
-            hin, hc, flat = S["head"]
-            d_v = d_verts.contiguous().view(n * 300, 3)
-            if G("pointNet.final_fc.weight") is not None:
-                K.linear_bwd_w(d_v, flat, G("pointNet.final_fc.weight"), G("pointNet.final_fc.bias"))
-            d_hc = K.linear_bwd_x(d_v, P["pointNet.final_fc.weight"]).view(hc.shape)
-            dzc = K.lrelu_bwd(d_hc, hc, SLOPE)
-            op, op_name = self.ops["pointNet.final_conv"], "pointNet.final_conv"
-            if G("pointNet.final_conv.weight") is not None:
-                op.wgrad(hin, dzc, G("pointNet.final_conv.weight"), G("pointNet.final_conv.bias"), h, w)
-            for nm, xin, o in reversed(S["head_ext"]):                # extpn: back through conv2, conv1
-                d_o = op.dgrad(dzc, P[op_name + ".weight"], h, w)
-                dzc = K.lrelu_bwd(d_o, o, SLOPE)
-                op, op_name = self.ops[nm], nm
-                if G(nm + ".weight") is not None:
-                    op.wgrad(xin, dzc, G(nm + ".weight"), G(nm + ".bias"), h, w)
-            if d_bsum is None:
-                d_bsum = op.dgrad(dzc, P[op_name + ".weight"], h, w)
-            else:
-                op.dgrad(dzc, P[op_name + ".weight"], h, w, dx=d_bsum, accumulate=True)
-        if d_bsum is None:
-            return None
+                d_cur, red = self.ops[up].dgrad_fold(d_u, P[up + ".weight"], oh, ow), None
+        return d_cur, d_skips
+
+    def bwd_head(self, P, G, S, d_verts, d_x, h, w):
+        """the point head's parameter gradients; returns its input gradient, accumulated into ``d_x`` if given"""
+        hin, hc, flat = S["head"]
+        d_v = d_verts.contiguous().view(-1, 3)
+        if G("pointNet.final_fc.weight") is not None:
+            K.linear_bwd_w(d_v, flat, G("pointNet.final_fc.weight"), G("pointNet.final_fc.bias"))
+        d_hc = K.linear_bwd_x(d_v, P["pointNet.final_fc.weight"]).view(hc.shape)
+        dzc = K.lrelu_bwd(d_hc, hc, SLOPE)
+        op, op_name = self.ops["pointNet.final_conv"], "pointNet.final_conv"
+        if G("pointNet.final_conv.weight") is not None:
+            op.wgrad(hin, dzc, G("pointNet.final_conv.weight"), G("pointNet.final_conv.bias"), h, w)
+        for nm, xin, o in reversed(S["head_ext"]):                    # extpn: back through conv2, conv1
+            d_o = op.dgrad(dzc, P[op_name + ".weight"], h, w)
+            dzc = K.lrelu_bwd(d_o, o, SLOPE)
+            op, op_name = self.ops[nm], nm
+            if G(nm + ".weight") is not None:
+                op.wgrad(xin, dzc, G(nm + ".weight"), G(nm + ".bias"), h, w)
+        if d_x is None:
+            return op.dgrad(dzc, P[op_name + ".weight"], h, w)
+        op.dgrad(dzc, P[op_name + ".weight"], h, w, dx=d_x, accumulate=True)
+        return d_x
+
+    def bwd_bottleneck(self, P, G, S, d_bsum, h, w, need_dx=True):
         outs, g_next = S["bott_outs"], None
         for j in reversed(range(self.depth)):
             name = "bottleneck.bottleneck%d.0" % (j + 1)
             dz = K.lrelu_bwd(d_bsum, outs[j], SLOPE, dy2=g_next)
             if G(name + ".weight") is not None:
                 self.ops[name].wgrad(S[name], dz, G(name + ".weight"), G(name + ".bias"), h, w)
-            g_next = self.ops[name].dgrad(dz, P[name + ".weight"], h, w)
-        # every weight gradient except the encoder's has been launched: a data-parallel trainer starts their
-        # all-reduce here, under the encoder's backward pass (train_step.py)
-        cb = self.after_deep_grads
-        if cb is not None:
-            K.flush_wgrad_reduces()      # (the hook reads the gradients launched so far)
-            cb()
-        dA, dB = g_next, None
-        for i in reversed(range(nb)):
+            if j > 0 or need_dx:
+                g_next = self.ops[name].dgrad(dz, P[name + ".weight"], h, w)
+        return g_next
+
+    def bwd_encoder(self, P, G, S, d_out, d_skips, H, W, need_dx):
+        """``d_out``: gradient of the last pooled map; ``d_skips[i]``: of block i + 1's output (or None)"""
+        dA, dB = d_out, None
+        for i in reversed(range(self.nb)):
             hi, wi = H >> i, W >> i
             idx = S["pool%d" % i]
             if i > 0:
@@ -314,6 +348,46 @@ class _SegEngine:
             dA, _ = self._dc_bwd(P, G, "encoder.encoder%d" % (i + 1), d_y, d_skips[i], hi, wi, S, i > 0 or need_dx,
                                  pooled=pooled)
         return dA
+
+    # ---------------------------------------------------------------- backward
+    def backward(self, P, S, d_logits, d_verts, need_dx, d_out2=None):
+        G = self.grad_of(P, S)
+        nb, (H, W) = self.nb, S["hw"]
+        d_skips = [None] * nb
+        d_bsum = None
+        if d_logits is not None:
+            d_logits = d_logits.contiguous()
+            if G("classifier.weight") is not None:
+                self.ops["classifier"].wgrad(S["cls_in"], d_logits, G("classifier.weight"), G("classifier.bias"), H, W)
+            # every decoder block's incoming gradient has ONE producer (the classifier's dgrad, then the 2x2 fold behind
+            # each up-convolution): that kernel also computes the block's second BatchNorm's backward-reduce partials
+            if self.bn:
+                d_cur, red = self.ops["classifier"].dgrad(d_logits, P["classifier.weight"], H, W, bnred=self._bn_of(S, 0))
+            else:
+                d_cur, red = self.ops["classifier"].dgrad(d_logits, P["classifier.weight"], H, W), None
+            d_bsum, d_skips = self.bwd_decoder(P, G, S, d_cur, red, H, W, fused=True)
+        h, w = H >> nb, W >> nb
+        if self.feature_dis and d_out2 is not None:
+            d_out2 = d_out2.contiguous()
+            op2 = self.ops["classifier2"]
+            if G("classifier2.weight") is not None:
+                op2.wgrad(S["bsum"], d_out2, G("classifier2.weight"), G("classifier2.bias"), h, w)
+            if d_bsum is None:
+                d_bsum = op2.dgrad(d_out2, P["classifier2.weight"], h, w)
+            else:
+                op2.dgrad(d_out2, P["classifier2.weight"], h, w, dx=d_bsum, accumulate=True)
+        if self.pointnet and d_verts is not None:
+            d_bsum = self.bwd_head(P, G, S, d_verts, d_bsum, h, w)
+        if d_bsum is None:
+            return None
+        g_next = self.bwd_bottleneck(P, G, S, d_bsum, h, w)
+        # every weight gradient except the encoder's has been launched: a data-parallel trainer starts their
+        # all-reduce here, under the encoder's backward pass (train_step.py)
+        cb = self.after_deep_grads
+        if cb is not None:
+            K.flush_wgrad_reduces()      # (the hook reads the gradients launched so far)
+            cb()
+        return self.bwd_encoder(P, G, S, g_next, d_skips, H, W, need_dx)
 
 
 class _SegFn(torch.autograd.Function):
@@ -346,8 +420,97 @@ class _SegFn(torch.autograd.Function):
         return (None, dx) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
+class _StageFn(torch.autograd.Function):
+    """one standalone call of a sub-module (Encoder / Bottleneck / PointNet / Decoder): its engine stage, forward and
+    backward.  Parameter gradients go to ``param.grad`` as in the network node; input gradients (the skip tensors'
+    included) go back through autograd."""
+
+    @staticmethod
+    def forward(ctx, module, n_in, *tensors):
+        eng, P = module._stage_engine()
+        S = eng.new_state(P, module.training)
+        xs = [t.contiguous().float() for t in tensors[:n_in]]
+        outs = module._stage_fwd(eng, P, xs, S)
+        if module.training:
+            for k, b in module.named_buffers():
+                if k.endswith("num_batches_tracked"):
+                    b.add_(1)      # (a view of the flat int64 buffer when optim.flatten_module re-seated it)
+        if getattr(module, "_keep_state", False):      # tests (shared-routing backward checks)
+            module._last_S = S
+        ctx.module, ctx.eng, ctx.P, ctx.S, ctx.n_in = module, eng, P, S, n_in
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        need = ctx.needs_input_grad[2:2 + ctx.n_in]
+        dxs = [None] * ctx.n_in
+        if any(g is not None for g in grads):
+            with K.deferred_wgrad_reduces():
+                dxs = ctx.module._stage_bwd(ctx.eng, ctx.P, ctx.S, [g if g is None else g.contiguous() for g in grads],
+                                            need)
+        ctx.S = ctx.P = None
+        return (None, None) + tuple(d if n else None for d, n in zip(dxs, need)) + \
+            (None,) * (len(ctx.needs_input_grad) - 2 - ctx.n_in)
+
+
+def _hip_only(module, *xs):
+    for x in xs:
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise RuntimeError("%s runs on HIP devices only (no CPU fallback)" % type(module).__name__)
+
+
+def _check_shape(module, what, x, shape):
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError("%s: %s has shape %s, expected %s" % (type(module).__name__, what, tuple(x.shape), tuple(shape)))
+
+
+def _materialise(y):
+    """a block output whose BatchNorm is still pending (TA), applied: what the sub-module returns.  Rounded once (fma), as
+    the fused network's next convolution applies it in its load: a chain of sub-modules computes what the network does"""
+    return K.bn_apply(y.t, _Affine(y.scale, y.shift), fma=True) if isinstance(y, TA) else y
+
+
+class _Affine:
+    __slots__ = ("scale", "shift")
+
+    def __init__(self, scale, shift):
+        self.scale, self.shift = scale, shift
+
+
+class _Stage(nn.Module):
+    """Shared plumbing of the segmenter's sub-modules.  Inside a ``Segmentation_model_Point`` (or ``Segmentation_model``)
+    a sub-module runs on its parent's engine -- the same ``ConvOp`` objects, packed weights and ``owner`` (whose ``_wgen``
+    the fused optimisers bump) -- looked up at call time, so that ``_build_engine`` may replace it.  Built on its own it
+    owns an engine of its one stage."""
+    _name = ""          # attribute name in the parent network = prefix of its layers in the engine
+
+    def _attach(self, host):
+        object.__setattr__(self, "_host", host)      # (not a registered child: the module tree and state_dict stay as they are)
+
+    def _stage_engine(self):
+        host = self.__dict__.get("_host")
+        if host is not None and getattr(host, self._name, None) is self:
+            eng = host._engine
+        else:
+            eng = self.__dict__.get("_own_engine")
+            if eng is None:
+                eng = self._make_engine()
+                for op in eng.ops.values():
+                    op.owner = self
+                self._own_engine = eng
+        pre = self._name + "."
+        P = {pre + k: v for k, v in self.named_parameters()}
+        P.update({pre + k: v for k, v in self.named_buffers()})
+        return eng, P
+
+
 # ============================================================================ module tree (reference names)
-class Encoder(nn.Module):
+class Encoder(_Stage):
+    """unet.py:7-51.  forward(x) -> (output, skip): the last pooled map and the list of the ``n_block`` block outputs
+    (after BatchNorm); ``conv1_1`` never runs."""
+    _name = "encoder"
+
     def __init__(self, filters=32, in_channels=3, n_block=4, kernel_size=(3, 3), batch_norm=True, padding='same'):
         super().__init__()
         self.filter = filters
@@ -363,9 +526,41 @@ class Encoder(nn.Module):
                 model += [BatchNorm2d(out_ch)]
             self.add_module('encoder%d' % (i + 1), nn.Sequential(*model))
             self.add_module('conv1_%d' % (i + 1), nn.Sequential(Conv2d(in_ch * 3, out_ch, 1), LeakyReLU(inplace=True)))
+        self._cfg = (in_channels, n_block, batch_norm, tuple(kernel_size) == (3, 3) and padding == 'same')
+
+    def _make_engine(self):
+        cin, nb, bn, _ = self._cfg
+        return _SegEngine(self.filter, cin, nb, 0, 0, False, 0, batchnorm=bn, parts=("encoder",))
+
+    def forward(self, x):
+        cin, nb, _, std = self._cfg
+        if not std:
+            raise NotImplementedError("Encoder: only kernel_size=(3, 3), padding='same' (the reference's defaults) run")
+        _hip_only(self, x)
+        if x.dim() != 4 or x.shape[1] != cin or x.shape[2] % (1 << nb) or x.shape[3] % (1 << nb):
+            raise ValueError("Encoder: input must be [n, %d, h, w] with h and w divisible by %d, got %s"
+                             % (cin, 1 << nb, tuple(x.shape)))
+        out = _StageFn.apply(self, 1, x, *self.parameters())
+        return out[0], list(out[1:])
+
+    def _stage_fwd(self, eng, P, xs, S):
+        S["hw"] = tuple(xs[0].shape[2:])
+        cur, skips = eng.fwd_encoder(P, xs[0], S["training"], S)
+        return [cur] + [_materialise(y) for y in skips]
+
+    def _stage_bwd(self, eng, P, S, grads, need):
+        d_out, d_skips = grads[0], list(grads[1:])
+        if d_out is None:      # (only skip tensors were used: the pooled map's gradient is zero)
+            idx = S["pool%d" % (eng.nb - 1)]
+            d_out = torch.zeros(idx.shape, dtype=torch.float32, device=idx.device)
+        H, W = S["hw"]
+        return [eng.bwd_encoder(P, eng.grad_of(P, S), S, d_out, d_skips, H, W, need[0])]
 
 
-class Bottleneck(nn.Module):
+class Bottleneck(_Stage):
+    """unet.py:54-73.  forward(x) -> the sum of the ``depth`` chained dilated convolution + LeakyReLU outputs"""
+    _name = "bottleneck"
+
     def __init__(self, filters=32, n_block=4, depth=4, kernel_size=(3, 3)):
         super().__init__()
         out_ch, in_ch = filters * 2 ** n_block, filters * 2 ** (n_block - 1)
@@ -375,9 +570,36 @@ class Bottleneck(nn.Module):
                 Conv2d(in_ch, out_ch, kernel_size, padding=d, dilation=d), LeakyReLU(inplace=True)))
             if i == 0:
                 in_ch = out_ch
+        self._cfg = (filters, n_block, depth, tuple(kernel_size) == (3, 3))
+
+    def _make_engine(self):
+        f, nb, depth, _ = self._cfg
+        return _SegEngine(f, 0, nb, depth, 0, False, 0, parts=("bottleneck",))
+
+    def forward(self, x):
+        f, nb, depth, std = self._cfg
+        if not std:
+            raise NotImplementedError("Bottleneck: only kernel_size=(3, 3) (the reference's default) runs")
+        _hip_only(self, x)
+        if depth < 1:
+            raise ValueError("Bottleneck: depth must be at least 1")
+        if x.dim() != 4 or x.shape[1] != f * 2 ** (nb - 1):
+            raise ValueError("Bottleneck: input must be [n, %d, h, w], got %s" % (f * 2 ** (nb - 1), tuple(x.shape)))
+        return _StageFn.apply(self, 1, x, *self.parameters())[0]
+
+    def _stage_fwd(self, eng, P, xs, S):
+        S["hw"] = tuple(xs[0].shape[2:])
+        return [eng.fwd_bottleneck(P, xs[0], S["hw"][0], S["hw"][1], S)]
+
+    def _stage_bwd(self, eng, P, S, grads, need):
+        h, w = S["hw"]
+        return [eng.bwd_bottleneck(P, eng.grad_of(P, S), S, grads[0], h, w, need_dx=need[0])]
 
 
-class PointNet(nn.Module):
+class PointNet(_Stage):
+    """unet.py:76-96.  forward(x) -> [n, num_points, 3] (``ext``: the two 3x3 convolutions in front)"""
+    _name = "pointNet"
+
     def __init__(self, num_points=300, fc_inch=81, conv_inch=512, ext=False):
         super().__init__()
         self.num_points = num_points
@@ -388,9 +610,34 @@ class PointNet(nn.Module):
         self.final_conv = Conv2d(conv_inch, self.num_points, kernel_size=6)
         self.final_fc = Linear(fc_inch, 3)
         self._ext = ext
+        self._cfg = (fc_inch, conv_inch)
+
+    def _make_engine(self):
+        fc_inch, ch = self._cfg
+        return _SegEngine(32, 0, 0, 0, 0, True, fc_inch, extpn=self._ext, parts=("pointNet",), head_ch=ch,
+                          num_points=self.num_points)
+
+    def forward(self, x):
+        _hip_only(self, x)
+        fc_inch, ch = self._cfg
+        if x.dim() != 4 or x.shape[1] != ch or x.shape[2] < 6 or x.shape[3] < 6:
+            raise ValueError("PointNet: input must be [n, %d, h, w] with h, w >= 6, got %s" % (ch, tuple(x.shape)))
+        return _StageFn.apply(self, 1, x, *self.parameters())[0]
+
+    def _stage_fwd(self, eng, P, xs, S):
+        S["hw"] = tuple(xs[0].shape[2:])
+        return [eng.fwd_head(P, xs[0], S["hw"][0], S["hw"][1], S)]
+
+    def _stage_bwd(self, eng, P, S, grads, need):
+        h, w = S["hw"]
+        return [eng.bwd_head(P, eng.grad_of(P, S), S, grads[0], None, h, w)]
 
 
-class Decoder(nn.Module):
+class Decoder(_Stage):
+    """unet.py:99-136.  forward(x, skip) -> the last block's output after BatchNorm, [n, filters, H, W]; pops the last
+    ``n_block`` entries of the caller's ``skip`` list, as the reference does."""
+    _name = "decoder"
+
     def __init__(self, filters=32, n_block=4, kernel_size=(3, 3), batch_norm=True, padding='same', drop=False):
         super().__init__()
         if drop:
@@ -410,6 +657,37 @@ class Decoder(nn.Module):
             if batch_norm:
                 model += [BatchNorm2d(out_ch)]
             self.add_module('decoder2_%d' % (i + 1), nn.Sequential(*model))
+        self._cfg = (filters, batch_norm, tuple(kernel_size) == (3, 3) and padding == 'same')
+
+    def _make_engine(self):
+        f, bn, _ = self._cfg
+        return _SegEngine(f, 0, self.n_block, 0, 0, False, 0, batchnorm=bn, parts=("decoder",))
+
+    def forward(self, x, skip):
+        f, _, std = self._cfg
+        nb = self.n_block
+        if not std:
+            raise NotImplementedError("Decoder: only kernel_size=(3, 3), padding='same' (the reference's defaults) run")
+        if len(skip) < nb:
+            raise IndexError("Decoder: %d blocks pop %d skip entries, the list holds %d" % (nb, nb, len(skip)))
+        _hip_only(self, x, *skip[-nb:])
+        if x.dim() != 4 or x.shape[1] != f * 2 ** nb:
+            raise ValueError("Decoder: input must be [n, %d, h, w], got %s" % (f * 2 ** nb, tuple(x.shape)))
+        n, _, h, w = x.shape
+        for i, t in enumerate(skip[-nb:]):          # (checked before the list is touched: a refused call leaves it whole)
+            _check_shape(self, "skip[%d]" % (len(skip) - nb + i), t, (n, f * 2 ** i, h << (nb - i), w << (nb - i)))
+        skips = [skip.pop() for _ in range(nb)][::-1]       # unet.py:134: one pop per block, deepest first
+        return _StageFn.apply(self, 1 + nb, x, *skips, *self.parameters())[0]
+
+    def _stage_fwd(self, eng, P, xs, S):
+        S["hw"] = tuple(xs[1].shape[2:])
+        h, w = xs[0].shape[2:]
+        return [_materialise(eng.fwd_decoder(P, xs[0], xs[1:], h, w, S["training"], S))]
+
+    def _stage_bwd(self, eng, P, S, grads, need):
+        H, W = S["hw"]
+        d_x, d_skips = eng.bwd_decoder(P, eng.grad_of(P, S), S, grads[0], None, H, W, fused=False)
+        return [d_x] + d_skips
 
 
 class Segmentation_model_Point(nn.Module):
@@ -438,6 +716,10 @@ class Segmentation_model_Point(nn.Module):
                                   batchnorm=batchnorm, feature_dis=feature_dis)
         for op in self._engine.ops.values():
             op.owner = self
+        for name in ("encoder", "bottleneck", "pointNet", "decoder"):      # standalone sub-module calls run on this engine
+            sub = getattr(self, name, None)
+            if sub is not None:
+                sub._attach(self)
 
     def _initialize_weights(self, heinit=False):                      # unet.py:194-208
         for m in self.modules():
