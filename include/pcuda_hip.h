@@ -370,6 +370,32 @@ int pcuda_dice_metric(const float* logits, const uint8_t* onehot, int n, int c, 
  * outputs images_chw [b][c][oh][ow], onehot [b][num_classes][oh][ow] */
 int pcuda_assemble_batch(const float* images_hwc, const int* mask_labels, int b, int h, int w, int c, int crop,
                          int num_classes, float* images_chw, uint8_t* onehot, pcuda_stream_t s);
+/* batch-global minimum and maximum of an fp32 buffer (data_generator_mmwhs.py:246-247) -> out2[0] = min, out2[1] = max,
+ * device floats, no host read; NaNs are skipped.  workspace: pcuda_minmax_workspace_size() bytes */
+size_t pcuda_minmax_workspace_size(void);
+int pcuda_minmax(const float* x, long long numel, float* out2, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* device-side light augmentation fused with the batch assembly above (light_aug data_generator_mmwhs.py:87-122 +
+ * :245-274; simple_aug data_generator_mscmrseg.py:135-167 + :305-317): per sample one inverse 2x3 matrix
+ * inv_mats[b][6] (float64, device; output pixel (x, y) of the FULL image -> source coordinate
+ * sx = m0 x + m1 y + m2, sy = m3 x + m4 y + m5: flips and the affine composed on the host), order[b] (0 = nearest
+ * floor(s + 0.5), anything else = bilinear in float64 with cval for a neighbour outside the image) and cval[b] (0..255),
+ * all device arrays.  images_hwc [b][h][w][c] fp32, or uint8 when images_u8.  rescale:
+ *   PCUDA_AUG_NONE    fp32: the values themselves are interpolated (no quantisation); uint8: float(q')
+ *   PCUDA_AUG_MINMAX  fp32 only, minmax = device (min, max): q = trunc((x - min) * 255 / (max - min)) as uint8, warp,
+ *                     out = min + float(q') * (max - min) / 255, all fp32; max == min gives q = 0, so every output = min
+ *   PCUDA_AUG_DIV255  uint8 only: float(q') / 255
+ * where q' = floor(v + 0.5) clipped to [0, 255].  Labels take order 0 and fill 0 whatever the image's order and cval.
+ * Outputs (each may be NULL, not all): images_chw [b][c][oh][ow] fp32 and onehot [b][num_classes][oh][ow] over the centre
+ * crop (crop as in pcuda_assemble_batch); over the full image full_mask [b][h][w] uint8 (label > 0: what the point-cloud
+ * sampler reads), labels_full [b][h][w] int32 and images_u8_full [b][h][w][c] (uint8 input only).  With identity
+ * matrices and PCUDA_AUG_NONE the cropped outputs are pcuda_assemble_batch's bit for bit. */
+#define PCUDA_AUG_NONE 0
+#define PCUDA_AUG_MINMAX 1
+#define PCUDA_AUG_DIV255 2
+int pcuda_augment_assemble(const void* images_hwc, int images_u8, const int* mask_labels, int b, int h, int w, int c, int crop,
+                           int num_classes, const double* inv_mats, const int* order, const int* cval, int rescale,
+                           const float* minmax, float* images_chw, uint8_t* onehot, uint8_t* full_mask, int* labels_full,
+                           uint8_t* images_u8_full, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

@@ -837,6 +837,65 @@ def assemble_batch(images_hwc, mask_labels, num_classes, crop=0):
     return out, onehot
 
 
+def minmax(x):
+    """fp32 tensor -> device tensor [2] = (min, max) over every element (no host read)."""
+    _req(x)
+    x = x.contiguous()
+    nbytes = L.lib().pcuda_minmax_workspace_size()
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty(2, dtype=torch.float32, device=x.device)
+    check(L.lib().pcuda_minmax(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "minmax")
+    return out
+
+
+AUG_NONE, AUG_MINMAX, AUG_DIV255 = 0, 1, 2
+
+
+def augment_assemble(images_hwc, mask_labels, inv_mats, order, cval, num_classes=5, crop=0, rescale=AUG_NONE, minmax=None,
+                     want_images=True, want_onehot=True, want_full_mask=False, want_labels=False, want_u8=False):
+    """Flips + affine + rescale + batch assembly in one launch (``pcuda_augment_assemble``).  images ``[B,H,W,C]`` fp32 or
+    uint8, labels ``[B,H,W]`` int32 or None, ``inv_mats`` float64 ``[B,2,3]``, ``order`` / ``cval`` int32 ``[B]``, all on
+    the device -> dict with the outputs asked for: ``images`` fp32 ``[B,C,h,w]``, ``onehot`` uint8 ``[B,K,h,w]`` (cropped),
+    ``full_mask`` uint8 ``[B,H,W]``, ``labels`` int32 ``[B,H,W]``, ``images_u8`` uint8 ``[B,H,W,C]`` (full size)."""
+    if images_hwc.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("augment_assemble: fp32 or uint8 images")
+    _req(images_hwc, images_hwc.dtype)
+    _req(inv_mats, torch.float64); _req(order, torch.int32); _req(cval, torch.int32)
+    images_hwc = images_hwc.contiguous()
+    b, h, w, c = images_hwc.shape
+    if tuple(inv_mats.shape) != (b, 2, 3) or tuple(order.shape) != (b,) or tuple(cval.shape) != (b,):
+        raise ValueError("augment_assemble: per-sample parameters do not match the batch of %d" % b)
+    dev = images_hwc.device
+    oh, ow = (2 * (crop // 2), 2 * (crop // 2)) if crop else (h, w)
+    if mask_labels is not None:
+        _req(mask_labels, torch.int32)
+        mask_labels = mask_labels.contiguous()
+        if tuple(mask_labels.shape) != (b, h, w):
+            raise ValueError("augment_assemble: mask shape %r does not match the images" % (tuple(mask_labels.shape),))
+    else:
+        want_onehot = want_full_mask = want_labels = False
+    out = {}
+    if want_images:
+        out["images"] = torch.empty((b, c, oh, ow), dtype=torch.float32, device=dev)
+    if want_onehot:
+        out["onehot"] = torch.empty((b, num_classes, oh, ow), dtype=torch.uint8, device=dev)
+    if want_full_mask:
+        out["full_mask"] = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+    if want_labels:
+        out["labels"] = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+    if want_u8:
+        out["images_u8"] = torch.empty((b, h, w, c), dtype=torch.uint8, device=dev)
+    if minmax is not None:
+        _req(minmax)
+    check(L.lib().pcuda_augment_assemble(images_hwc.data_ptr(), int(images_hwc.dtype == torch.uint8), _ptr(mask_labels), b, h, w, c,
+                                         int(crop), int(num_classes), inv_mats.contiguous().data_ptr(),
+                                         order.contiguous().data_ptr(), cval.contiguous().data_ptr(), int(rescale),
+                                         _ptr(minmax), _ptr(out.get("images")), _ptr(out.get("onehot")),
+                                         _ptr(out.get("full_mask")), _ptr(out.get("labels")), _ptr(out.get("images_u8")),
+                                         _stream()), "augment_assemble")
+    return out
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum."""
     if x.dtype not in (torch.float32, torch.uint8):

@@ -1,0 +1,298 @@
+"""Device-side light augmentation for the loader path.
+
+The reference's ``light_aug`` (``src/data_generator_mmwhs.py:87-122``) and ``simple_aug``
+(``src/data_generator_mscmrseg.py:135-167``) are ``imgaug`` pipelines: ``Fliplr``, ``Flipud`` and, sometimes, one
+``Affine`` (scale, translate, rotate, shear, interpolation order 0 or 1, constant fill), applied in random order.  Here
+the per-sample parameters are drawn on the host from a numpy ``Generator``, composed into one inverse 2x3 matrix per
+sample in float64, and a single HIP kernel (``csrc/augment.hip``) warps the batch, rescales it and assembles it (centre
+crop, channels first, one-hot) -- so the device-side point-cloud sampler finally has a device-side producer.
+
+The sub-pixel convention is this build's own (imgaug / cv2 are not vendored by the reference: parity unpinned) and is
+pinned against ``scipy.ndimage.affine_transform`` by ``tests/golden/augment.npz``:
+
+* centre ``c = ((W-1)/2, (H-1)/2)``; forward map in pixel coordinates (x right, y down)
+  ``A = T(c + (tx*W, ty*H)) . R(rotate) . Sh(shear) . S(sx, sy) . T(-c)`` with ``R = [[cos, -sin], [sin, cos]]`` and
+  ``Sh = [[1, tan(shear)], [0, 1]]``; flips are ``x -> W-1-x`` and ``y -> H-1-y``; the maps are multiplied in application
+  order; the kernel receives the inverse (output pixel -> source coordinate)
+* coordinates and interpolation in float64; order 0 takes the texel at ``floor(coord + 0.5)``, order 1 is bilinear with
+  ``cval`` for a neighbour outside the image; the result is ``floor(v + 0.5)`` clipped to [0, 255]
+* masks take order 0 and fill 0 whatever the image's order and ``cval`` are
+
+The heavy pipeline (``augmentation``: Superpixels, median blur, elastic, piecewise affine, hue/saturation ...) is out of
+scope."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+from typing import Iterable, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import kernels as K
+from .npy2point import masks_to_pointclouds
+
+OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
+
+HEAVY_MESSAGE = ("The heavy pipeline (`augmentation`: Superpixels, median blur, elastic, piecewise affine, hue/saturation ...) "
+                 "is out of scope.")
+
+# (p_fliplr, p_flipud, p_affine): data_generator_mmwhs.py:89-94, data_generator_mscmrseg.py:136-142
+_PRESETS = {"mmwhs_light": (0.2, 0.2, 0.3), "mscmrseg_simple": (0.3, 0.3, 0.45)}
+# shared by both pipelines (data_generator_mmwhs.py:95-100, data_generator_mscmrseg.py:143-150)
+SCALE = (0.8, 1.2)
+TRANSLATE_X = (-0.1, 0.05)
+TRANSLATE_Y = (-0.1, 0.1)
+ROTATE = (-10.0, 10.0)
+SHEAR = (-12.0, 12.0)
+
+
+@dataclass
+class AugmentParams:
+    """Per-sample parameters (numpy arrays of length B) and the one application order of the batch: ``op_order`` lists
+    ``OP_FLIPLR``, ``OP_FLIPUD``, ``OP_AFFINE`` in the order they are applied (``random_order=True`` draws one order per
+    batch).  ``translate_*`` are fractions of the width / height, ``rotate`` and ``shear`` degrees."""
+    flip_lr: np.ndarray
+    flip_ud: np.ndarray
+    affine_on: np.ndarray
+    scale_x: np.ndarray
+    scale_y: np.ndarray
+    translate_x: np.ndarray
+    translate_y: np.ndarray
+    rotate: np.ndarray
+    shear: np.ndarray
+    order: np.ndarray
+    cval: np.ndarray
+    op_order: Tuple[int, int, int] = field(default=(OP_FLIPLR, OP_FLIPUD, OP_AFFINE))
+
+    @property
+    def batch(self) -> int:
+        return len(self.flip_lr)
+
+    @staticmethod
+    def identity(batch: int) -> "AugmentParams":
+        z, o = np.zeros(batch, dtype=np.float64), np.ones(batch, dtype=np.float64)
+        f = np.zeros(batch, dtype=bool)
+        i = np.zeros(batch, dtype=np.int64)
+        return AugmentParams(f.copy(), f.copy(), f.copy(), o.copy(), o.copy(), z.copy(), z.copy(), z.copy(), z.copy(), i.copy(),
+                             i.copy())
+
+    def is_identity(self) -> bool:
+        return not (np.any(self.flip_lr) or np.any(self.flip_ud) or np.any(self.affine_on))
+
+    def validate(self) -> None:
+        b = self.batch
+        for name in ("flip_ud", "affine_on", "scale_x", "scale_y", "translate_x", "translate_y", "rotate", "shear", "order",
+                     "cval"):
+            if len(getattr(self, name)) != b:
+                raise ValueError("AugmentParams.%s has %d entries, flip_lr has %d" % (name, len(getattr(self, name)), b))
+        if sorted(int(o) for o in self.op_order) != [OP_FLIPLR, OP_FLIPUD, OP_AFFINE]:
+            raise ValueError("AugmentParams.op_order must be a permutation of (0, 1, 2), got %r" % (tuple(self.op_order),))
+        order, cval = np.asarray(self.order), np.asarray(self.cval)
+        if np.any((order != 0) & (order != 1)):
+            raise ValueError("AugmentParams.order must be 0 or 1")
+        if np.any((cval < 0) | (cval > 255)) or np.any(cval != np.floor(cval)):
+            raise ValueError("AugmentParams.cval must be an integer in [0, 255]")
+
+
+def sample_params(batch: int, preset: str, rng: np.random.Generator) -> AugmentParams:
+    """Draw the parameters of one batch.  ``preset``: ``"mmwhs_light"`` (flips 0.2 / 0.2, affine with p = 0.3) or
+    ``"mscmrseg_simple"`` (0.3 / 0.3, p = 0.45); both: scale 0.8-1.2 per axis, translate x in (-0.1, 0.05) and y in
+    (-0.1, 0.1), rotate +/-10, shear +/-12 degrees, order from {0, 1}, cval from 0..255, one operation order per batch.
+    (imgaug's own parameter stream is not reproduced: parity unpinned.)"""
+    if preset == "heavy":
+        raise NotImplementedError(HEAVY_MESSAGE)
+    if preset not in _PRESETS:
+        raise ValueError("unknown augmentation preset %r (have: %s)" % (preset, ", ".join(sorted(_PRESETS))))
+    p_lr, p_ud, p_aff = _PRESETS[preset]
+    op_order = tuple(int(i) for i in rng.permutation(3))
+    u = lambda lo_hi: rng.uniform(lo_hi[0], lo_hi[1], batch)
+    return AugmentParams(flip_lr=rng.random(batch) < p_lr, flip_ud=rng.random(batch) < p_ud, affine_on=rng.random(batch) < p_aff,
+                         scale_x=u(SCALE), scale_y=u(SCALE), translate_x=u(TRANSLATE_X), translate_y=u(TRANSLATE_Y),
+                         rotate=u(ROTATE), shear=u(SHEAR), order=rng.integers(0, 2, batch), cval=rng.integers(0, 256, batch),
+                         op_order=op_order)
+
+
+def _translate(tx, ty):
+    return np.array([[1.0, 0.0, tx], [0.0, 1.0, ty], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+
+def forward_matrices(params: AugmentParams, h: int, w: int) -> np.ndarray:
+    """float64 ``[B,3,3]``: source pixel (x, y, 1) -> output pixel, the operations multiplied in application order."""
+    params.validate()
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    out = np.empty((params.batch, 3, 3), dtype=np.float64)
+    for i in range(params.batch):
+        m = np.eye(3, dtype=np.float64)
+        for op in params.op_order:
+            if op == OP_FLIPLR and params.flip_lr[i]:
+                m = np.array([[-1.0, 0.0, w - 1.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]) @ m
+            elif op == OP_FLIPUD and params.flip_ud[i]:
+                m = np.array([[1.0, 0.0, 0.0], [0.0, -1.0, h - 1.0], [0.0, 0.0, 1.0]]) @ m
+            elif op == OP_AFFINE and params.affine_on[i]:
+                r, s = math.radians(float(params.rotate[i])), math.radians(float(params.shear[i]))
+                rot = np.array([[math.cos(r), -math.sin(r), 0.0], [math.sin(r), math.cos(r), 0.0], [0.0, 0.0, 1.0]])
+                sh = np.array([[1.0, math.tan(s), 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
+                sc = np.diag([float(params.scale_x[i]), float(params.scale_y[i]), 1.0])
+                a = _translate(cx + float(params.translate_x[i]) * w, cy + float(params.translate_y[i]) * h) @ rot @ sh @ sc \
+                    @ _translate(-cx, -cy)
+                m = a @ m
+        out[i] = m
+    return out
+
+
+def inverse_matrices(params: AugmentParams, h: int, w: int) -> np.ndarray:
+    """float64 ``[B,2,3]``: output pixel (x, y) -> source coordinate, what the kernel consumes.  A singular map (a zero
+    scale, a 90 degree shear) raises ``ValueError``."""
+    fwd = forward_matrices(params, h, w)
+    out = np.empty((params.batch, 2, 3), dtype=np.float64)
+    for i, m in enumerate(fwd):
+        det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+        if not np.all(np.isfinite(m)) or not abs(det) > 1e-12:
+            raise ValueError("augmentation matrix of sample %d is singular (determinant %r)" % (i, det))
+        out[i] = np.linalg.inv(m)[:2]
+    return out
+
+
+def kernel_params(params: AugmentParams, h: int, w: int):
+    """(inverse matrices float64 [B,2,3], order int32 [B], cval int32 [B]) as the kernel takes them: ``order`` and ``cval``
+    only matter where an affine is applied (a flip maps integer pixels to integer pixels), so they are 0 elsewhere."""
+    inv = inverse_matrices(params, h, w)
+    on = np.asarray(params.affine_on, dtype=bool)
+    order = np.where(on, np.asarray(params.order), 0).astype(np.int32)
+    cval = np.where(on, np.asarray(params.cval), 0).astype(np.int32)
+    return inv, order, cval
+
+
+def upload_params(params: Optional[AugmentParams], batch: int, h: int, w: int, device: torch.device):
+    """Validate on the host, then move the kernel's parameter arrays through pinned, non-blocking copies (no
+    synchronisation)."""
+    if params is None:
+        params = AugmentParams.identity(batch)
+    if params.batch != batch:
+        raise ValueError("AugmentParams for %d samples, batch of %d" % (params.batch, batch))
+    inv, order, cval = kernel_params(params, h, w)
+
+    def put(a):
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        if device.type == "cuda":
+            t = t.pin_memory()
+        return t.to(device, non_blocking=True)
+    return put(inv), put(order), put(cval)
+
+
+def _labels(masks: torch.Tensor) -> torch.Tensor:
+    if masks.dim() == 4 and masks.shape[-1] == 1:
+        masks = masks[..., 0]
+    return masks.to(torch.int32)
+
+
+def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optional[AugmentParams], num_classes: int = 5,
+                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
+                  firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True):
+    """``data_generator_mmwhs.py:245-274`` after the file reads (``rescale="minmax"``, fp32 images), or
+    ``data_generator_mscmrseg.py:305-317`` (``rescale="div255"``, uint8 images), on the device: images ``[B,H,W,C]``,
+    integer masks ``[B,H,W]`` (or ``[B,H,W,1]``) ->
+    ``(images [B,C,h,w] fp32, one-hot uint8 [B,K,h,w], verts fp32 [B,300,3] / 255 or None)``.
+
+    ``"minmax"``: batch-global min and max (kept on the device), ``q = trunc((x - min) * 255 / (max - min))`` as uint8,
+    warp, ``min + float(q') * (max - min) / 255``, all fp32.  ``max == min`` is undefined in the reference (a NaN cast to
+    uint8); here ``q`` is 0 everywhere, so every output equals ``min``.  ``"div255"``: warp, ``float32(q') / 255``.
+    ``None``: no quantisation, the fp32 values themselves are gathered / interpolated; with ``params=None`` or
+    all-identity parameters this is ``assemble_batch`` bit for bit.
+
+    ``resample_verts`` re-samples the point cloud from the FULL-size warped mask (``:255-263``); the mask is written by the
+    same launch (``fused_mask``) or by a second launch of the kernel over the full image.  Otherwise ``verts`` (integer
+    vertices stored with the data set) are only scaled.  The augmentation adds no host synchronisation; the sampler's one
+    ``counts.max()`` is its own."""
+    lab = _labels(masks)
+    b, h, w, _ = images_hwc.shape
+    dev = images_hwc.device
+    inv, order, cval = upload_params(params, b, h, w, dev)
+    mm = None
+    if rescale == "minmax":
+        if images_hwc.dtype != torch.float32:
+            raise TypeError("augment_batch: the min-max rescale takes fp32 images")
+        mode, mm = K.AUG_MINMAX, K.minmax(images_hwc)
+    elif rescale == "div255":
+        if images_hwc.dtype != torch.uint8:
+            raise TypeError("augment_batch: the /255 rescale takes uint8 images")
+        mode = K.AUG_DIV255
+    elif rescale is None:
+        mode = K.AUG_NONE
+    else:
+        raise ValueError("augment_batch: rescale must be 'minmax', 'div255' or None, got %r" % (rescale,))
+    out = K.augment_assemble(images_hwc, lab, inv, order, cval, num_classes, crop_size, mode, mm,
+                             want_full_mask=resample_verts and fused_mask)
+    if resample_verts:
+        full = out["full_mask"] if fused_mask else K.augment_assemble(
+            images_hwc, lab, inv, order, cval, num_classes, crop_size, mode, mm, want_images=False, want_onehot=False,
+            want_full_mask=True)["full_mask"]
+        if firsts is None:
+            firsts = torch.zeros(b, dtype=torch.int32, device=dev)
+        verts = masks_to_pointclouds(full, firsts)
+    v = None if verts is None else verts.to(torch.float32) / torch.full((), 255.0, dtype=torch.float32, device=verts.device)
+    return out["images"], out["onehot"], v
+
+
+def light_aug(images: torch.Tensor, masks: Optional[torch.Tensor] = None, params: Optional[AugmentParams] = None,
+              segmap: bool = False):
+    """``data_generator_mmwhs.py:87-122``: uint8 ``[B,H,W,C]`` images (and integer masks ``[B,H,W]`` / ``[B,H,W,1]``) on
+    the device -> the warped uint8 images (and masks, same shape and dtype).  ``params`` is required: draw it with
+    ``sample_params(B, "mmwhs_light", rng)``.  (``segmap`` only selects imgaug's container type in the reference.)"""
+    if params is None:
+        raise TypeError("light_aug: params is required (sample_params(batch, preset, rng)); there is no silent identity")
+    if images.dtype != torch.uint8 or images.dim() != 4:
+        raise TypeError("light_aug: uint8 [B,H,W,C] images")
+    b, h, w, _ = images.shape
+    inv, order, cval = upload_params(params, b, h, w, images.device)
+    lab = None if masks is None else _labels(masks)
+    out = K.augment_assemble(images, lab, inv, order, cval, 2, 0, K.AUG_NONE, None, want_images=False, want_onehot=False,
+                             want_labels=lab is not None, want_u8=True)
+    if masks is None:
+        return out["images_u8"]
+    return out["images_u8"], out["labels"].to(masks.dtype).reshape(masks.shape)
+
+
+def simple_aug(image: torch.Tensor, mask: Optional[torch.Tensor], params: Optional[AugmentParams] = None):
+    """``data_generator_mscmrseg.py:135-167``: as ``light_aug`` (preset ``"mscmrseg_simple"``), also for one ``[H,W,C]``
+    image with its ``[H,W]`` / ``[H,W,1]`` mask."""
+    if params is None:
+        raise TypeError("simple_aug: params is required (sample_params(batch, preset, rng)); there is no silent identity")
+    if image.dim() == 4:
+        return light_aug(image, mask, params)
+    if mask is None:
+        return light_aug(image[None], None, params)[0]
+    im, m = light_aug(image[None], mask[None], params)
+    return im[0], m[0]
+
+
+class AugmentedBatches:
+    """Wraps a host iterator of raw ``(images [B,H,W,C], masks [B,H,W] or [B,H,W,1])`` batches (optionally with the stored
+    integer vertices as a third item) and yields the ``(x [B,C,h,w] fp32, y [B,K,h,w] uint8 one-hot, z [B,300,3] fp32)``
+    device tensors ``train_epoch`` consumes.  Raw batches go to the device one ahead through pinned staging buffers
+    (``DeviceBatches``); the parameters of each batch are drawn from ``rng`` on the host and ride along through pinned,
+    non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last."""
+
+    def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
+                 crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2):
+        if preset == "heavy":
+            raise NotImplementedError(HEAVY_MESSAGE)
+        if preset not in _PRESETS:
+            raise ValueError("unknown augmentation preset %r" % (preset,))
+        from .._epoch import DeviceBatches      # (imports the trainer: only when batches are actually wrapped)
+        self.batches = DeviceBatches(iterator, device, depth)
+        self.preset, self.rng = preset, rng
+        self.num_classes, self.crop_size, self.rescale, self.resample_verts = num_classes, crop_size, rescale, resample_verts
+        self.last_params: Optional[AugmentParams] = None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        item = next(self.batches)
+        images, masks = item[0], item[1]
+        verts = item[2] if len(item) > 2 else None
+        self.last_params = sample_params(images.shape[0], self.preset, self.rng)
+        return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
+                             resample_verts=self.resample_verts, verts=verts)

@@ -3,7 +3,7 @@
 What the reference's data generators do to a batch AFTER augmentation (``src/data_generator_mmwhs.py:255-274``,
 ``src/utils/utils.py:7-29``, ``crop_volume`` ``:134-137``): re-sample the surface point cloud of every
 (augmented) mask, centre-crop, move channels first, one-hot the labels, scale the vertices by 1/255.
-CSV/NIfTI reading and imgaug stay on the CPU (out of scope); the raw ``[B,H,W,C]`` images and integer masks are
+CSV/NIfTI reading stays on the CPU (the light imgaug pipelines in front of this tail: ``utils/augment.py``); the raw ``[B,H,W,C]`` images and integer masks are
 uploaded once and everything else happens here."""
 from __future__ import annotations
 
