@@ -396,6 +396,44 @@ int pcuda_augment_assemble(const void* images_hwc, int images_u8, const int* mas
                            int num_classes, const double* inv_mats, const int* order, const int* cval, int rescale,
                            const float* minmax, float* images_chw, uint8_t* onehot, uint8_t* full_mask, int* labels_full,
                            uint8_t* images_u8_full, pcuda_stream_t s);
+/* device-side photometric augmentation: the photometric operators of ImageProcessor.augmentation2
+ * (data_generator_mscmrseg.py:87-132; called at :305-309) on uint8 images [b][h][w][c], c = 1..4, as a per-sample program
+ * of `slots` (0..8) slots in device memory: opcode [b][slots], iarg [b][slots][4], farg [b][slots][16] (float64),
+ * seed [b][slots] (64-bit Philox key).  The value is uint8 between two slots; float64 arithmetic in a fixed order,
+ * floor(v + 0.5) clipped to [0, 255]; reflect-101 borders, the median replicates.  Per opcode:
+ *   PCUDA_PHOTO_NOP             copy (so does an unknown opcode: the host validates programs)
+ *   PCUDA_PHOTO_GAUSSIAN_BLUR   iarg[0] = radius 0..12, farg[0..radius] = normalised weights w[|d|] (computed on the host);
+ *                               rows, then columns on the unrounded values: t = x[0] w[0]; d = r..1: t += (x[-d] + x[d]) w[d]
+ *   PCUDA_PHOTO_AVERAGE_BLUR    iarg[0] = k 2..7, offsets -(k / 2) .. k - k / 2 - 1, (2 S + k k) / (2 k k) in integers
+ *   PCUDA_PHOTO_MEDIAN_BLUR     iarg[0] = odd k 3..11, replicated border
+ *   PCUDA_PHOTO_CONV3X3         farg[0..8]: correlation, taps summed row-major from 0 (Sharpen, Emboss)
+ *   PCUDA_PHOTO_GAUSSIAN_NOISE  farg[0] = scale, iarg[0] = per_channel: v + scale z, z = Box-Muller in float64 of the first
+ *                               two words of Philox4x32-10(key = seed, counter = element index; pixel index if !per_channel)
+ *   PCUDA_PHOTO_DROPOUT         iarg[0] = per_channel, iarg[1] = threshold (uint32 bits): 0 iff the first word < threshold
+ *   PCUDA_PHOTO_COARSE_DROPOUT  the same on an iarg[2] x iarg[3] grid, cell ((y h') / h, (x w') / w)
+ *   PCUDA_PHOTO_INVERT          iarg[0] = channel bit mask: 255 - v
+ *   PCUDA_PHOTO_ADD             iarg[ch]: clipped integer add
+ *   PCUDA_PHOTO_MULTIPLY        farg[ch]: floor(v m + 0.5) clipped
+ *   PCUDA_PHOTO_GRAYSCALE       farg[0] = alpha, c = 3 (channel 0 = red): g = 0.299 c0 + 0.587 c1 + 0.114 c2,
+ *                               (1 - alpha) v + alpha g; c = 1: copy
+ * The result depends on (image, program) only, never on the launch geometry.  `in` is never written and in == out is
+ * rejected; slots == 0 copies.  workspace: pcuda_photometric_workspace_size bytes, 16-byte aligned, needed for slots > 1. */
+#define PCUDA_PHOTO_NOP 0
+#define PCUDA_PHOTO_GAUSSIAN_BLUR 1
+#define PCUDA_PHOTO_AVERAGE_BLUR 2
+#define PCUDA_PHOTO_MEDIAN_BLUR 3
+#define PCUDA_PHOTO_CONV3X3 4
+#define PCUDA_PHOTO_GAUSSIAN_NOISE 5
+#define PCUDA_PHOTO_DROPOUT 6
+#define PCUDA_PHOTO_COARSE_DROPOUT 7
+#define PCUDA_PHOTO_INVERT 8
+#define PCUDA_PHOTO_ADD 9
+#define PCUDA_PHOTO_MULTIPLY 10
+#define PCUDA_PHOTO_GRAYSCALE 11
+size_t pcuda_photometric_workspace_size(int b, int h, int w, int c);
+int pcuda_photometric(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
+                      const int* iarg, const double* farg, const unsigned long long* seed, void* workspace,
+                      size_t workspace_bytes, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

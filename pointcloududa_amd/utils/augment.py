@@ -19,7 +19,11 @@ pinned against ``scipy.ndimage.affine_transform`` by ``tests/golden/augment.npz`
 * masks take order 0 and fill 0 whatever the image's order and ``cval`` are
 
 The heavy pipeline (``augmentation``: Superpixels, median blur, elastic, piecewise affine, hue/saturation ...) is out of
-scope."""
+scope.  The photometric operators of ``augmentation2`` (blurs, sharpen / emboss, noise, dropouts, invert, add, multiply,
+grayscale) live in ``utils/photometric.py`` (f7) and are re-exported here; ``augment_batch(.., photometric=program)`` and
+``AugmentedBatches(.., photometric_preset=..)`` apply them to uint8 images in front of the warp.  Not built, there or here:
+``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)``, ``AddToHueAndSaturation``, ``CropAndPad`` and the
+elastic / piecewise / perspective warps."""
 from __future__ import annotations
 
 import math
@@ -31,6 +35,8 @@ import torch
 
 from .. import kernels as K
 from .npy2point import masks_to_pointclouds
+from .photometric import (PHOTOMETRIC_PRESET, PhotoProgram, emboss_weights, gaussian_weights, photometric_aug,  # noqa: F401
+                          sample_program, sharpen_weights, upload_program)
 
 OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
 
@@ -189,7 +195,8 @@ def _labels(masks: torch.Tensor) -> torch.Tensor:
 
 def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optional[AugmentParams], num_classes: int = 5,
                   crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
-                  firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True):
+                  firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True,
+                  photometric: Optional[PhotoProgram] = None):
     """``data_generator_mmwhs.py:245-274`` after the file reads (``rescale="minmax"``, fp32 images), or
     ``data_generator_mscmrseg.py:305-317`` (``rescale="div255"``, uint8 images), on the device: images ``[B,H,W,C]``,
     integer masks ``[B,H,W]`` (or ``[B,H,W,1]``) ->
@@ -204,10 +211,18 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
     ``resample_verts`` re-samples the point cloud from the FULL-size warped mask (``:255-263``); the mask is written by the
     same launch (``fused_mask``) or by a second launch of the kernel over the full image.  Otherwise ``verts`` (integer
     vertices stored with the data set) are only scaled.  The augmentation adds no host synchronisation; the sampler's one
-    ``counts.max()`` is its own."""
+    ``counts.max()`` is its own.
+
+    ``photometric``: a ``PhotoProgram`` applied to the uint8 images in front of the warp (``photometric_aug``: the
+    photometric part of ``augmentation2``, ``data_generator_mscmrseg.py:87-132``); masks and vertices are untouched by it.  fp32
+    images (``rescale="minmax"``) with a program raise ``TypeError``."""
     lab = _labels(masks)
     b, h, w, _ = images_hwc.shape
     dev = images_hwc.device
+    if photometric is not None:
+        if rescale == "minmax" or images_hwc.dtype != torch.uint8:
+            raise TypeError("augment_batch: a photometric program takes uint8 images (rescale='div255' or None)")
+        images_hwc = photometric_aug(images_hwc, photometric)
     inv, order, cval = upload_params(params, b, h, w, dev)
     mm = None
     if rescale == "minmax":
@@ -272,19 +287,28 @@ class AugmentedBatches:
     integer vertices as a third item) and yields the ``(x [B,C,h,w] fp32, y [B,K,h,w] uint8 one-hot, z [B,300,3] fp32)``
     device tensors ``train_epoch`` consumes.  Raw batches go to the device one ahead through pinned staging buffers
     (``DeviceBatches``); the parameters of each batch are drawn from ``rng`` on the host and ride along through pinned,
-    non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last."""
+    non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
+    ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
+    uint8 images in front of the warp."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
-                 crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2):
-        if preset == "heavy":
+                 crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
+                 photometric_preset: Optional[str] = None):
+        if preset == "heavy" or photometric_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
         if preset not in _PRESETS:
             raise ValueError("unknown augmentation preset %r" % (preset,))
+        if photometric_preset is not None and photometric_preset != PHOTOMETRIC_PRESET:
+            raise ValueError("unknown photometric preset %r" % (photometric_preset,))
+        if photometric_preset is not None and rescale == "minmax":
+            raise TypeError("AugmentedBatches: a photometric preset takes uint8 images (rescale='div255' or None)")
         from .._epoch import DeviceBatches      # (imports the trainer: only when batches are actually wrapped)
         self.batches = DeviceBatches(iterator, device, depth)
         self.preset, self.rng = preset, rng
         self.num_classes, self.crop_size, self.rescale, self.resample_verts = num_classes, crop_size, rescale, resample_verts
+        self.photometric_preset = photometric_preset
         self.last_params: Optional[AugmentParams] = None
+        self.last_program: Optional[PhotoProgram] = None
 
     def __iter__(self):
         return self
@@ -294,5 +318,7 @@ class AugmentedBatches:
         images, masks = item[0], item[1]
         verts = item[2] if len(item) > 2 else None
         self.last_params = sample_params(images.shape[0], self.preset, self.rng)
+        if self.photometric_preset is not None:
+            self.last_program = sample_program(images.shape[0], self.photometric_preset, self.rng)
         return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
-                             resample_verts=self.resample_verts, verts=verts)
+                             resample_verts=self.resample_verts, verts=verts, photometric=self.last_program)
