@@ -434,6 +434,42 @@ size_t pcuda_photometric_workspace_size(int b, int h, int w, int c);
 int pcuda_photometric(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
                       const int* iarg, const double* farg, const unsigned long long* seed, void* workspace,
                       size_t workspace_bytes, pcuda_stream_t s);
+/* device-side geometric augmentation: the warps of ImageProcessor.augmentation (data_generator_mscmrseg.py:20-84; called at
+ * :305-309) on uint8 images [b][h][w][c], c = 1..4, h, w >= 2, and optional int32 labels [b][h][w], as a per-sample program
+ * of `slots` (0..8) slots in device memory: opcode [b][slots], iarg [b][slots][4], farg [b][slots][32] (float64),
+ * seed [b][slots] (64-bit Philox key).  Every slot is one resampling, one launch; the value is uint8 again between two slots.
+ * A slot computes a source coordinate (sx, sy) per output pixel (x, y) in float64 and samples there:
+ *   iarg[0]  order: 0 = the texel at floor(s + 0.5); anything else = bilinear over (floor(s), floor(s) + 1), summed as
+ *            pcuda_augment_assemble sums, floor(v + 0.5) clipped to [0, 255]
+ *   iarg[1]  border mode per neighbour index: PCUDA_GEO_CONSTANT (cval = iarg[2]), _EDGE, _REFLECT (no edge repeat),
+ *            _SYMMETRIC, _WRAP; anything else behaves as constant
+ * Labels take order 0 and constant 0 at the same coordinate.  A NaN coordinate or one with |s| > 2^30 takes cval (labels 0)
+ * in every mode; indices are folded in integers before any load.  Per opcode:
+ *   PCUDA_GEO_NOP               copy (so does an unknown opcode: the host validates programs)
+ *   PCUDA_GEO_HOMOGRAPHY        farg[0..8] = inverse 3x3 map h, row-major: d = (h6 x + h7 y) + h8,
+ *                               sx = ((h0 x + h1 y) + h2) / d, sy = ((h3 x + h4 y) + h5) / d
+ *   PCUDA_GEO_ELASTIC           iarg[3] = radius r 0..4, farg[0] = alpha, farg[1..1+r] = one-sided normalised weights;
+ *                               noise 2 u - 1, u = (word + 0.5) 2^-32 of words 0 (dx) and 1 (dy) of Philox4x32-10
+ *                               (key = seed, counter = y w + x), reflect-101 outside the image; blurred along y, then
+ *                               along x (t = n[0] w[0]; d = r..1: t += (n[-d] + n[d]) w[d]); sx = x + alpha bx, sy = y + alpha by
+ *   PCUDA_GEO_PIECEWISE_AFFINE  iarg[3] = G 2..4, farg[i G + j] / farg[16 + i G + j] = source x / y of control point (i, j)
+ *                               of the regular G x G grid over [0, w-1] x [0, h-1]; cells split along the TL-BR diagonal
+ * The result depends on (image, program) only, never on the launch geometry.  `in` (labels_in) is never written and
+ * in == out is rejected; labels_in and labels_out are both NULL or both given; slots == 0 copies.  workspace:
+ * pcuda_geometric_workspace_size bytes, 16-byte aligned, needed for slots > 1. */
+#define PCUDA_GEO_NOP 0
+#define PCUDA_GEO_HOMOGRAPHY 1
+#define PCUDA_GEO_ELASTIC 2
+#define PCUDA_GEO_PIECEWISE_AFFINE 3
+#define PCUDA_GEO_CONSTANT 0
+#define PCUDA_GEO_EDGE 1
+#define PCUDA_GEO_REFLECT 2
+#define PCUDA_GEO_SYMMETRIC 3
+#define PCUDA_GEO_WRAP 4
+size_t pcuda_geometric_workspace_size(int b, int h, int w, int c, int with_labels);
+int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w, int c,
+                    int slots, const int* opcode, const int* iarg, const double* farg, const unsigned long long* seed,
+                    void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

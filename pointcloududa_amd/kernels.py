@@ -920,6 +920,40 @@ def photometric(images_u8, opcode, iarg, farg, seed, out=None):
     return out
 
 
+def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=None):
+    """A per-sample geometric program over uint8 ``[B,H,W,C]`` images and optional int32 ``[B,H,W]`` labels
+    (``pcuda_geometric``): ``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,4]``, ``farg`` float64 ``[B,S,32]``, ``seed`` int64
+    ``[B,S]`` (the bits of the 64-bit Philox key), all on the device, ``S`` = 0..8 -> ``(images, labels or None)``, new tensors
+    (the inputs are never written)."""
+    _req(images_u8, torch.uint8)
+    if images_u8.dim() != 4:
+        raise TypeError("geometric: uint8 [B,H,W,C] images")
+    images_u8 = images_u8.contiguous()
+    b, h, w, c = images_u8.shape
+    _req(opcode, torch.int32); _req(iarg, torch.int32); _req(farg, torch.float64); _req(seed, torch.int64)
+    slots = opcode.shape[1] if opcode.dim() == 2 else -1
+    if tuple(opcode.shape) != (b, slots) or tuple(iarg.shape) != (b, slots, 4) or tuple(farg.shape) != (b, slots, 32) or \
+            tuple(seed.shape) != (b, slots):
+        raise ValueError("geometric: the program's arrays do not match the batch of %d" % b)
+    if labels is not None:
+        _req(labels, torch.int32)
+        labels = labels.contiguous()
+        if tuple(labels.shape) != (b, h, w):
+            raise ValueError("geometric: label shape %r does not match the images" % (tuple(labels.shape),))
+        if labels_out is None:
+            labels_out = torch.empty_like(labels)
+    else:
+        labels_out = None
+    if out is None:
+        out = torch.empty_like(images_u8)
+    nbytes = L.lib().pcuda_geometric_workspace_size(b, h, w, c, int(labels is not None)) if slots > 1 else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    check(L.lib().pcuda_geometric(images_u8.data_ptr(), out.data_ptr(), _ptr(labels), _ptr(labels_out), b, h, w, c, slots,
+                                  opcode.contiguous().data_ptr(), iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(),
+                                  seed.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()), "geometric")
+    return out, labels_out
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum."""
     if x.dtype not in (torch.float32, torch.uint8):

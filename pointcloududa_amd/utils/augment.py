@@ -21,9 +21,12 @@ pinned against ``scipy.ndimage.affine_transform`` by ``tests/golden/augment.npz`
 The heavy pipeline (``augmentation``: Superpixels, median blur, elastic, piecewise affine, hue/saturation ...) is out of
 scope.  The photometric operators of ``augmentation2`` (blurs, sharpen / emboss, noise, dropouts, invert, add, multiply,
 grayscale) live in ``utils/photometric.py`` (f7) and are re-exported here; ``augment_batch(.., photometric=program)`` and
-``AugmentedBatches(.., photometric_preset=..)`` apply them to uint8 images in front of the warp.  Not built, there or here:
-``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)``, ``AddToHueAndSaturation``, ``CropAndPad`` and the
-elastic / piecewise / perspective warps."""
+``AugmentedBatches(.., photometric_preset=..)`` apply them to uint8 images in front of the warp.  The warps of the heavy
+pipeline (``CropAndPad``, the +/-45 degree ``Affine`` with every border mode, elastic, piecewise affine, perspective) live in
+``utils/geometric.py`` (f8) and are re-exported here too; ``augment_batch(.., heavy=plan)`` and
+``AugmentedBatches(.., heavy_preset="heavy_device")`` run a whole plan (photometric and geometric stages interleaved) on the uint8
+images and the masks in front of the f6 launch.  Not built, there or here: ``Superpixels``,
+``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and ``AddToHueAndSaturation``; the string ``"heavy"`` keeps raising."""
 from __future__ import annotations
 
 import math
@@ -37,6 +40,8 @@ from .. import kernels as K
 from .npy2point import masks_to_pointclouds
 from .photometric import (PHOTOMETRIC_PRESET, PhotoProgram, emboss_weights, gaussian_weights, photometric_aug,  # noqa: F401
                           sample_program, sharpen_weights, upload_program)
+from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, HeavyPlan, geometric_aug, heavy_aug,  # noqa: F401
+                        sample_geo_program, sample_heavy_plan, upload_geo_program)
 
 OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
 
@@ -196,7 +201,7 @@ def _labels(masks: torch.Tensor) -> torch.Tensor:
 def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optional[AugmentParams], num_classes: int = 5,
                   crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
                   firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True,
-                  photometric: Optional[PhotoProgram] = None):
+                  photometric: Optional[PhotoProgram] = None, heavy: Optional[HeavyPlan] = None):
     """``data_generator_mmwhs.py:245-274`` after the file reads (``rescale="minmax"``, fp32 images), or
     ``data_generator_mscmrseg.py:305-317`` (``rescale="div255"``, uint8 images), on the device: images ``[B,H,W,C]``,
     integer masks ``[B,H,W]`` (or ``[B,H,W,1]``) ->
@@ -215,7 +220,15 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
 
     ``photometric``: a ``PhotoProgram`` applied to the uint8 images in front of the warp (``photometric_aug``: the
     photometric part of ``augmentation2``, ``data_generator_mscmrseg.py:87-132``); masks and vertices are untouched by it.  fp32
-    images (``rescale="minmax"``) with a program raise ``TypeError``."""
+    images (``rescale="minmax"``) with a program raise ``TypeError``.
+
+    ``heavy``: a ``HeavyPlan`` (``sample_heavy_plan``: the reference's default ``augmentation``, ``data_generator_mscmrseg.py:20-84``)
+    run on the uint8 images AND the masks in front of everything else (``heavy_aug``); with ``resample_verts`` the point
+    cloud is drawn from the full-size warped mask, as without a plan.  fp32 images with a plan raise ``TypeError``."""
+    if heavy is not None:
+        if rescale == "minmax" or images_hwc.dtype != torch.uint8:
+            raise TypeError("augment_batch: a heavy plan takes uint8 images (rescale='div255' or None)")
+        images_hwc, masks = heavy_aug(images_hwc, masks, heavy)
     lab = _labels(masks)
     b, h, w, _ = images_hwc.shape
     dev = images_hwc.device
@@ -289,14 +302,22 @@ class AugmentedBatches:
     (``DeviceBatches``); the parameters of each batch are drawn from ``rng`` on the host and ride along through pinned,
     non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
-    uint8 images in front of the warp."""
+    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"`` or ``"mscmrseg_aug2_device"``) ``preset`` must
+    be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
-                 photometric_preset: Optional[str] = None):
-        if preset == "heavy" or photometric_preset == "heavy":
+                 photometric_preset: Optional[str] = None, heavy_preset: Optional[str] = None):
+        if preset == "heavy" or photometric_preset == "heavy" or heavy_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
-        if preset not in _PRESETS:
+        if heavy_preset is not None:
+            if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET):
+                raise ValueError("unknown heavy preset %r" % (heavy_preset,))
+            if preset is not None or photometric_preset is not None:
+                raise ValueError("AugmentedBatches: a heavy preset is the whole recipe (preset and photometric_preset must be None)")
+            if rescale == "minmax":
+                raise TypeError("AugmentedBatches: a heavy preset takes uint8 images (rescale='div255' or None)")
+        elif preset not in _PRESETS:
             raise ValueError("unknown augmentation preset %r" % (preset,))
         if photometric_preset is not None and photometric_preset != PHOTOMETRIC_PRESET:
             raise ValueError("unknown photometric preset %r" % (photometric_preset,))
@@ -306,7 +327,8 @@ class AugmentedBatches:
         self.batches = DeviceBatches(iterator, device, depth)
         self.preset, self.rng = preset, rng
         self.num_classes, self.crop_size, self.rescale, self.resample_verts = num_classes, crop_size, rescale, resample_verts
-        self.photometric_preset = photometric_preset
+        self.photometric_preset, self.heavy_preset = photometric_preset, heavy_preset
+        self.last_plan: Optional[HeavyPlan] = None
         self.last_params: Optional[AugmentParams] = None
         self.last_program: Optional[PhotoProgram] = None
 
@@ -317,6 +339,11 @@ class AugmentedBatches:
         item = next(self.batches)
         images, masks = item[0], item[1]
         verts = item[2] if len(item) > 2 else None
+        if self.heavy_preset is not None:
+            self.last_params = AugmentParams.identity(images.shape[0])
+            self.last_plan = sample_heavy_plan(images.shape[0], self.heavy_preset, self.rng, images.shape[1], images.shape[2])
+            return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
+                                 resample_verts=self.resample_verts, verts=verts, heavy=self.last_plan)
         self.last_params = sample_params(images.shape[0], self.preset, self.rng)
         if self.photometric_preset is not None:
             self.last_program = sample_program(images.shape[0], self.photometric_preset, self.rng)

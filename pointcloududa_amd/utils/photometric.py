@@ -33,9 +33,9 @@ and is pinned by ``tests/golden/photometric.npz`` (``scripts/make_photometric_go
 restatement).
 
 NOT built (named in DESIGN.md f7): ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
-``AddToHueAndSaturation`` (the other three ``SomeOf`` entries: SLIC, simplex noise, cv2's uint8 HSV); ``CropAndPad`` (geometric:
-it moves the mask; its constant-fill case is an ``AugmentParams`` scale + translate); the elastic / piecewise / perspective
-warps of the heavy ``augmentation`` pipeline -- ``"heavy"`` keeps raising."""
+``AddToHueAndSaturation`` (the other three ``SomeOf`` entries: SLIC, simplex noise, cv2's uint8 HSV) -- ``"heavy"`` keeps
+raising.  ``CropAndPad`` and the elastic / piecewise / perspective warps of the heavy ``augmentation`` pipeline move the mask:
+they live in ``utils/geometric.py`` (f8), whose ``sample_heavy_plan`` interleaves them with the operators of this file."""
 from __future__ import annotations
 
 from dataclasses import dataclass
