@@ -215,7 +215,8 @@ int pcuda_wgrad_reduce_batch(const pcuda_reduce_job* host_jobs, int njobs, pcuda
  * (unet.py:23-30,116-125); also BatchNorm1d of PointNetCls.py (hw = points or 1).
  * ---------------------------------------------------------------------------------- */
 /* reduce per-tile partials -> mean, invstd, scale = gamma*invstd, shift = beta - mean*scale;
- * running stats updated with momentum (unbiased variance), torch semantics. count = n*h*w */
+ * running stats updated with momentum (unbiased variance), torch semantics. count = n*h*w.
+ * count == 1: var = 0 (unbiased = var), scale = 0 and shift = beta -- the output is the constant beta */
 int pcuda_bn_finalize(const float* partials, int ntiles, int c, long long count, const float* gamma,
                       const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                       float* mean, float* invstd, float* scale, float* shift, pcuda_stream_t s);

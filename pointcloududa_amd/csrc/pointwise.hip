@@ -100,12 +100,14 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
   if (threadIdx.x == 0) {
     const double m = sh[0][0] / count;
     double var = sh[1][0] / count - m * m;
-    if (var < 0) var = 0;
+    // count == 1: the variance of one value is 0 by definition, not the rounding residue of the float32 a * a next to
+    // eps; the normalised value is then 0 and the output the constant beta, which scale = 0 states exactly
+    if (var < 0 || count <= 1) var = 0;
     const float is = (float)(1.0 / sqrt(var + (double)eps));
     const float g = gamma ? gamma[ch] : 1.f, b = beta ? beta[ch] : 0.f;
     mean[ch] = (float)m;
     invstd[ch] = is;
-    const float sc = g * is;
+    const float sc = count > 1 ? g * is : 0.f;
     scale[ch] = sc;
     shift[ch] = b - (float)m * sc;
     if (running_mean) {
@@ -249,7 +251,9 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     if (dgamma) dgamma[ch] = accumulate ? dgamma[ch] + (float)S2 : (float)S2;
     if (dbeta) dbeta[ch] = accumulate ? dbeta[ch] + (float)S1 : (float)S1;
     const double g = gamma ? (double)gamma[ch] : 1.0, is = invstd[ch], m = mean[ch];
-    const double sc = g * is;
+    // count == 1: the output of a training BatchNorm over one value is the constant beta, its input gradient exactly 0
+    // (the three terms below would leave the rounding residue of sc * S1 instead)
+    const double sc = count == 1 ? 0.0 : g * is;
     coef[ch * 3 + 0] = (float)sc;
     // count < 0: FROZEN statistics (eval-mode BatchNorm, mean / invstd from the running buffers): the layer is a fixed
     // per-channel affine, the batch-mean terms of the training formula vanish; dgamma / dbeta are the same sums
