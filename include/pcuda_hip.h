@@ -471,6 +471,45 @@ size_t pcuda_geometric_workspace_size(int b, int h, int w, int c, int with_label
 int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w, int c,
                     int slots, const int* opcode, const int* iarg, const double* farg, const unsigned long long* seed,
                     void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* device-side stylize augmentation: the three entries of the reference's SomeOf lists that pcuda_photometric and
+ * pcuda_geometric do not hold (data_generator_mscmrseg.py:46, 57-60, 69) on uint8 images [b][h][w][c], c = 1..4, as a per-sample
+ * program of `slots` (0..8) slots in device memory: opcode [b][slots], iarg [b][slots][12], farg [b][slots][16] (float64),
+ * table [b][slots][768] (float64: three coarse grids of up to 16 x 16 values, row-major, grid k at offset 256 k), seed
+ * [b][slots] (64-bit Philox key).  The value is uint8 between two slots.  rdiv(a, b) = floor((2 a + b) / (2 b)).  Per opcode:
+ *   PCUDA_STYLE_NOP                  copy (so does an unknown opcode: the host validates programs)
+ *   PCUDA_STYLE_HUE_SATURATION       c = 3 (channel 0 = red; any other c copies), iarg[0] = dh, iarg[1] = ds, integers only:
+ *                                    V = max, d = V - min, S = rdiv(255 d, V) (0 if V = 0), H = 0 if d = 0 else
+ *                                    (base + rdiv(30 num, d)) mod 180, (base, num) = (0, g - b) if V == r, (60, b - r) if V == g,
+ *                                    else (120, r - g); H' = (H + dh) mod 180 >= 0, S' = clip(S + ds, 0, 255); sec = H' / 30,
+ *                                    F = H' % 30, p = rdiv(V (255 - S'), 255), q = rdiv(V (7650 - S' F), 7650),
+ *                                    t = rdiv(V (7650 - S' (30 - F)), 7650); (r, g, b) by sector 0..5 = (V,t,p), (q,V,p),
+ *                                    (p,V,t), (p,q,V), (t,p,V), (V,p,q)
+ *   PCUDA_STYLE_NOISE_ALPHA_CONV3X3  iarg[0] = n 1..3 grids, iarg[1] = upscale (0 nearest: cell ((y h') / h, (x w') / w);
+ *                                    1 bilinear: sy = (y + 0.5) h' / h - 0.5 clamped to [0, h' - 1], rows g00 (1 - fx) + g01 fx,
+ *                                    then top (1 - fy) + bot fy), iarg[2] = aggregation (0 min, 1 mean in grid order, 2 max),
+ *                                    iarg[3] = sigmoid on: m = 1 / (1 + exp(-(20 (m - 0.5) - farg[9]))), iarg[4 + 2 k],
+ *                                    iarg[5 + 2 k] = h', w' of grid k (2..16); farg[0..8] = 3x3 correlation as
+ *                                    PCUDA_PHOTO_CONV3X3, e = its rounded result; out = floor((1 - m) x + m e + 0.5) clipped;
+ *                                    float64 in this order, one m for all channels
+ *   PCUDA_STYLE_SUPERPIXELS          iarg[0], iarg[1] = gy, gx (gy gx <= 256), iarg[2] = updates 0..10, iarg[3] = M2
+ *                                    (compactness squared), iarg[4] = threshold (uint32 bits); integers only.  Centre
+ *                                    k = j gx + i starts at (((2j+1) h) / (2 gy), ((2i+1) w) / (2 gx)) with that pixel's colour; a
+ *                                    pixel takes, among the centres of the 3x3 grid cells around its cell ((y gy) / h,
+ *                                    (x gx) / w) that exist, the smallest 64-bit D = dc2 S2 + M2 ds2 (S2 = max(1, (h w) / (gy gx))),
+ *                                    ties to the lowest k; update: centre = rdiv(sum, n) of colour, y, x (n = 0: stays); after
+ *                                    the updates and one last assignment segment k takes its mean colour rdiv(sum, n) iff the
+ *                                    first word of Philox4x32-10(key = seed, counter = k) < threshold, else it is copied
+ * The result depends on (image, program) only, never on the launch geometry.  `in` is never written and in == out is
+ * rejected; slots == 0 copies.  workspace: pcuda_stylize_workspace_size bytes, 16-byte aligned, needed for slots > 0 (a
+ * uint8 label plane and the second image of the ping-pong). */
+#define PCUDA_STYLE_NOP 0
+#define PCUDA_STYLE_HUE_SATURATION 1
+#define PCUDA_STYLE_NOISE_ALPHA_CONV3X3 2
+#define PCUDA_STYLE_SUPERPIXELS 3
+size_t pcuda_stylize_workspace_size(int b, int h, int w, int c);
+int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode, const int* iarg,
+                  const double* farg, const double* table, const unsigned long long* seed, void* workspace,
+                  size_t workspace_bytes, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

@@ -954,6 +954,30 @@ def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=
     return out, labels_out
 
 
+def stylize(images_u8, opcode, iarg, farg, table, seed, out=None):
+    """A per-sample stylize program over uint8 ``[B,H,W,C]`` images (``pcuda_stylize``): ``opcode`` int32 ``[B,S]``, ``iarg`` int32
+    ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed`` int64 ``[B,S]`` (the bits of the 64-bit
+    Philox key), all on the device, ``S`` = 0..8 -> a new uint8 tensor (the input is never written)."""
+    _req(images_u8, torch.uint8)
+    if images_u8.dim() != 4:
+        raise TypeError("stylize: uint8 [B,H,W,C] images")
+    images_u8 = images_u8.contiguous()
+    b, h, w, c = images_u8.shape
+    _req(opcode, torch.int32); _req(iarg, torch.int32); _req(farg, torch.float64); _req(table, torch.float64); _req(seed, torch.int64)
+    slots = opcode.shape[1] if opcode.dim() == 2 else -1
+    if tuple(opcode.shape) != (b, slots) or tuple(iarg.shape) != (b, slots, 12) or tuple(farg.shape) != (b, slots, 16) or \
+            tuple(table.shape) != (b, slots, 768) or tuple(seed.shape) != (b, slots):
+        raise ValueError("stylize: the program's arrays do not match the batch of %d" % b)
+    if out is None:
+        out = torch.empty_like(images_u8)
+    nbytes = L.lib().pcuda_stylize_workspace_size(b, h, w, c) if slots > 0 else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    check(L.lib().pcuda_stylize(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, opcode.contiguous().data_ptr(),
+                                iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(), table.contiguous().data_ptr(),
+                                seed.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()), "stylize")
+    return out
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum."""
     if x.dtype not in (torch.float32, torch.uint8):

@@ -18,15 +18,17 @@ pinned against ``scipy.ndimage.affine_transform`` by ``tests/golden/augment.npz`
   ``cval`` for a neighbour outside the image; the result is ``floor(v + 0.5)`` clipped to [0, 255]
 * masks take order 0 and fill 0 whatever the image's order and ``cval`` are
 
-The heavy pipeline (``augmentation``: Superpixels, median blur, elastic, piecewise affine, hue/saturation ...) is out of
-scope.  The photometric operators of ``augmentation2`` (blurs, sharpen / emboss, noise, dropouts, invert, add, multiply,
+imgaug's own parameter stream of the heavy pipeline (``augmentation``) is not reproduced: the string ``"heavy"`` keeps
+raising.  The photometric operators of ``augmentation2`` (blurs, sharpen / emboss, noise, dropouts, invert, add, multiply,
 grayscale) live in ``utils/photometric.py`` (f7) and are re-exported here; ``augment_batch(.., photometric=program)`` and
 ``AugmentedBatches(.., photometric_preset=..)`` apply them to uint8 images in front of the warp.  The warps of the heavy
 pipeline (``CropAndPad``, the +/-45 degree ``Affine`` with every border mode, elastic, piecewise affine, perspective) live in
 ``utils/geometric.py`` (f8) and are re-exported here too; ``augment_batch(.., heavy=plan)`` and
 ``AugmentedBatches(.., heavy_preset="heavy_device")`` run a whole plan (photometric and geometric stages interleaved) on the uint8
-images and the masks in front of the f6 launch.  Not built, there or here: ``Superpixels``,
-``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and ``AddToHueAndSaturation``; the string ``"heavy"`` keeps raising."""
+images and the masks in front of the f6 launch.  ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
+``AddToHueAndSaturation`` live in ``utils/stylize.py`` (f9) and are re-exported here as well: the presets
+``"heavy_full_device"`` and ``"mscmrseg_aug2_full_device"`` hold all fifteen / twelve ``SomeOf`` entries of the two recipes, while
+``"heavy_device"`` and ``"mscmrseg_aug2_device"`` keep drawing what they drew without the three."""
 from __future__ import annotations
 
 import math
@@ -42,6 +44,8 @@ from .photometric import (PHOTOMETRIC_PRESET, PhotoProgram, emboss_weights, gaus
                           sample_program, sharpen_weights, upload_program)
 from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, HeavyPlan, geometric_aug, heavy_aug,  # noqa: F401
                         sample_geo_program, sample_heavy_plan, upload_geo_program)
+from .stylize import (AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, directed_edge_weights, edge_detect_weights,  # noqa: F401
+                      sample_style_program, simplex_grid, stylize_aug, superpixel_grid, upload_style_program)
 
 OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
 
@@ -302,7 +306,7 @@ class AugmentedBatches:
     (``DeviceBatches``); the parameters of each batch are drawn from ``rng`` on the host and ride along through pinned,
     non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
-    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"`` or ``"mscmrseg_aug2_device"``) ``preset`` must
+    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"`` or their ``_full_`` twins) ``preset`` must
     be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
@@ -311,7 +315,7 @@ class AugmentedBatches:
         if preset == "heavy" or photometric_preset == "heavy" or heavy_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
         if heavy_preset is not None:
-            if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET):
+            if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET, HEAVY_FULL_PRESET, AUG2_FULL_PRESET):
                 raise ValueError("unknown heavy preset %r" % (heavy_preset,))
             if preset is not None or photometric_preset is not None:
                 raise ValueError("AugmentedBatches: a heavy preset is the whole recipe (preset and photometric_preset must be None)")

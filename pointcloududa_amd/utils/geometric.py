@@ -34,9 +34,10 @@ imgaug / skimage / cv2 are not vendored by the reference: parity with imgaug is 
 and is pinned by ``tests/golden/geometric.npz`` (``scripts/make_geometric_golden.py``: a scipy ``map_coordinates`` and a
 plain-numpy restatement).  Two divergences from the reference's recipe: numpy's statistical pad modes (``linear_ramp``,
 ``maximum``, ``mean``, ``median``, ``minimum``) are not built, so ``CropAndPad`` draws from the five border modes above, and
-imgaug's parameter stream is not reproduced.  NOT built: ``Superpixels``,
-``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)``, ``AddToHueAndSaturation`` and interpolation orders above 1; the string
-``"heavy"`` keeps raising ``NotImplementedError``."""
+imgaug's parameter stream is not reproduced.  NOT built: interpolation orders above 1; the string ``"heavy"``
+keeps raising ``NotImplementedError``.  ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
+``AddToHueAndSaturation`` live in ``utils/stylize.py`` (f9): the presets ``"heavy_full_device"`` and
+``"mscmrseg_aug2_full_device"`` of ``sample_heavy_plan`` interleave them with the entries of this file and f7's."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -47,7 +48,9 @@ import torch
 
 from .. import kernels as K
 from . import photometric as P
+from . import stylize as St
 from .photometric import PhotoProgram, gaussian_weights, photometric_aug
+from .stylize import AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, stylize_aug
 
 OP_NOP, OP_HOMOGRAPHY, OP_ELASTIC, OP_PIECEWISE = range(4)
 OP_NAMES = ("NOP", "HOMOGRAPHY", "ELASTIC", "PIECEWISE_AFFINE")
@@ -290,6 +293,9 @@ def geometric_aug(images: torch.Tensor, masks: Optional[torch.Tensor], program: 
 
 # ------------------------------------------------------------------------------------------------ sampling
 _PHOTO_BLOCK = tuple(("p", e) for e in range(9))
+# the reference's list order: Superpixels, blur, sharpen, emboss, SimplexNoiseAlpha, noise, dropout, invert, add, hue, ...
+_FULL_BLOCK = ((("s", St.ENTRY_SUPERPIXELS),) + _PHOTO_BLOCK[:3] + (("s", St.ENTRY_NOISE_ALPHA),) + _PHOTO_BLOCK[3:7] +
+               (("s", St.ENTRY_HUE),) + _PHOTO_BLOCK[7:])
 _PRESETS = {
     # data_generator_mscmrseg.py:23-82 minus Superpixels, SimplexNoiseAlpha, AddToHueAndSaturation
     HEAVY_DEVICE_PRESET: dict(
@@ -297,7 +303,14 @@ _PRESETS = {
         block=_PHOTO_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
     # data_generator_mscmrseg.py:89-130 minus the same three
     AUG2_DEVICE_PRESET: dict(outer=(("g", ENTRY_CROP_AND_PAD), "block"), block=_PHOTO_BLOCK),
+    # data_generator_mscmrseg.py:23-82, all fifteen SomeOf entries (f9)
+    HEAVY_FULL_PRESET: dict(
+        outer=(("g", ENTRY_FLIPLR), ("g", ENTRY_FLIPUD), ("g", ENTRY_CROP_AND_PAD), ("g", ENTRY_AFFINE), "block"),
+        block=_FULL_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
+    # data_generator_mscmrseg.py:89-130, all twelve
+    AUG2_FULL_PRESET: dict(outer=(("g", ENTRY_CROP_AND_PAD), "block"), block=_FULL_BLOCK),
 }
+_SOMETIMES = {("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE), ("s", St.ENTRY_SUPERPIXELS)}
 _OUTER_P = {ENTRY_FLIPLR: FLIP_LR_P, ENTRY_FLIPUD: FLIP_UD_P, ENTRY_CROP_AND_PAD: SOMETIMES_P, ENTRY_AFFINE: SOMETIMES_P}
 
 
@@ -313,14 +326,14 @@ def _check_preset(preset):
 def _select(b, spec, rng):
     """-> (entries in application order, on bool [B, len(entries)]): one outer and one inner order per batch
     (``random_order=True`` as f6 and f7 draw it); ``SomeOf((0, 5))`` picks a uniform count of distinct block entries per
-    sample, and the three warps inside the block sit behind ``sometimes(0.5)``"""
+    sample, and the three warps inside the block (and, in the full presets, Superpixels) sit behind ``sometimes(0.5)``"""
     outer, block = spec["outer"], spec["block"]
     outer_order, inner_order = rng.permutation(len(outer)), rng.permutation(len(block))
     count = rng.integers(SOMEOF_COUNT[0], SOMEOF_COUNT[1] + 1, b)
     rank = np.argsort(np.argsort(rng.random((b, len(block))), axis=1), axis=1)
     chosen = rank < count[:, None]
-    for k, (kind, _) in enumerate(block):
-        if kind == "g":
+    for k, entry in enumerate(block):
+        if entry in _SOMETIMES:
             chosen[:, k] &= rng.random(b) < SOMETIMES_P
     outer_on = {k: rng.random(b) < _OUTER_P[e[1]] for k, e in enumerate(outer) if e != "block"}
     entries, on = [], []
@@ -442,10 +455,10 @@ def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int
 
 @dataclass
 class HeavyPlan:
-    """The ordered stages of one batch: ``PhotoProgram`` and ``GeoProgram`` alternate; every stage covers the whole batch
-    (a sample without an active entry in a stage holds NOPs there)."""
+    """The ordered stages of one batch: ``PhotoProgram``, ``GeoProgram`` and (f9) ``StyleProgram`` stages, no two neighbours of
+    one kind; every stage covers the whole batch (a sample without an active entry in a stage holds NOPs there)."""
     batch: int
-    stages: List[Union[PhotoProgram, GeoProgram]] = field(default_factory=list)
+    stages: List[Union[PhotoProgram, GeoProgram, StyleProgram]] = field(default_factory=list)
 
     def is_identity(self) -> bool:
         return all(st.is_identity() for st in self.stages)
@@ -459,10 +472,15 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
     ``"heavy_device"``: ``augmentation`` minus Superpixels, SimplexNoiseAlpha and AddToHueAndSaturation -- the outer order is
     over {Fliplr, Flipud, CropAndPad, Affine, SomeOf block}; ``SomeOf`` draws 0..5 of the twelve built entries (f7's nine and
     the three warps, each warp behind ``sometimes(0.5)``).  ``"mscmrseg_aug2_device"``: ``augmentation2`` minus the same
-    three -- ``sometimes(CropAndPad)`` and f7's nine-entry block, in random order."""
+    three -- ``sometimes(CropAndPad)`` and f7's nine-entry block, in random order.
+
+    ``"heavy_full_device"`` and ``"mscmrseg_aug2_full_device"`` (f9): the same two recipes with all fifteen / twelve ``SomeOf``
+    entries -- ``sometimes`` Superpixels, SimplexNoiseAlpha and AddToHueAndSaturation (``utils/stylize.py``) sit in the block
+    at the reference's list positions, and consecutive stylize entries form one ``StyleProgram``."""
     spec = _check_preset(preset)
     entries, on = _select(batch, spec, rng)
     dg, dp = _draw_geo(batch, rng, h, w), _draw_photo(batch, rng)
+    ds = St.draw_style(batch, rng) if any(e[0] == "s" for e in entries) else None
     used = [k for k in range(len(entries)) if on[:, k].any()]      # (an entry nobody drew does not split a stage)
     entries, on = [entries[k] for k in used], on[:, used]
     plan = HeavyPlan(batch)
@@ -474,13 +492,15 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
             e += 1
         used = int(on[:, k:e].sum(1).max()) if batch else 0
         if used:
-            prog = PhotoProgram.identity(batch, used) if kind == "p" else GeoProgram.identity(batch, used)
+            prog = {"p": PhotoProgram, "g": GeoProgram, "s": StyleProgram}[kind].identity(batch, used)
             for i in range(batch):
                 s = 0
                 for q in range(k, e):
                     if on[i, q]:
                         if kind == "p":
                             _encode_photo(prog, i, s, entries[q][1], dp)
+                        elif kind == "s":
+                            St.encode_style(prog, i, s, entries[q][1], ds, h, w)
                         else:
                             _encode_geo(prog, i, s, entries[q][1], dg, h, w)
                         s += 1
@@ -501,6 +521,10 @@ def heavy_aug(images: torch.Tensor, masks: Optional[torch.Tensor], plan: Optiona
     for stage in plan.stages:
         if isinstance(stage, PhotoProgram):
             images = photometric_aug(images, stage)
-        else:
+        elif isinstance(stage, StyleProgram):
+            images = stylize_aug(images, stage)
+        elif isinstance(stage, GeoProgram):
             images, masks = geometric_aug(images, masks, stage)
+        else:
+            raise TypeError("heavy_aug: a stage is a PhotoProgram, a GeoProgram or a StyleProgram, got %s" % type(stage).__name__)
     return images, masks

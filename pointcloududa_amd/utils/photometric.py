@@ -32,9 +32,9 @@ only.  imgaug / cv2 are not vendored by the reference: parity with imgaug is unp
 and is pinned by ``tests/golden/photometric.npz`` (``scripts/make_photometric_golden.py``: a scipy and a plain-numpy
 restatement).
 
-NOT built (named in DESIGN.md f7): ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
-``AddToHueAndSaturation`` (the other three ``SomeOf`` entries: SLIC, simplex noise, cv2's uint8 HSV) -- ``"heavy"`` keeps
-raising.  ``CropAndPad`` and the elastic / piecewise / perspective warps of the heavy ``augmentation`` pipeline move the mask:
+NOT in this program type: ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
+``AddToHueAndSaturation`` (the other three ``SomeOf`` entries) live in ``utils/stylize.py`` (f9); ``"heavy"`` keeps raising (imgaug's
+parameter stream is not reproduced).  ``CropAndPad`` and the elastic / piecewise / perspective warps of the heavy ``augmentation`` pipeline move the mask:
 they live in ``utils/geometric.py`` (f8), whose ``sample_heavy_plan`` interleaves them with the operators of this file."""
 from __future__ import annotations
 
@@ -293,7 +293,8 @@ def sample_program(batch: int, preset: str, rng: np.random.Generator) -> PhotoPr
     random order per batch (as ``sample_params``), 5 slots, seeds drawn from ``rng``.
 
     Absent from the reference's list: ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
-    ``AddToHueAndSaturation``; so is the ``CropAndPad`` in front of it.  imgaug's own parameter stream is not reproduced
+    ``AddToHueAndSaturation`` (``utils/stylize.py``; the preset ``"mscmrseg_aug2_full_device"`` of ``sample_heavy_plan`` holds all
+    twelve); so is the ``CropAndPad`` in front of it.  imgaug's own parameter stream is not reproduced
     (parity unpinned)."""
     if preset == "heavy":
         from .augment import HEAVY_MESSAGE

@@ -1,0 +1,421 @@
+"""Device-side "stylize" augmentation for the loader path: the three entries of the reference's
+``SomeOf`` lists that f7 and f8 left out -- ``Superpixels`` (``src/data_generator_mscmrseg.py:46`` / ``:98``),
+``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` (``:57-60`` / ``:108-111``) and ``AddToHueAndSaturation`` (``:69`` /
+``:120``) -- as a per-sample PROGRAM that one HIP entry point (``csrc/stylize.hip``) runs over uint8 ``[B,H,W,C]`` images.  Masks
+and stored vertices are untouched by all three.
+
+A program has ``S`` slots per sample (``S <= 8``); slot ``s`` of sample ``i`` is ``opcode[i, s]`` with ``iarg[i, s, :12]`` (int32),
+``farg[i, s, :16]`` (float64), ``table[i, s, :768]`` (float64: three coarse grids of up to 16 x 16 values) and ``seed[i, s]``
+(uint64).  ``rdiv(a, b) = floor((2 a + b) / (2 b))``, a true floor.
+
+==========================  ==================================================================================
+``OP_NOP``                  copy
+``OP_HUE_SATURATION``       C = 3, channel 0 = red; ``iarg[0]`` = dh (hue is 0..179), ``iarg[1]`` = ds; integers only:
+                            ``V = max``, ``d = V - min``, ``S = rdiv(255 d, V)``, ``H = (base + rdiv(30 num, d)) mod 180`` with
+                            (base, num) = (0, g - b) | (60, b - r) | (120, r - g) by the first of r, g, b that equals V; ``H' =
+                            (H + dh) mod 180``, ``S' = clip(S + ds, 0, 255)``; back through ``p = rdiv(V (255 - S'), 255)``,
+                            ``q = rdiv(V (7650 - S' F), 7650)``, ``t = rdiv(V (7650 - S' (30 - F)), 7650)``, ``F = H' % 30``, by
+                            sector ``H' // 30``: (V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q)
+``OP_NOISE_ALPHA_CONV3X3``  ``iarg[0]`` = n (1..3 grids), ``iarg[1]`` = upscale (``UPSCALE_NEAREST`` | ``UPSCALE_BILINEAR``),
+                            ``iarg[2]`` = aggregation (``AGG_MIN`` | ``AGG_MEAN`` | ``AGG_MAX``), ``iarg[3]`` = sigmoid on,
+                            ``iarg[4 + 2 k : 6 + 2 k]`` = (h', w') of grid k (2..16 each), ``table[256 k + y w' + x]`` = its values
+                            in [0, 1] (``simplex_grid``, evaluated HERE in float64, as f7 evaluates the Gaussian's weights),
+                            ``farg[0..8]`` = 3x3 correlation weights (``edge_detect_weights``, ``directed_edge_weights``),
+                            ``farg[9]`` = the sigmoid's threshold t.  Each grid is upscaled to H x W (nearest: cell
+                            ``((y h') // H, (x w') // W)``; bilinear: source ``(y + 0.5) h' / H - 0.5`` clamped to
+                            ``[0, h' - 1]``), the n masks are aggregated (the mean sums in grid order), optionally
+                            ``m = 1 / (1 + exp(-(20 (m - 0.5) - t)))``; ``e = to_u8(f7's CONV3X3)`` (reflect-101 border),
+                            ``out = to_u8((1 - m) x + m e)``; float64 in this order, one m for all channels
+``OP_SUPERPIXELS``          ``iarg[0:2]`` = (gy, gx), ``gy gx <= 256``; ``iarg[2]`` = updates (0..10), ``iarg[3]`` = M2 =
+                            ``floor(compactness^2 + 0.5)``, ``farg[0]`` = p_replace (the kernel gets ``floor(p 2^32)`` in
+                            ``iarg[4]``), ``farg[1]`` = compactness, ``seed``.  A grid SLIC in integers only: centre
+                            ``k = j gx + i`` starts at ``(((2j+1) H) // (2 gy), ((2i+1) W) // (2 gx))`` with that pixel's colour; a pixel
+                            takes, among the centres of the 3x3 grid cells around its own cell ``((y gy) // H, (x gx) // W)``
+                            that exist, the smallest ``D = dc2 S2 + M2 ds2`` (``S2 = max(1, (H W) // (gy gx))``), ties to the
+                            lowest k; update: centre = ``rdiv(sum, n)`` of colour, y and x, a centre without pixels stays; after
+                            the updates and one last assignment, segment k takes its mean colour ``rdiv(sum, n)`` iff the first
+                            word of f7's Philox4x32-10 (key = ``seed``, counter = k) is below the threshold, else it is copied
+==========================  ==================================================================================
+
+The value is uint8 again between two slots.  imgaug / cv2 / skimage are not vendored by the reference: parity with imgaug is
+unpinned, the convention is this build's own and is pinned by ``tests/golden/stylize.npz`` (``scripts/make_stylize_golden.py``:
+a vectorised numpy restatement and an independent one -- plain Python integers for hue and superpixels, scipy for
+noise-alpha).  Divergences from imgaug: hue / saturation follow the integer formulas above (cv2's uint8 HSV tables differ by
+a grey level in places) and one value moves both (``per_channel`` is not built); the simplex noise is this file's (gradient
+from Philox, grids of at most 16 x 16, nearest and bilinear upscale only -- no cubic); the superpixels are a grid SLIC without
+a connectivity pass and without imgaug's downscale to 128 pixels.  The string ``"heavy"`` keeps raising (imgaug's parameter
+stream is not reproduced)."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import kernels as K
+
+OP_NOP, OP_HUE_SATURATION, OP_NOISE_ALPHA_CONV3X3, OP_SUPERPIXELS = range(4)
+OP_NAMES = ("NOP", "HUE_SATURATION", "NOISE_ALPHA_CONV3X3", "SUPERPIXELS")
+MAX_SLOTS, IARGS, FARGS = 8, 12, 16
+GRID_VALUES, MAX_GRIDS = 256, 3
+TABLE = MAX_GRIDS * GRID_VALUES
+UPSCALE_NEAREST, UPSCALE_BILINEAR = 0, 1
+AGG_MIN, AGG_MEAN, AGG_MAX = 0, 1, 2
+MAX_SEGMENTS, MAX_UPDATES = 256, 10
+HEAVY_FULL_PRESET, AUG2_FULL_PRESET = "heavy_full_device", "mscmrseg_aug2_full_device"
+
+# data_generator_mscmrseg.py:46, 57-60, 69
+(ENTRY_SUPERPIXELS, ENTRY_NOISE_ALPHA, ENTRY_HUE) = range(3)
+STYLE_ENTRY_NAMES = ("superpixels", "simplex_noise_alpha", "hue_saturation")
+SUPERPIXELS_P_REPLACE, SUPERPIXELS_SEGMENTS = (0.0, 1.0), (20, 200)
+SUPERPIXELS_UPDATES, SUPERPIXELS_COMPACTNESS = 5, 10
+EDGE_ALPHA, EDGE_DIRECTION = (0.5, 1.0), (0.0, 1.0)
+HUE_VALUE = (-20, 20)
+# this build's own (imgaug's defaults where it has one): 1..3 grids of 2..16 cells per side, nearest or bilinear with equal
+# probability, min / mean / max with equal probability, the sigmoid always on with a threshold drawn from N(0, 5)
+NOISE_ITERATIONS, NOISE_SIZE, NOISE_SIGMOID_P, NOISE_THRESH_SIGMA = (1, 3), (2, 16), 1.0, 5.0
+
+_M32 = np.uint64(0xFFFFFFFF)
+_F2, _G2 = 0.5 * (math.sqrt(3.0) - 1.0), (3.0 - math.sqrt(3.0)) / 6.0
+# eight gradients, two squares turned against the axes and the diagonals: with Perlin's (+-1, +-1), (+-1, 0), (0, +-1) the three corner
+# terms cancel to ~1e-14 on whole families of integer points, which puts the mask within rounding error of exactly 1/2
+_GRAD = ((1.0, 0.3), (-0.3, 1.0), (-1.0, -0.3), (0.3, -1.0), (0.8, 0.7), (-0.7, 0.8), (-0.8, -0.7), (0.7, -0.8))
+
+
+def philox_word0(key: int, counter) -> np.ndarray:
+    """uint32: the first word of Philox4x32-10 as ``csrc/photometric.hip`` implements it, key = a 64-bit integer, counter
+    ``(c, 0, 0, 0)`` for every c of the array"""
+    k0, k1 = np.uint64(int(key) & 0xFFFFFFFF), np.uint64(int(key) >> 32)
+    c0 = np.asarray(counter).astype(np.uint64)
+    c1, c2, c3 = np.zeros_like(c0), np.zeros_like(c0), np.zeros_like(c0)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c0.astype(np.uint32)
+
+
+def _philox_word0_scalar(key: int, c: int) -> int:
+    k0, k1 = key & 0xFFFFFFFF, (key >> 32) & 0xFFFFFFFF
+    c0, c1, c2, c3 = c & 0xFFFFFFFF, 0, 0, 0
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0
+
+
+def threshold(p: float) -> int:
+    """``floor(p 2^32)``, at most ``2^32 - 1``: a segment is replaced iff its 32-bit draw is below it"""
+    return min(int(np.floor(float(p) * 4294967296.0)), 4294967295)
+
+
+def edge_detect_weights(alpha: float) -> np.ndarray:
+    """float64 ``[3,3]``: ``(1 - a) I + a [[0,1,0],[1,-4,1],[0,1,0]]`` (imgaug's EdgeDetect)"""
+    ident = np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], dtype=np.float64)
+    eff = np.array([[0, 1, 0], [1, -4, 1], [0, 1, 0]], dtype=np.float64)
+    return (1.0 - float(alpha)) * ident + float(alpha) * eff
+
+
+def directed_edge_weights(alpha: float, direction: float) -> np.ndarray:
+    """float64 ``[3,3]``: imgaug's DirectedEdgeDetect construction.  ``direction`` in turns (0 = up, clockwise): the unit
+    vector ``(cos(a - pi / 2), sin(a - pi / 2))``, ``a = 2 pi direction``; the similarity of neighbour ``(x, y)`` is
+    ``(1 - angle / 180)^4`` with the angle between the two vectors in degrees; the similarities are normalised to sum 1,
+    the centre is -1, and the result is blended with the identity by alpha (imgaug truncates the direction to whole
+    degrees; this does not)"""
+    rad = 2.0 * math.pi * float(direction)
+    dx, dy = math.cos(rad - 0.5 * math.pi), math.sin(rad - 0.5 * math.pi)
+    eff = np.zeros((3, 3), dtype=np.float64)
+    for x in (-1, 0, 1):
+        for y in (-1, 0, 1):
+            if (x, y) != (0, 0):
+                norm = math.sqrt(float(x * x + y * y))
+                cosine = min(1.0, max(-1.0, (x * dx + y * dy) / norm))
+                eff[y + 1, x + 1] = (1.0 - math.degrees(math.acos(cosine)) / 180.0) ** 4
+    eff = eff / eff.sum()
+    eff[1, 1] = -1.0
+    ident = np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], dtype=np.float64)
+    return (1.0 - float(alpha)) * ident + float(alpha) * eff
+
+
+def simplex_grid(h2: int, w2: int, seed: int) -> np.ndarray:
+    """float64 ``[h2,w2]`` in [0, 1]: 2-D simplex noise (Gustavson's formulation: skew ``F2 = (sqrt 3 - 1) / 2``, unskew
+    ``G2 = (3 - sqrt 3) / 6``, three corners with ``max(0, 0.5 - x^2 - y^2)^4 (g . (x, y))``, times 70) at the integer points
+    ``(x, y) = (column + ox, row + oy)``, where the offsets ``ox, oy = 1 + (word & 0xFFF)`` come from the first Philox words for the
+    counters 0xFFFFFFFF and 0xFFFFFFFE (the noise is exactly 0 at the origin; away from it no mask value is exactly 1/2, so
+    no blend sits exactly on a rounding boundary); the gradient of the simplex lattice point ``(i, j)`` is one of eight directions (``_GRAD``), index = the
+    low three bits of the first Philox word for counter ``(i & 0xFFFF) << 16 | (j & 0xFFFF)`` under ``seed``; the value is
+    ``clip((n + 1) / 2, 0, 1)``.  ``simplex_grid_scalar`` is the same in plain Python floats."""
+    ox, oy = (1.0 + float(int(v) & 0xFFF) for v in philox_word0(seed, np.array([0xFFFFFFFF, 0xFFFFFFFE], dtype=np.uint32)))
+    y, x = np.meshgrid(np.arange(h2, dtype=np.float64) + oy, np.arange(w2, dtype=np.float64) + ox, indexing="ij")
+    s = (x + y) * _F2
+    i, j = np.floor(x + s), np.floor(y + s)
+    t = (i + j) * _G2
+    x0, y0 = x - (i - t), y - (j - t)
+    i1 = (x0 > y0).astype(np.float64)
+    j1 = 1.0 - i1
+    grad = np.array(_GRAD, dtype=np.float64)
+    total = np.zeros((h2, w2), dtype=np.float64)
+    for di, dj, xk, yk in ((0.0, 0.0, x0, y0), (i1, j1, x0 - i1 + _G2, y0 - j1 + _G2),
+                           (1.0, 1.0, x0 - 1.0 + 2.0 * _G2, y0 - 1.0 + 2.0 * _G2)):
+        ii, jj = (i + di).astype(np.int64), (j + dj).astype(np.int64)
+        g = grad[philox_word0(seed, ((ii & 0xFFFF) << 16) | (jj & 0xFFFF)) & np.uint32(7)]
+        tt = 0.5 - xk * xk - yk * yk
+        t2 = tt * tt
+        total = total + np.where(tt < 0.0, 0.0, t2 * t2 * (g[..., 0] * xk + g[..., 1] * yk))
+    return np.clip((70.0 * total + 1.0) * 0.5, 0.0, 1.0)
+
+
+def simplex_grid_scalar(h2: int, w2: int, seed: int) -> np.ndarray:
+    out = np.zeros((h2, w2), dtype=np.float64)
+    ox = 1.0 + float(_philox_word0_scalar(int(seed), 0xFFFFFFFF) & 0xFFF)
+    oy = 1.0 + float(_philox_word0_scalar(int(seed), 0xFFFFFFFE) & 0xFFF)
+    for row in range(h2):
+        for col in range(w2):
+            x, y = float(col) + ox, float(row) + oy
+            s = (x + y) * _F2
+            i, j = math.floor(x + s), math.floor(y + s)
+            t = (i + j) * _G2
+            x0, y0 = x - (i - t), y - (j - t)
+            i1, j1 = (1, 0) if x0 > y0 else (0, 1)
+            total = 0.0
+            for di, dj, xk, yk in ((0, 0, x0, y0), (i1, j1, x0 - i1 + _G2, y0 - j1 + _G2),
+                                   (1, 1, x0 - 1.0 + 2.0 * _G2, y0 - 1.0 + 2.0 * _G2)):
+                gx, gy = _GRAD[_philox_word0_scalar(int(seed), (((i + di) & 0xFFFF) << 16) | ((j + dj) & 0xFFFF)) & 7]
+                tt = 0.5 - xk * xk - yk * yk
+                t2 = tt * tt
+                total = total + (0.0 if tt < 0.0 else t2 * t2 * (gx * xk + gy * yk))
+            out[row, col] = min(1.0, max(0.0, (70.0 * total + 1.0) * 0.5))
+    return out
+
+
+def superpixel_grid(n_segments: int, h: int, w: int):
+    """(gy, gx) for about ``n_segments`` square cells: ``gy = max(1, floor(sqrt(n h / w) + 0.5))``, ``gx = max(1, floor(n / gy +
+    0.5))``, at most one cell per pixel row / column, the larger side reduced until ``gy gx <= 256``"""
+    n = float(n_segments)
+    gy = min(h, max(1, int(math.floor(math.sqrt(n * h / w) + 0.5))))
+    gx = min(w, max(1, int(math.floor(n / gy + 0.5))))
+    while gy * gx > MAX_SEGMENTS:
+        if gy >= gx:
+            gy -= 1
+        else:
+            gx -= 1
+    return gy, gx
+
+
+@dataclass
+class StyleProgram:
+    """``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed``
+    uint64 ``[B,S]`` (numpy, on the host; the module docstring says what each opcode reads).  The ``set_*`` methods encode slot
+    ``s`` of sample ``i``."""
+    opcode: np.ndarray
+    iarg: np.ndarray
+    farg: np.ndarray
+    table: np.ndarray
+    seed: np.ndarray
+
+    @property
+    def batch(self) -> int:
+        return self.opcode.shape[0]
+
+    @property
+    def slots(self) -> int:
+        return self.opcode.shape[1]
+
+    @staticmethod
+    def identity(batch: int, slots: int = 1) -> "StyleProgram":
+        return StyleProgram(np.zeros((batch, slots), dtype=np.int32), np.zeros((batch, slots, IARGS), dtype=np.int32),
+                            np.zeros((batch, slots, FARGS), dtype=np.float64), np.zeros((batch, slots, TABLE), dtype=np.float64),
+                            np.zeros((batch, slots), dtype=np.uint64))
+
+    def is_identity(self) -> bool:
+        return not np.any(self.opcode != OP_NOP)
+
+    def _clear(self, i, s, op):
+        self.opcode[i, s] = op
+        self.iarg[i, s] = 0
+        self.farg[i, s] = 0.0
+        self.table[i, s] = 0.0
+        self.seed[i, s] = 0
+
+    def set_nop(self, i, s):
+        self._clear(i, s, OP_NOP)
+
+    def set_hue_saturation(self, i, s, dh, ds):
+        self._clear(i, s, OP_HUE_SATURATION)
+        self.iarg[i, s, 0], self.iarg[i, s, 1] = int(dh), int(ds)
+
+    def set_noise_alpha(self, i, s, weights3x3, grids, upscale=UPSCALE_BILINEAR, aggregation=AGG_MAX, sigmoid=True, thresh=0.0):
+        """``grids``: 1..3 arrays ``[h', w']`` (2..16 per side) of mask values in [0, 1] (``simplex_grid``)"""
+        grids = [np.asarray(g, dtype=np.float64) for g in grids]
+        if not 1 <= len(grids) <= MAX_GRIDS or any(g.ndim != 2 or g.size > GRID_VALUES for g in grids):
+            raise ValueError("set_noise_alpha: 1..3 grids of at most 16 x 16 values")
+        self._clear(i, s, OP_NOISE_ALPHA_CONV3X3)
+        self.iarg[i, s, :4] = (len(grids), int(upscale), int(aggregation), int(bool(sigmoid)))
+        for k, g in enumerate(grids):
+            self.iarg[i, s, 4 + 2 * k:6 + 2 * k] = g.shape
+            self.table[i, s, GRID_VALUES * k:GRID_VALUES * k + g.size] = g.reshape(-1)
+        self.farg[i, s, :9] = np.asarray(weights3x3, dtype=np.float64).reshape(9)
+        self.farg[i, s, 9] = thresh
+
+    def set_superpixels(self, i, s, gy, gx, p_replace, seed, iters=SUPERPIXELS_UPDATES, compactness=SUPERPIXELS_COMPACTNESS):
+        self._clear(i, s, OP_SUPERPIXELS)
+        self.iarg[i, s, :4] = (int(gy), int(gx), int(iters), int(math.floor(float(compactness) ** 2 + 0.5)))
+        self.farg[i, s, 0], self.farg[i, s, 1] = p_replace, compactness
+        self.seed[i, s] = seed
+
+    def validate(self, h: Optional[int] = None, w: Optional[int] = None, channels: Optional[int] = None) -> None:
+        """Raises ``ValueError`` (naming the field) for a program the kernels are not defined on: shapes and dtypes, more
+        than 8 slots, unknown opcodes, non-finite ``farg`` / ``table``; hue on C other than 3, dh outside [-180, 180] or ds
+        outside [-255, 255]; a grid count outside 1..3, a grid side outside 2..16, an unknown upscale or aggregation, a sigmoid
+        flag that is not 0 / 1, table values outside [0, 1], a threshold beyond +/-1000; gy or gx below 1 or above H / W,
+        ``gy gx > 256``, updates outside 0..10, M2 outside 0..2^20, p_replace outside [0, 1]."""
+        op, ia, fa, tb, sd = self.opcode, self.iarg, self.farg, self.table, self.seed
+        if getattr(op, "ndim", 0) != 2 or op.dtype != np.int32:
+            raise ValueError("StyleProgram.opcode must be int32 [B,S]")
+        b, s = op.shape
+        if s > MAX_SLOTS:
+            raise ValueError("StyleProgram: %d slots, at most %d" % (s, MAX_SLOTS))
+        for name, a, shape, dt in (("iarg", ia, (b, s, IARGS), np.int32), ("farg", fa, (b, s, FARGS), np.float64),
+                                   ("table", tb, (b, s, TABLE), np.float64), ("seed", sd, (b, s), np.uint64)):
+            if getattr(a, "shape", None) != shape or a.dtype != dt:
+                raise ValueError("StyleProgram.%s must be %s %r" % (name, np.dtype(dt).name, list(shape)))
+        if np.any((op < 0) | (op > OP_SUPERPIXELS)):
+            raise ValueError("StyleProgram.opcode: unknown opcode")
+        if channels is not None and not 1 <= channels <= 4:
+            raise ValueError("StyleProgram: 1..4 channels, got %d" % channels)
+        if not np.all(np.isfinite(fa)):
+            raise ValueError("StyleProgram.farg must be finite")
+        if not np.all(np.isfinite(tb)):
+            raise ValueError("StyleProgram.table must be finite")
+        i = ia[op == OP_HUE_SATURATION]
+        if len(i):
+            if channels is not None and channels != 3:
+                raise ValueError("StyleProgram: HUE_SATURATION takes 3 channels, got %d" % channels)
+            if np.any(np.abs(i[:, 0]) > 180):
+                raise ValueError("StyleProgram: HUE_SATURATION dh (iarg[0]) must be in [-180, 180]")
+            if np.any(np.abs(i[:, 1]) > 255):
+                raise ValueError("StyleProgram: HUE_SATURATION ds (iarg[1]) must be in [-255, 255]")
+        m = op == OP_NOISE_ALPHA_CONV3X3
+        i, f, t = ia[m], fa[m], tb[m]
+        if len(i):
+            if np.any((i[:, 0] < 1) | (i[:, 0] > MAX_GRIDS)):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 grid count (iarg[0]) must be in 1..3")
+            if np.any((i[:, 1] != UPSCALE_NEAREST) & (i[:, 1] != UPSCALE_BILINEAR)):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 upscale (iarg[1]) must be 0 (nearest) or 1 (bilinear)")
+            if np.any((i[:, 2] < AGG_MIN) | (i[:, 2] > AGG_MAX)):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 aggregation (iarg[2]) must be 0 (min), 1 (mean) or 2 (max)")
+            if np.any((i[:, 3] != 0) & (i[:, 3] != 1)):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 sigmoid (iarg[3]) must be 0 or 1")
+            live = np.repeat(np.arange(MAX_GRIDS)[None, :] < i[:, 0:1], 2, axis=1)
+            sides = i[:, 4:4 + 2 * MAX_GRIDS]
+            if np.any(((sides < 2) | (sides > 16)) & live):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 grid sides (iarg[4:10]) must be in 2..16")
+            if np.any((t < 0.0) | (t > 1.0)):
+                raise ValueError("StyleProgram.table: NOISE_ALPHA_CONV3X3 mask values must be in [0, 1]")
+            if np.any(np.abs(f[:, 9]) > 1000.0):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 sigmoid threshold (farg[9]) must be in [-1000, 1000]")
+        m = op == OP_SUPERPIXELS
+        i, f = ia[m], fa[m]
+        if len(i):
+            if np.any(i[:, 0] < 1) or np.any(i[:, 1] < 1) or (h is not None and np.any(i[:, 0] > h)) or \
+                    (w is not None and np.any(i[:, 1] > w)):
+                raise ValueError("StyleProgram: SUPERPIXELS gy, gx (iarg[0:2]) must be in 1..H, 1..W")
+            if np.any(i[:, 0].astype(np.int64) * i[:, 1] > MAX_SEGMENTS):
+                raise ValueError("StyleProgram: SUPERPIXELS gy gx must be at most %d" % MAX_SEGMENTS)
+            if np.any((i[:, 2] < 0) | (i[:, 2] > MAX_UPDATES)):
+                raise ValueError("StyleProgram: SUPERPIXELS updates (iarg[2]) must be in 0..%d" % MAX_UPDATES)
+            if np.any((i[:, 3] < 0) | (i[:, 3] > (1 << 20))):
+                raise ValueError("StyleProgram: SUPERPIXELS M2 (iarg[3], compactness squared) must be in 0..2^20")
+            if np.any((f[:, 0] < 0) | (f[:, 0] > 1)):
+                raise ValueError("StyleProgram: SUPERPIXELS p_replace (farg[0]) must be in [0, 1]")
+
+    def kernel_arrays(self, h: int, w: int, channels: Optional[int] = None):
+        """(opcode, iarg, farg, table, seed as int64 bits) as the kernel takes them: validated for ``h x w x channels``
+        images, with the replacement thresholds in ``iarg[4]``"""
+        self.validate(h, w, channels)
+        ia = self.iarg.copy()
+        for i, s in zip(*np.nonzero(self.opcode == OP_SUPERPIXELS)):
+            ia[i, s, 4] = np.array(threshold(self.farg[i, s, 0]), dtype=np.uint32).view(np.int32)      # (the bits)
+        return self.opcode, ia, self.farg, self.table, self.seed.view(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ sampling
+def draw_style(b: int, rng: np.random.Generator):
+    """the parameters of the three entries for every sample of a batch (the reference's ranges; the module constants say
+    what this build chose where imgaug leaves a default)"""
+    u = lambda lo_hi, *shape: rng.uniform(lo_hi[0], lo_hi[1], (b,) + shape)
+    return dict(
+        sp_p=u(SUPERPIXELS_P_REPLACE), sp_n=rng.integers(SUPERPIXELS_SEGMENTS[0], SUPERPIXELS_SEGMENTS[1] + 1, b),
+        sp_seed=rng.integers(0, 2 ** 64, b, dtype=np.uint64),
+        na_kind=rng.integers(0, 2, b), na_alpha=u(EDGE_ALPHA), na_dir=u(EDGE_DIRECTION),
+        na_iters=rng.integers(NOISE_ITERATIONS[0], NOISE_ITERATIONS[1] + 1, b),
+        na_size=rng.integers(NOISE_SIZE[0], NOISE_SIZE[1] + 1, (b, MAX_GRIDS, 2)),
+        na_up=rng.integers(0, 2, b), na_agg=rng.integers(0, 3, b), na_sig=rng.random(b) < NOISE_SIGMOID_P,
+        na_thresh=rng.standard_normal(b) * NOISE_THRESH_SIGMA, na_seed=rng.integers(0, 2 ** 64, (b, MAX_GRIDS), dtype=np.uint64),
+        hue=rng.integers(HUE_VALUE[0], HUE_VALUE[1] + 1, b))
+
+
+def encode_style(prog: StyleProgram, i: int, s: int, entry: int, d, h: int, w: int) -> None:
+    if entry == ENTRY_SUPERPIXELS:
+        gy, gx = superpixel_grid(int(d["sp_n"][i]), h, w)
+        prog.set_superpixels(i, s, gy, gx, d["sp_p"][i], d["sp_seed"][i])
+    elif entry == ENTRY_NOISE_ALPHA:
+        wts = edge_detect_weights(d["na_alpha"][i]) if d["na_kind"][i] == 0 else directed_edge_weights(d["na_alpha"][i], d["na_dir"][i])
+        grids = [simplex_grid(int(d["na_size"][i, k, 0]), int(d["na_size"][i, k, 1]), int(d["na_seed"][i, k]))
+                 for k in range(int(d["na_iters"][i]))]
+        prog.set_noise_alpha(i, s, wts, grids, int(d["na_up"][i]), int(d["na_agg"][i]), bool(d["na_sig"][i]), d["na_thresh"][i])
+    else:
+        v = int(d["hue"][i])
+        prog.set_hue_saturation(i, s, int(math.floor(v * 180.0 / 255.0 + 0.5)), v)
+
+
+def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> StyleProgram:
+    """Draw the three STYLE entries of one batch of a preset (``"heavy_full_device"`` or ``"mscmrseg_aug2_full_device"``) for
+    ``h x w`` images as one program of three slots, in the batch's order (the other entries of the recipe are skipped:
+    ``sample_heavy_plan`` interleaves all kinds): ``sometimes(0.5)`` Superpixels (p_replace U(0, 1), n_segments 20..200 ->
+    ``superpixel_grid``, 5 updates, compactness 10), SimplexNoiseAlpha (alpha U(0.5, 1), OneOf EdgeDetect | DirectedEdgeDetect
+    with direction U(0, 1); 1..3 grids of 2..16 cells per side, nearest | bilinear, min | mean | max, sigmoid with a threshold
+    from N(0, 5)) and AddToHueAndSaturation (v integer in -20..20: ds = v, dh = floor(v 180 / 255 + 0.5)), each only for the
+    samples whose ``SomeOf((0, 5))`` drew it."""
+    from . import geometric as Geo
+    spec = Geo._check_preset(preset)
+    entries, on = Geo._select(batch, spec, rng)
+    d = draw_style(batch, rng)
+    sty = [k for k, e in enumerate(entries) if e[0] == "s"]
+    if not sty:
+        raise ValueError("preset %r holds no stylize entry (have: %s, %s)" % (preset, HEAVY_FULL_PRESET, AUG2_FULL_PRESET))
+    prog = StyleProgram.identity(batch, len(sty))
+    for i in range(batch):
+        s = 0
+        for k in sty:
+            if on[i, k]:
+                encode_style(prog, i, s, entries[k][1], d, h, w)
+                s += 1
+    return prog
+
+
+def upload_style_program(program: StyleProgram, batch: int, h: int, w: int, channels: int, device: torch.device):
+    """Validate on the host, then move the kernel's arrays through pinned, non-blocking copies (no synchronisation)."""
+    if program.batch != batch:
+        raise ValueError("StyleProgram for %d samples, batch of %d" % (program.batch, batch))
+
+    def put(a):
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        if device.type == "cuda":
+            t = t.pin_memory()
+        return t.to(device, non_blocking=True)
+    return tuple(put(a) for a in program.kernel_arrays(h, w, channels))
+
+
+def stylize_aug(images: torch.Tensor, program: Optional[StyleProgram] = None) -> torch.Tensor:
+    """uint8 ``[B,H,W,C]`` images on the device -> the stylized uint8 images (a new tensor).  ``program`` is required: build
+    it with ``StyleProgram.set_*`` or draw it with ``sample_style_program(B, "heavy_full_device", rng, H, W)``."""
+    if program is None:
+        raise TypeError("stylize_aug: program is required (sample_style_program(batch, preset, rng, h, w)); there is no silent identity")
+    if images.dtype != torch.uint8 or images.dim() != 4:
+        raise TypeError("stylize_aug: uint8 [B,H,W,C] images")
+    b, h, w, c = images.shape
+    return K.stylize(images, *upload_style_program(program, b, h, w, c, images.device))
