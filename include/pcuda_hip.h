@@ -510,6 +510,26 @@ size_t pcuda_stylize_workspace_size(int b, int h, int w, int c);
 int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode, const int* iarg,
                   const double* farg, const double* table, const unsigned long long* seed, void* workspace,
                   size_t workspace_bytes, pcuda_stream_t s);
+/* device-side histogram matching: match_histograms(img, reference_img, multichannel=True) of the MM-WHS generator
+ * (data_generator_mmwhs.py:174-176, 236-237; train_mmwhs.py -mh) on images [b][h][w][c], c = 1..4, fp32 or uint8 (is_u8),
+ * against a template that is fixed for the run and arrives as tables in device memory: tvalues / tquantiles [c][tstride]
+ * (float64; per channel the template's sorted distinct values tv and tq = cumsum(counts) / M) and tlen[c] (1..tstride valid
+ * entries; clamped into that range on the device).  Per plane (b, c) of N = h w values and per value s:
+ *   cnt = #{s' in the plane : s' <= s} (-0.0 and +0.0 are one value), q = double(cnt) / double(N)
+ *   j = the last index with tq[j] <= q;  j < 0: tv[0];  j == len - 1: tv[len - 1];  tq[j] == q: tv[j];  otherwise
+ *   slope = (tv[j+1] - tv[j]) / (tq[j+1] - tq[j]), r = slope (q - tq[j]) + tv[j]
+ * every operation rounded separately in float64 (np.unique / np.cumsum / np.interp; the library is built with
+ * -ffp-contract=off).  fp32 images store float(r) (round to nearest even); uint8 images store uint8(trunc(r)) and want a
+ * uint8 template (r stays in [0, 255]; the host checks that, the device clips).  NaN in an image is unsupported (the
+ * reference's result is garbage there too); +-inf are ordinary values.  fp32: each plane's order-preserving 32-bit keys are
+ * sorted in the workspace (one workgroup per plane: LSD radix sort, 8-bit digits, four passes) and every value finds cnt by
+ * binary search; uint8: a 256-bin histogram and a 256-entry LUT per plane, no workspace.  Integer atomics only: the same
+ * bits from run to run.  Never allocates, never synchronises; `in` is never written and in == out is rejected; b h w == 0 is
+ * a no-op returning 0.  workspace: pcuda_match_hist_workspace_size bytes (8 per fp32 value; 0 for uint8), 16-byte aligned. */
+size_t pcuda_match_hist_workspace_size(int b, int h, int w, int c, int is_u8);
+int pcuda_match_hist(const void* in, void* out, int is_u8, int b, int h, int w, int c, const double* tvalues,
+                     const double* tquantiles, const int* tlen, int tstride, void* workspace, size_t workspace_bytes,
+                     pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

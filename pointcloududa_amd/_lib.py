@@ -131,6 +131,8 @@ _PROTOS = {
     "pcuda_geometric": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_stylize_workspace_size": (sz, [i32, i32, i32, i32]),
     "pcuda_stylize": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "pcuda_match_hist_workspace_size": (sz, [i32, i32, i32, i32, i32]),
+    "pcuda_match_hist": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
     "pcuda_argmax_labels": (i32, [vp, i32, i64, i64, i32, i32, i64, vp, vp]),
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
     "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),

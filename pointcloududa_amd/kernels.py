@@ -978,6 +978,32 @@ def stylize(images_u8, opcode, iarg, farg, table, seed, out=None):
     return out
 
 
+def match_hist(images, tvalues, tquantiles, tlen, out=None):
+    """Histogram matching of ``[B,H,W,C]`` fp32 or uint8 images against a template's tables (``pcuda_match_hist``): ``tvalues`` and
+    ``tquantiles`` float64 ``[C,T]`` (per channel the template's sorted distinct values and ``cumsum(counts) / M``), ``tlen`` int32
+    ``[C]`` valid entries, all on the device -> a new tensor of the images' dtype (the input is never written)."""
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("match_hist: fp32 or uint8 images, got %s" % (images.dtype,))
+    _req(images, images.dtype)
+    if images.dim() != 4:
+        raise TypeError("match_hist: [B,H,W,C] images")
+    images = images.contiguous()
+    b, h, w, c = images.shape
+    _req(tvalues, torch.float64); _req(tquantiles, torch.float64); _req(tlen, torch.int32)
+    if tvalues.dim() != 2 or tvalues.shape[0] != c or tvalues.shape[1] < 1 or tquantiles.shape != tvalues.shape or \
+            tuple(tlen.shape) != (c,):
+        raise ValueError("match_hist: the tables do not match the %d channels of the images" % c)
+    if out is None:
+        out = torch.empty_like(images)
+    is_u8 = int(images.dtype == torch.uint8)
+    nbytes = L.lib().pcuda_match_hist_workspace_size(b, h, w, c, is_u8)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device) if nbytes else None
+    check(L.lib().pcuda_match_hist(images.data_ptr(), out.data_ptr(), is_u8, b, h, w, c, tvalues.contiguous().data_ptr(),
+                                   tquantiles.contiguous().data_ptr(), tlen.contiguous().data_ptr(), int(tvalues.shape[1]),
+                                   _ptr(ws), nbytes, _stream()), "match_hist")
+    return out
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum."""
     if x.dtype not in (torch.float32, torch.uint8):

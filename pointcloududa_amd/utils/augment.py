@@ -28,7 +28,10 @@ pipeline (``CropAndPad``, the +/-45 degree ``Affine`` with every border mode, el
 images and the masks in front of the f6 launch.  ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
 ``AddToHueAndSaturation`` live in ``utils/stylize.py`` (f9) and are re-exported here as well: the presets
 ``"heavy_full_device"`` and ``"mscmrseg_aug2_full_device"`` hold all fifteen / twelve ``SomeOf`` entries of the two recipes, while
-``"heavy_device"`` and ``"mscmrseg_aug2_device"`` keep drawing what they drew without the three."""
+``"heavy_device"`` and ``"mscmrseg_aug2_device"`` keep drawing what they drew without the three.  Histogram matching against a
+fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
+``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
+in front of everything else."""
 from __future__ import annotations
 
 import math
@@ -46,6 +49,7 @@ from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, Hea
                         sample_geo_program, sample_heavy_plan, upload_geo_program)
 from .stylize import (AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, directed_edge_weights, edge_detect_weights,  # noqa: F401
                       sample_style_program, simplex_grid, stylize_aug, superpixel_grid, upload_style_program)
+from .histmatch import HistReference, match_histograms, reference_tables  # noqa: F401
 
 OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
 
@@ -205,7 +209,8 @@ def _labels(masks: torch.Tensor) -> torch.Tensor:
 def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optional[AugmentParams], num_classes: int = 5,
                   crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
                   firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True,
-                  photometric: Optional[PhotoProgram] = None, heavy: Optional[HeavyPlan] = None):
+                  photometric: Optional[PhotoProgram] = None, heavy: Optional[HeavyPlan] = None,
+                  match_hist: Optional[HistReference] = None):
     """``data_generator_mmwhs.py:245-274`` after the file reads (``rescale="minmax"``, fp32 images), or
     ``data_generator_mscmrseg.py:305-317`` (``rescale="div255"``, uint8 images), on the device: images ``[B,H,W,C]``,
     integer masks ``[B,H,W]`` (or ``[B,H,W,1]``) ->
@@ -228,7 +233,14 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
 
     ``heavy``: a ``HeavyPlan`` (``sample_heavy_plan``: the reference's default ``augmentation``, ``data_generator_mscmrseg.py:20-84``)
     run on the uint8 images AND the masks in front of everything else (``heavy_aug``); with ``resample_verts`` the point
-    cloud is drawn from the full-size warped mask, as without a plan.  fp32 images with a plan raise ``TypeError``."""
+    cloud is drawn from the full-size warped mask, as without a plan.  fp32 images with a plan raise ``TypeError``.
+
+    ``match_hist``: a ``HistReference``; the raw images (fp32 or uint8) are histogram-matched against it before anything else
+    (``match_histograms``: ``data_generator_mmwhs.py:236-237``, the generator's ``-mh``), so the batch min / max of
+    ``rescale="minmax"`` are those of the matched images and a heavy plan or a photometric program sees the matched uint8
+    images; masks and vertices are untouched.  ``params=None, rescale=None`` is then the generator's ``aug=''`` branch."""
+    if match_hist is not None:
+        images_hwc = match_histograms(images_hwc, match_hist)
     if heavy is not None:
         if rescale == "minmax" or images_hwc.dtype != torch.uint8:
             raise TypeError("augment_batch: a heavy plan takes uint8 images (rescale='div255' or None)")
@@ -307,11 +319,14 @@ class AugmentedBatches:
     non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
     uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"`` or their ``_full_`` twins) ``preset`` must
-    be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters."""
+    be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters.  With
+    ``match_hist_reference`` (an ``[H,W,C]`` numpy image) its tables are built and uploaded once (``match_hist``) and every batch
+    is histogram-matched against it first."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
-                 photometric_preset: Optional[str] = None, heavy_preset: Optional[str] = None):
+                 photometric_preset: Optional[str] = None, heavy_preset: Optional[str] = None,
+                 match_hist_reference: Optional[np.ndarray] = None):
         if preset == "heavy" or photometric_preset == "heavy" or heavy_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
         if heavy_preset is not None:
@@ -332,6 +347,7 @@ class AugmentedBatches:
         self.preset, self.rng = preset, rng
         self.num_classes, self.crop_size, self.rescale, self.resample_verts = num_classes, crop_size, rescale, resample_verts
         self.photometric_preset, self.heavy_preset = photometric_preset, heavy_preset
+        self.match_hist = None if match_hist_reference is None else HistReference(match_hist_reference, device)
         self.last_plan: Optional[HeavyPlan] = None
         self.last_params: Optional[AugmentParams] = None
         self.last_program: Optional[PhotoProgram] = None
@@ -347,9 +363,11 @@ class AugmentedBatches:
             self.last_params = AugmentParams.identity(images.shape[0])
             self.last_plan = sample_heavy_plan(images.shape[0], self.heavy_preset, self.rng, images.shape[1], images.shape[2])
             return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
-                                 resample_verts=self.resample_verts, verts=verts, heavy=self.last_plan)
+                                 resample_verts=self.resample_verts, verts=verts, heavy=self.last_plan,
+                                 match_hist=self.match_hist)
         self.last_params = sample_params(images.shape[0], self.preset, self.rng)
         if self.photometric_preset is not None:
             self.last_program = sample_program(images.shape[0], self.photometric_preset, self.rng)
         return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
-                             resample_verts=self.resample_verts, verts=verts, photometric=self.last_program)
+                             resample_verts=self.resample_verts, verts=verts, photometric=self.last_program,
+                             match_hist=self.match_hist)
