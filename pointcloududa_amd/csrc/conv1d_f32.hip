@@ -15,6 +15,7 @@
 // conv_wgrad.hip, deterministic).
 #include "common.h"
 #include "conv_host.h"
+#include "variants.h"
 
 namespace {
 
@@ -341,11 +342,11 @@ extern "C" int pcuda_conv1d_k1_fwd(const float* x, const float* w, const float* 
   const bool vec = vec_ok(x, w, y, cin, cout, l, cin);
   const dim3 g2(cdiv(p.ncols, BN), cdiv(cout, 128)), g1(cdiv(p.ncols, BN), cdiv(cout, 64));
   if (cout > 64 && (long long)g2.x * g2.y >= 512) {
-    if (vec) hipLaunchKernelGGL((c1d_gemm_kernel<2, false, true>), g2, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((c1d_gemm_kernel<2, false, false>), g2, dim3(256), 0, s, p);
+    if (vec) { note_kernel("c1d_gemm mb2 ta0 vec1"); hipLaunchKernelGGL((c1d_gemm_kernel<2, false, true>), g2, dim3(256), 0, s, p); }
+    else { note_kernel("c1d_gemm mb2 ta0 vec0"); hipLaunchKernelGGL((c1d_gemm_kernel<2, false, false>), g2, dim3(256), 0, s, p); }
   } else {
-    if (vec) hipLaunchKernelGGL((c1d_gemm_kernel<1, false, true>), g1, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((c1d_gemm_kernel<1, false, false>), g1, dim3(256), 0, s, p);
+    if (vec) { note_kernel("c1d_gemm mb1 ta0 vec1"); hipLaunchKernelGGL((c1d_gemm_kernel<1, false, true>), g1, dim3(256), 0, s, p); }
+    else { note_kernel("c1d_gemm mb1 ta0 vec0"); hipLaunchKernelGGL((c1d_gemm_kernel<1, false, false>), g1, dim3(256), 0, s, p); }
   }
   PCUDA_CHECK_LAUNCH("c1d_gemm_kernel(fwd)");
   return PCUDA_OK;
@@ -363,11 +364,11 @@ extern "C" int pcuda_conv1d_k1_dgrad(const float* dy, const float* w, float* dx,
   const dim3 g2(cdiv(p.ncols, BN), cdiv(cin, 128)), g1(cdiv(p.ncols, BN), cdiv(cin, 64));
   // (128-row tiles only where they still fill the chip twice: 1024 -> 128 channels on 9600 points is 150 of them)
   if (cin > 64 && (long long)g2.x * g2.y >= 512) {
-    if (vec) hipLaunchKernelGGL((c1d_gemm_kernel<2, true, true>), g2, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((c1d_gemm_kernel<2, true, false>), g2, dim3(256), 0, s, p);
+    if (vec) { note_kernel("c1d_gemm mb2 ta1 vec1"); hipLaunchKernelGGL((c1d_gemm_kernel<2, true, true>), g2, dim3(256), 0, s, p); }
+    else { note_kernel("c1d_gemm mb2 ta1 vec0"); hipLaunchKernelGGL((c1d_gemm_kernel<2, true, false>), g2, dim3(256), 0, s, p); }
   } else {
-    if (vec) hipLaunchKernelGGL((c1d_gemm_kernel<1, true, true>), g1, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((c1d_gemm_kernel<1, true, false>), g1, dim3(256), 0, s, p);
+    if (vec) { note_kernel("c1d_gemm mb1 ta1 vec1"); hipLaunchKernelGGL((c1d_gemm_kernel<1, true, true>), g1, dim3(256), 0, s, p); }
+    else { note_kernel("c1d_gemm mb1 ta1 vec0"); hipLaunchKernelGGL((c1d_gemm_kernel<1, true, false>), g1, dim3(256), 0, s, p); }
   }
   PCUDA_CHECK_LAUNCH("c1d_gemm_kernel(dgrad)");
   return PCUDA_OK;
@@ -397,6 +398,7 @@ extern "C" int pcuda_conv1d_k1_wgrad(const float* x, const float* dy, float* dw,
     snprintf(tag, sizeof(tag), "conv1d f32 wgrad n%d cin%d cout%d l%d ksplit%d", b, cin, cout, l, ks);
     ProfScope prof(PCUDA_FAM_DENSE_F32, 2.0 * b * l * (double)cin * cout, s, tag);
     const dim3 grid(cdiv(cin, BN), cdiv(cout, 64 * mb), ks);
+    note_kernel(mb == 2 ? "c1d_wgrad mb2" : "c1d_wgrad mb1");
     if (mb == 2) hipLaunchKernelGGL((c1d_wgrad_kernel<2>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((c1d_wgrad_kernel<1>), grid, dim3(256), 0, s, p);
     PCUDA_CHECK_LAUNCH("c1d_wgrad_kernel");

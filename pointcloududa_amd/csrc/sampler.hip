@@ -177,12 +177,18 @@ extern "C" int pcuda_fps(const double* pts, const int* counts, const int* first,
                          pcuda_stream_t s) {
   if (!pts || !counts || !first || !idx || b <= 0 || npts_max <= 0 || k <= 0)
     PCUDA_FAIL(PCUDA_E_BADARG, "fps: bad arguments");
+  // the most dynamic LDS a launch asks for: 150 KB + the kernel's 52 static bytes fit the CU's 160 KB
+  constexpr size_t LDS_MAX = 150 * 1024;
   const size_t lds = (size_t)npts_max * sizeof(double);
-  if (lds > 150 * 1024) PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "fps: at most %d points per cloud", (int)(150 * 1024 / 8));
+  if (lds > LDS_MAX) PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "fps: at most %d points per cloud", (int)(LDS_MAX / 8));
   static DeviceOnce lds_opt;
   if (const unsigned long long devbit = lds > 32 * 1024 ? lds_opt.pending() : 0ull) {
-    if (hipFuncSetAttribute((const void*)fps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    // (the runtime refuses a request that, with the static LDS, exceeds the CU's: asking for all 160 KB failed here, and
+    // the error it left behind surfaced in the next launch check of the process)
+    if (hipFuncSetAttribute((const void*)fps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
+      (void)hipGetLastError();
       PCUDA_FAIL(PCUDA_E_LAUNCH, "fps: cannot raise dynamic LDS");
+    }
     lds_opt.mark(devbit);
   }
   hipLaunchKernelGGL(fps_kernel, dim3(b), dim3(256), lds, (hipStream_t)s, pts, counts, first, npts_max, k, idx);

@@ -1,7 +1,7 @@
-"""Plain float64 statements of the memory-bound operations (BatchNorm, pooling, dense, optimisers, losses), written from
-the formulas: what the *_edges_gpu tests compare the HIP kernels with.  Inputs are the kernels' float32 tensors (and the
-float32 values of their scalar arguments) cast up; nothing here calls a kernel.  tests/test_fp64_refs.py checks every
-function against torch autograd / torch.optim in float64 on the CPU."""
+"""Plain float64 statements of the memory-bound operations (BatchNorm, pooling, dense, optimisers, losses) and of the k = 1
+Conv1d, written from the formulas: what the *_edges_gpu tests compare the HIP kernels with.  Inputs are the kernels'
+float32 tensors (and the float32 values of their scalar arguments) cast up; nothing here calls a kernel.
+tests/test_fp64_refs.py checks every function against torch autograd / torch.optim in float64 on the CPU."""
 import math
 
 import numpy as np
@@ -171,6 +171,22 @@ def linear_backward(dy, x, w):
 def bmm(a, b, ta=False, tb=False):
     a, b = up(a), up(b)
     return torch.matmul(a.transpose(1, 2) if ta else a, b.transpose(1, 2) if tb else b)
+
+
+def conv1d_k1(x, w, b=None):
+    """torch.nn.Conv1d(cin, cout, 1) on [B,cin,L]: (y, sum of y, sum of y^2), the sums per output channel over batch and
+    points (what the BatchNorm partials of the kernel's epilogue add up to)"""
+    y = torch.matmul(up(w), up(x))                                 # [cout,cin] x [B,cin,L] -> [B,cout,L]
+    if b is not None:
+        y = y + up(b)[None, :, None]
+    return y, y.sum((0, 2)), (y * y).sum((0, 2))
+
+
+def conv1d_k1_backward(dy, x, w):
+    """(dx, dw, db) of y[b,o,l] = sum_c w[o,c] x[b,c,l] + bias[o]"""
+    dy, x, w = up(dy), up(x), up(w)
+    flat = lambda t: t.transpose(0, 1).reshape(t.shape[1], -1)    # [B,C,L] -> [C, B*L]
+    return torch.matmul(w.t(), dy), flat(dy) @ flat(x).t(), dy.sum((0, 2))
 
 
 def max_points(x):

@@ -127,6 +127,31 @@ def test_linear_bmm_max_points(m, k, n):
     assert torch.equal(h.double().gather(2, i[..., None])[..., 0], v)
 
 
+@pytest.mark.parametrize("b,cin,cout,l", [(1, 1, 1, 1), (3, 5, 7, 11), (2, 33, 4, 65)])
+@pytest.mark.parametrize("bias", [False, True])
+def test_conv1d_k1(b, cin, cout, l, bias):
+    rng = np.random.default_rng(8)
+    x, w, bv, g = _r(rng, b, cin, l), _r(rng, cout, cin), (_r(rng, cout) if bias else None), _r(rng, b, cout, l)
+    xr, wr = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    br = bv.double().requires_grad_(True) if bias else None
+    y_ref = F.conv1d(xr, wr[:, :, None], br)
+    y_ref.backward(g.double())
+    y, s1, s2 = R.conv1d_k1(x, w, bv)
+    assert y.shape == (b, cout, l) and rel_err(y, y_ref) < TOL
+    yd = y_ref.detach()
+    assert rel_err(s1, yd.sum((0, 2))) < TOL and rel_err(s2, (yd ** 2).sum((0, 2))) < TOL
+    # the same sums as BatchNorm1d's batch statistics see them: mean = s1 / n, biased variance = s2 / n - mean^2
+    n = b * l
+    assert rel_err(s1 / n, yd.mean((0, 2))) < TOL
+    assert float((s2 / n - (s1 / n) ** 2 - yd.var((0, 2), unbiased=False)).abs().max()) < TOL * max(1.0, float(s2.max() / n))
+    dx, dw, db = R.conv1d_k1_backward(g, x, w)
+    assert rel_err(dx, xr.grad) < TOL and rel_err(dw, wr.grad) < TOL
+    if bias:
+        assert rel_err(db, br.grad) < TOL
+    else:
+        assert rel_err(db, g.double().sum((0, 2))) < TOL
+
+
 @pytest.mark.parametrize("numel", [1, 257])
 @pytest.mark.parametrize("wd", [0.0, 0.01])
 def test_optimisers(numel, wd):
