@@ -186,8 +186,17 @@ class ConvOp:
             nt = lib.pcuda_conv2d_fwd_tiles(C.byref(g), _precision)
             partials = torch.empty((nt, self.cout, 2), dtype=torch.float32, device=w.device)
         src, dst = make_src(xa, x2), make_dst(out)
-        check(lib.pcuda_conv2d_forward(C.byref(g), _precision, C.byref(src), pk.data_ptr(), _ptr(b), float(slope),
-                                       C.byref(dst), _ptr(partials), _stream()), "conv2d_forward")
+        rc = lib.pcuda_conv2d_forward(C.byref(g), _precision, C.byref(src), pk.data_ptr(), _ptr(b), float(slope),
+                                      C.byref(dst), _ptr(partials), _stream())
+        if rc == L.PCUDA_E_UNSUPPORTED and want_stats:
+            # the partial sums are sized by the tiles of the kernel the GEOMETRY selects (pcuda_conv2d_fwd_tiles); a view that
+            # kernel cannot address (off its alignment, split) runs on one with other tiles: the convolution without
+            # statistics, then the statistics of what it stored as their own kernel
+            check(lib.pcuda_conv2d_forward(C.byref(g), _precision, C.byref(src), pk.data_ptr(), _ptr(b), float(slope),
+                                           C.byref(dst), None, _stream()), "conv2d_forward")
+            partials, nt, _ = bn_stats(out)
+            return out, partials, nt
+        check(rc, "conv2d_forward")
         return out, partials, nt
 
     def dgrad(self, dy, w, in_h, in_w, dx=None, dx2=None, accumulate=False, bnred=None):

@@ -48,6 +48,7 @@ import torch
 
 import fp64_refs as R
 from conftest import rel_err
+from layout_helpers import place_view as _place
 
 pytestmark = pytest.mark.gpu
 
@@ -72,25 +73,6 @@ def _params(rng, c):
 
 def _prefill(c, lo=0.5):
     return torch.tensor([(lo + 0.25 * i) * (-1) ** i for i in range(c)], dtype=torch.float32)
-
-
-def _place(t, dev, layout="dense"):
-    """``t`` on the device in a given memory layout; what surrounds it is NaN, so a read outside it shows"""
-    if layout == "dense":
-        return t.to(dev)
-    if layout == "slice":                      # big[:, 1:c+1]
-        big = torch.full((t.shape[0], t.shape[1] + 2) + tuple(t.shape[2:]), float("nan"), device=dev)
-        v = big[:, 1:t.shape[1] + 1]
-    elif layout == "pad":                      # plane stride hw + 1
-        assert t.dim() == 3
-        big = torch.full((t.shape[0], t.shape[1] + 2, t.shape[2] + 1), float("nan"), device=dev)
-        v = big[:, 1:t.shape[1] + 1, :t.shape[2]]
-    elif layout == "off4":                     # base pointer 4 bytes past 16-byte alignment
-        big = torch.full((t.numel() + 1,), float("nan"), device=dev)
-        v = big[1:].view(t.shape)
-        assert v.data_ptr() % 16 == 4
-    v.copy_(t.to(dev))
-    return v
 
 
 @functools.lru_cache(maxsize=None)
