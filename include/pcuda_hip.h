@@ -589,6 +589,30 @@ int pcuda_conv1d_k1_wgrad(const float* x, const float* dy, float* dw, float* db,
 /* max over the last axis of x[b][c][l] with argmax (PointNetCls.py:44,162) */
 int pcuda_max_points_fwd(const float* x, int b, int c, int l, float* y, int* idx, pcuda_stream_t s);
 int pcuda_max_points_bwd(const float* dy, const int* idx, int b, int c, int l, float* dx, pcuda_stream_t s);
+/* Small-tensor forms of the point-cloud discriminator (csrc/pointnet_small.hip).  Each computes, bit for bit, what the
+ * general entry points named with it compute: same association of every sum, another mapping to threads.
+ * bn1d_fwd: training BatchNorm1d on a[b][c] (rows a_sn floats apart, channels contiguous; count = b) in one launch =
+ *   pcuda_bn_stats + pcuda_bn_finalize + pcuda_bn_apply (flags = relu ? PCUDA_BN_APPLY_RELU : 0).
+ * bn1d_bwd: = pcuda_bn_bwd_reduce + pcuda_bn_bwd_finalize(count = b) + pcuda_bn_bwd_apply with one gradient source.
+ *   Both return PCUDA_E_UNSUPPORTED for b > 1024; a second gradient share (dy2) and frozen statistics (count < 0) have
+ *   no fused form: use the three calls. */
+int pcuda_bn1d_fwd(const float* a, long long a_sn, int b, int c, const float* gamma, const float* beta, float eps,
+                   float momentum, float* running_mean, float* running_var, float* mean, float* invstd, float* scale,
+                   float* shift, int relu, float* y, long long y_sn, pcuda_stream_t s);
+int pcuda_bn1d_bwd(const float* dy, long long dy_sn, const float* a, long long a_sn, int b, int c, const float* gamma,
+                   const float* mean, const float* invstd, const float* scale, const float* shift, int post_relu,
+                   float act_slope, float* dgamma, float* dbeta, int accumulate, float* dz, long long dz_sn,
+                   pcuda_stream_t s);
+/* The two passes of the BatchNorm backward whose incoming gradient is pcuda_max_points_bwd(g, idx), without that dense
+ * [b][c][l] tensor: g, idx dense [b][c]; a, dz dense [b][c][l]; l <= 2048 (PCUDA_E_UNSUPPORTED above).
+ * reduce_maxpts writes red[b][c][2] = what pcuda_bn_bwd_reduce writes for the dense gradient (ntiles = b), the input of
+ * pcuda_bn_bwd_finalize; apply_maxpts = pcuda_bn_bwd_apply on the dense gradient. */
+int pcuda_bn_bwd_reduce_maxpts(const float* g, const int* idx, const float* a, const float* mean, const float* invstd,
+                               const float* scale, const float* shift, int post_relu, int b, int c, int l, float* red,
+                               pcuda_stream_t s);
+int pcuda_bn_bwd_apply_maxpts(const float* g, const int* idx, const float* a, const float* coef, const float* scale,
+                              const float* shift, int post_relu, float act_slope, float* dz, int b, int c, int l,
+                              pcuda_stream_t s);
 /* batched small matmul C[b] = op(A[b]) . op(B[b]); A [m][k] (or [k][m] when ta), B [k][n] (or [n][k] when tb) */
 int pcuda_bmm(const float* a, const float* bmat, float* c, int batch, int m, int k, int n, int ta, int tb,
               int accumulate, pcuda_stream_t s);

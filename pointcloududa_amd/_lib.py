@@ -150,6 +150,10 @@ _PROTOS = {
     "pcuda_conv1d_k1_wgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
     "pcuda_max_points_fwd": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "pcuda_max_points_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "pcuda_bn1d_fwd": (i32, [vp, i64, i32, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]),
+    "pcuda_bn1d_bwd": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, f32, vp, vp, i32, vp, i64, vp]),
+    "pcuda_bn_bwd_reduce_maxpts": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "pcuda_bn_bwd_apply_maxpts": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, vp]),
     "pcuda_bmm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "pcuda_surface_vertices": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
     "pcuda_surface_vertices_mc": (i32, [vp, i32, i32, i32, vp, i32, vp, vp]),

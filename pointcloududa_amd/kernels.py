@@ -445,11 +445,51 @@ def bn_apply(a: torch.Tensor, st: BNState, relu=False, out=None, fma=False):
     return out
 
 
+# PCUDA_PN_SMALL=0: the point-cloud discriminator's small tensors take the general kernels (one element per workgroup on
+# [B, C], the dense gradient behind the max over points) instead of csrc/pointnet_small.hip -- same bits, the A/B switch
+_pn_small = os.environ.get("PCUDA_PN_SMALL", "1") != "0"
+
+
+def _bn1d_ok(*ts):
+    """[B, C] tensors the one-launch BatchNorm1d kernels take: B <= 1024, channels contiguous"""
+    return _pn_small and all(t.dim() == 2 and t.shape[0] <= 1024 and t.stride(1) == 1 and t.shape[1] <= t.stride(0) <= 1 << 20
+                             for t in ts)
+
+
+def bn1d_forward(a, gamma, beta, running_mean, running_var, relu=False, eps=1e-5, momentum=0.1):
+    """training BatchNorm1d on [B, C]: (BNState, y) of bn_stats -> bn_finalize -> bn_apply in one launch, or None where
+    the fused kernel does not apply (B > 1024, strided channels, PCUDA_PN_SMALL=0)"""
+    _req(a)
+    if not _bn1d_ok(a):
+        return None
+    b, c = a.shape
+    st = BNState()
+    buf = torch.empty((4, c), dtype=torch.float32, device=a.device)
+    st.mean, st.invstd, st.scale, st.shift, st.count = buf[0], buf[1], buf[2], buf[3], b
+    y = torch.empty((b, c), dtype=torch.float32, device=a.device)
+    check(L.lib().pcuda_bn1d_fwd(a.data_ptr(), a.stride(0), b, c, _ptr(gamma), _ptr(beta), eps, momentum,
+                                 _ptr(running_mean), _ptr(running_var), st.mean.data_ptr(), st.invstd.data_ptr(),
+                                 st.scale.data_ptr(), st.shift.data_ptr(), 1 if relu else 0, y.data_ptr(), y.stride(0),
+                                 _stream()), "bn1d_fwd")
+    return st, y
+
+
 def bn_backward(dy, a, st: BNState, gamma, dgamma, dbeta, dy2=None, post_relu=False, act_slope=1.0,
                 accumulate=True, red=None, frozen=False):
     """Backward of [a = lrelu(z, act_slope)] -> BN (post_relu=False) or a -> BN -> ReLU (post_relu=True).
     Returns dz (gradient w.r.t. the pre-activation conv output, or w.r.t. a when post_relu).
     ``frozen``: ``st`` holds the running statistics (eval-mode BatchNorm): the layer is a fixed affine."""
+    if dy2 is None and red is None and not frozen and _bn1d_ok(a, dy):
+        # [B, C]: reduce, finalize and apply in one launch (a second share, partials from a dgrad epilogue and frozen
+        # statistics have no fused form)
+        _req(a); _req(dy)
+        b, c = a.shape
+        dz = torch.empty((b, c), dtype=torch.float32, device=a.device)
+        check(L.lib().pcuda_bn1d_bwd(dy.data_ptr(), dy.stride(0), a.data_ptr(), a.stride(0), b, c, _ptr(gamma),
+                                     st.mean.data_ptr(), st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
+                                     1 if post_relu else 0, float(act_slope), _ptr(dgamma), _ptr(dbeta),
+                                     1 if accumulate else 0, dz.data_ptr(), dz.stride(0), _stream()), "bn1d_bwd")
+        return dz
     n, c, hw, asn, asc = _planes(a)
     _, _, _, dsn, dsc = _planes(dy)
     d2p, d2sn, d2sc = None, 0, 0
@@ -1192,6 +1232,34 @@ def max_points_bwd(dy, idx, l):
     dx = torch.empty((b, c, l), dtype=torch.float32, device=dy.device)
     check(L.lib().pcuda_max_points_bwd(dy.data_ptr(), idx.data_ptr(), b, c, l, dx.data_ptr(), _stream()), "max_points_bwd")
     return dx
+
+
+def bn_backward_maxpts(g, idx, a, st: BNState, gamma, dgamma, dbeta, post_relu=False, act_slope=1.0, accumulate=True,
+                       frozen=False):
+    """bn_backward(max_points_bwd(g, idx, L), a, ...) without the dense [B, C, L] gradient: (g, idx) are read in place.
+    L <= 2048 (one tile of the general reduce per row); above that, and under PCUDA_PN_SMALL=0, the dense path."""
+    _req(a); _req(g)
+    b, c, l = a.shape
+    if not (_pn_small and l <= 2048 and a.is_contiguous()):
+        return bn_backward(max_points_bwd(g.contiguous(), idx, l), a, st, gamma, dgamma, dbeta, post_relu=post_relu,
+                           act_slope=act_slope, accumulate=accumulate, frozen=frozen)
+    g = g.contiguous()
+    assert idx.is_contiguous() and idx.dtype == torch.int32 and g.shape == idx.shape == (b, c)
+    lib = L.lib()
+    pr = 1 if post_relu else 0
+    red = torch.empty((b, c, 2), dtype=torch.float32, device=a.device)
+    check(lib.pcuda_bn_bwd_reduce_maxpts(g.data_ptr(), idx.data_ptr(), a.data_ptr(), st.mean.data_ptr(),
+                                         st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), pr, b, c, l,
+                                         red.data_ptr(), _stream()), "bn_bwd_reduce_maxpts")
+    coef = torch.empty((c, 3), dtype=torch.float32, device=a.device)
+    check(lib.pcuda_bn_bwd_finalize(red.data_ptr(), b, c, -(b * l) if frozen else b * l, _ptr(gamma), st.invstd.data_ptr(),
+                                    st.mean.data_ptr(), _ptr(dgamma), _ptr(dbeta), 1 if accumulate else 0,
+                                    coef.data_ptr(), _stream()), "bn_bwd_finalize")
+    dz = torch.empty((b, c, l), dtype=torch.float32, device=a.device)
+    check(lib.pcuda_bn_bwd_apply_maxpts(g.data_ptr(), idx.data_ptr(), a.data_ptr(), coef.data_ptr(), st.scale.data_ptr(),
+                                        st.shift.data_ptr(), pr, float(act_slope), dz.data_ptr(), b, c, l, _stream()),
+          "bn_bwd_apply_maxpts")
+    return dz
 
 
 def bmm(a, b, ta=False, tb=False):

@@ -36,12 +36,16 @@ def _identity(k, device):
 
 
 class _Var:
-    __slots__ = ("t", "g")
+    # sp: the gradient as (g [B,C], idx [B,C]) of a max over points, not yet scattered to [B,C,L] (``sp_ok``: this value is
+    # a BatchNorm output, whose backward reads that pair in place)
+    __slots__ = ("t", "g", "sp", "sp_ok")
 
     def __init__(self, t):
-        self.t, self.g = t, None
+        self.t, self.g, self.sp, self.sp_ok = t, None, None, False
 
     def acc(self, g):
+        if self.sp is not None:      # a second consumer after all: the dense gradient, summed in the order it always was
+            self.g, self.sp = K.max_points_bwd(self.sp[0], self.sp[1], self.t.shape[2]), None
         self.g = g if self.g is None else K.add_n([self.g, g])
 
 
@@ -104,20 +108,37 @@ class _Tape:
             if cnt == 1:      # a standalone STNkd / PointNetfeat at batch size 1: torch's BatchNorm raises here too
                 raise RuntimeError("Expected more than 1 value per channel when training, got input size %s (%s)"
                                    % (tuple(a.t.shape), bn))
+            fused = None
             if part is None:
-                part, nt, cnt = K.bn_stats(a.t)
-            st = K.bn_finalize(part, nt, cnt, P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
-                               P[bn + ".running_var"])
+                if a.t.dim() == 2:      # [B, C]: statistics, finalize and apply in one launch
+                    fused = K.bn1d_forward(a.t, P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
+                                           P[bn + ".running_var"], relu=relu)
+                if fused is None:
+                    part, nt, cnt = K.bn_stats(a.t)
+            if fused is None:
+                st = K.bn_finalize(part, nt, cnt, P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"],
+                                   P[bn + ".running_var"])
         else:
+            fused = None
             st = K.BNState()
             inv = torch.rsqrt(P[bn + ".running_var"] + 1e-5)
             st.mean, st.invstd, st.count = P[bn + ".running_mean"], inv, cnt
             st.scale = (P[bn + ".weight"] * inv).contiguous()
             st.shift = (P[bn + ".bias"] - P[bn + ".running_mean"] * st.scale).contiguous()
-        y = _Var(K.bn_apply(a.t, st, relu=relu))
+        if fused is not None:
+            st, yt = fused
+        else:
+            yt = K.bn_apply(a.t, st, relu=relu)
+        y = _Var(yt)
+        y.sp_ok = yt.dim() == 3
         self._rec(bn, y.t, relu)
 
         def bwd():
+            if y.sp is not None:      # the only consumer was a max over points: its (g, idx) read in place
+                (g, idx), y.sp = y.sp, None
+                a.acc(K.bn_backward_maxpts(g, idx, a.t, st, P[bn + ".weight"], self.G(bn + ".weight"), self.G(bn + ".bias"),
+                                           post_relu=relu, act_slope=1.0, frozen=not self.training))
+                return
             if y.g is None:
                 return
             a.acc(K.bn_backward(y.g, a.t, st, P[bn + ".weight"], self.G(bn + ".weight"), self.G(bn + ".bias"),
@@ -162,7 +183,11 @@ class _Tape:
         l = x.t.shape[2]
 
         def bwd():
-            if y.g is not None:
+            if y.g is None:
+                return
+            if x.sp_ok and x.g is None and x.sp is None and K._pn_small and l <= 2048:
+                x.sp = (y.g.contiguous(), idx)      # (a later x.acc() scatters it: _Var.acc)
+            else:
                 x.acc(K.max_points_bwd(y.g.contiguous(), idx, l))
         self.steps.append(bwd)
         return y
