@@ -22,6 +22,32 @@ over channels (for a weight gradient the channel is a ``cout`` row), so that a w
 scale of the others.  Per-channel SUMS (bias gradient, BatchNorm partial sums) cancel, so a channel's own value is no scale for
 its summation error: ``sum_err`` divides by the channel's sum of |terms| instead, the quantity every fp32 summation bound is
 stated in.
+
+The purpose-built kernels (anti-phase, row-streaming, wgrad3, wgrad3r, wgrad1, the direct kernels; tests/conv_special_child.py)
+need three things more:
+
+* The affine on load (the lazy BatchNorm, ``pcuda_src.scale1 / shift1``): every kernel applies it as ONE ``fmaf(x, sc, sh)`` in
+  fp32 BEFORE the bf16 split (csrc/conv_rs.hip:166 and :177 for the halo pixel, csrc/conv_wgrad3r.hip:163-164,
+  csrc/conv_wgrad1.hip:129, csrc/conv_wgrad3.hip:244, csrc/conv_ap_impl.h:252, csrc/conv_direct.hip:289 in pw_fwd_kernel, which
+  then multiplies the unrounded result), and padding is zero AFTER the affine
+  (conv_rs.hip:162 ``vm``, conv_wgrad3r.hip:160 ``rvalid`` / :125 ``hvalid``).  ``affine_operand`` is
+  ``float32(float64(x) * sc + sh)``: the product of two fp32 values is exact in float64 (48 bits), so this is the singly
+  rounded FMA up to double rounding -- the float64 sum rounds to 53 bits before the rounding to 24, which moves the result by
+  one fp32 ulp where the float64 value falls within 2^-29 ulp of an fp32 tie (about one element in 2^28; it changes a bf16 hi
+  plane only if the element also sits on a bf16 tie).  The references take the OPERAND (``source_operand``), so their zero
+  padding is applied after the affine by construction.
+* Two sources (the zero-copy concat): ``source_operand(x1, sc, sh, x2)`` = cat(affine(x1), x2), the affine on the first source
+  only, as every caller uses it.
+* The direct (vector-ALU) kernels' operand model, ``model="direct"``: they rebuild the weight from the packed planes as
+  hi + lo -- hi alone in bf16 mode, whose records carry no lo plane (``if (p.rec > IG_REC) v += ...[32]``:
+  csrc/conv_direct.hip:68-69 c1_fwd, :255-258 pw_fwd, :323-326 pw_dgrad; csrc/conv_direct_d1.hip:55-58 d1_dgrad, :373-375
+  d5_fwd) -- and multiply UNROUNDED fp32 activations with fp32 FMA: one plane (x, hi + lo) or (x, hi), one chain
+  (``bound_of(e32, None)``).  hi + lo is exact in fp32 (16 significant bits).  The direct weight gradients (c1_wgrad_kernel,
+  d1_wgrad_kernel) read no packed weight and round nothing: ``prec=None``.  ``d1_fwd_kernel`` (conv_direct_d1.hip:524-540) is
+  an MFMA kernel with the ordinary split and the three planes: the ordinary model.
+  Against the bf16x3 model the direct one keeps what that drops: with x = xh + xl + r, |xl| <= 2^-9 |x|, |r| <= 2^-18 |x|,
+  |wl| <= 2^-9 |w|:  direct - bf16x3 = sum xl wl + sum r (wh + wl), at most (2^-18 + 2^-18 (1 + 2^-8)) sum |x| |w|
+  <= 2^-17 (1 + 2^-8) sum |x| |w| (tests/test_conv_exact_ref.py checks it).
 """
 import os
 import re
@@ -69,6 +95,36 @@ def planes(a, b, prec):
         return [(ah, bh)]
     assert prec == "bf16x3", prec
     return [(al, bh), (ah, bl), (ah, bh)]
+
+
+def affine_operand(x, sc=None, sh=None):
+    """the fp32 value a kernel splits: fmaf(x, sc, sh) per channel (module docstring: float32(float64(x) * sc + sh))"""
+    if sc is None:
+        return x.float()
+    assert x.dtype == sc.dtype == sh.dtype == torch.float32
+    return (x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None]).float()
+
+
+def source_operand(x1, sc=None, sh=None, x2=None):
+    """cat(affine(x1), x2): the operand of a launch with one or two sources, the affine on the first"""
+    a = affine_operand(x1, sc, sh)
+    return a if x2 is None else torch.cat([a, x2.float()], 1)
+
+
+def planes_direct(x, w, prec):
+    """the direct kernels' one product plane: (unrounded activation, hi + lo of the weight; hi alone in bf16 mode)"""
+    wh, wl = split_hi_lo(w)
+    assert prec in ("bf16", "bf16x3"), prec
+    return [(x.float(), wh + wl if prec == "bf16x3" else wh)]
+
+
+def _act_w_planes(act, w, prec, model):
+    if prec is None:
+        return [(act.float(), w.float())]
+    if model == "direct":
+        return planes_direct(act, w, prec)
+    assert model == "mfma", model
+    return planes(act, w, prec)
 
 
 # ------------------------------------------------------------------------------------------ error measures
@@ -149,20 +205,21 @@ def fold2(d):
     return d.reshape(n, c, h // 2, 2, w // 2, 2).sum((3, 5))
 
 
-def forward_ref(g, x, w, b, slope, prec, dtype=torch.float64):
+def forward_ref(g, x, w, b, slope, prec, dtype=torch.float64, model="mfma"):
     """y = lrelu(conv(up(x), w) + b) on the kernels' operand planes (prec) or on the unrounded operands (prec=None), evaluated
-    in ``dtype``.  x is the STORED input (half resolution when in_up: rounding commutes with the nearest-x2 fold)."""
+    in ``dtype``.  x is the STORED input (half resolution when in_up: rounding commutes with the nearest-x2 fold); with an
+    affine on load or two sources: ``source_operand(...)``.  model: "mfma" or "direct" (module docstring)."""
     xu = g.up(x.float())
-    pl = [(xu, w.float())] if prec is None else planes(xu, w, prec)
+    pl = _act_w_planes(xu, w, prec, model)
     z = _sum_planes(lambda a, c: F.conv2d(a, c, None, **g.kw()), pl, dtype)
     if b is not None:
         z = z + b.to(dtype)[None, :, None, None]
     return _lrelu(z, slope)
 
 
-def dgrad_ref(g, dy, w, prec, dtype=torch.float64, base=None, mask=None, fold=False):
+def dgrad_ref(g, dy, w, prec, dtype=torch.float64, base=None, mask=None, fold=False, model="mfma"):
     """dx (logical resolution; folded 2x2 when ``fold``) = conv^T(dy, w) [+ base] [* (a > 0 ? 1 : slope), mask = (a, slope)]"""
-    pl = [(dy.float(), w.float())] if prec is None else planes(dy, w, prec)
+    pl = _act_w_planes(dy, w, prec, model)
     size = (g.n, g.cin, g.h, g.w)
     d = _sum_planes(lambda a, c: G.conv2d_input(size, c, a, **g.kw()), pl, dtype)
     if fold:

@@ -148,3 +148,105 @@ def test_one_accumulator_for_three_planes_rounds_more_than_one_chain():
     ratio = float(np.sqrt((e_one ** 2).mean() / (e_sep ** 2).mean()))
     print("interleaved / separate rms error:", ratio)
     assert 1.4 < ratio <= 3.0
+
+
+# ------------------------------------------------------------------------------------------ the purpose-built kernels' paths
+def _affine_data(seed=5, n=2, c1=24, c2=16, cout=40, h=12, w_=16, k=3):
+    rng = np.random.default_rng(seed)
+    t = lambda *s, sd=1.0, mu=0.0: torch.from_numpy(rng.normal(mu, sd, s).astype(np.float32))
+    # shifts far from zero: a border padded BEFORE the affine would carry them
+    return dict(x1=t(n, c1, h, w_), x2=t(n, c2, h, w_), sc=t(c1, sd=0.3, mu=1.0), sh=t(c1, sd=0.3, mu=2.5),
+                w=t(cout, c1 + c2, k, k, sd=0.1), b=t(cout, sd=0.1), dz=t(n, cout, h, w_),
+                g=R.Geom(n, c1 + c2, cout, h, w_, k, 1, k // 2, 1))
+
+
+def test_affine_operand_is_the_singly_rounded_fma():
+    d = _affine_data()
+    a = R.affine_operand(d["x1"], d["sc"], d["sh"])
+    exact = d["x1"].double() * d["sc"].double()[None, :, None, None] + d["sh"].double()[None, :, None, None]
+    assert a.dtype == torch.float32
+    # within half an fp32 ulp of the exact value (2^-24 relative), and NOT the doubly rounded fp32 product + sum everywhere
+    assert bool(((a.double() - exact).abs() <= 2.0 ** -24 * exact.abs()).all())
+    two_step = d["x1"] * d["sc"][None, :, None, None] + d["sh"][None, :, None, None]
+    assert bool((two_step != a).any())
+    assert torch.equal(R.affine_operand(d["x1"]), d["x1"])
+    cat = R.source_operand(d["x1"], d["sc"], d["sh"], d["x2"])
+    assert torch.equal(cat[:, :24], a) and torch.equal(cat[:, 24:], d["x2"])
+
+
+def test_affine_and_two_sources_equal_autograd_in_float64():
+    """prec=None: forward, weight gradient and data gradient of conv(cat(x1 * sc + sh, x2)) against torch autograd in float64
+    (the operand's own fp32 rounding taken out by building the autograd graph ON the operand)"""
+    d = _affine_data()
+    g = d["g"]
+    xin = R.source_operand(d["x1"], d["sc"], d["sh"], d["x2"]).double().requires_grad_(True)
+    wt = d["w"].double().requires_grad_(True)
+    bias = d["b"].double().requires_grad_(True)
+    z = torch.nn.functional.conv2d(xin, wt, bias, padding=1)
+    y = torch.nn.functional.leaky_relu(z, 0.2)
+    z.backward(d["dz"].double())
+    op = R.source_operand(d["x1"], d["sc"], d["sh"], d["x2"])
+    assert torch.allclose(R.forward_ref(g, op, d["w"], d["b"], 0.2, None), y.detach(), rtol=1e-13, atol=1e-13)
+    assert torch.allclose(R.wgrad_ref(g, op, d["dz"], None), wt.grad, rtol=1e-13, atol=1e-12)
+    assert torch.allclose(R.dgrad_ref(g, d["dz"], d["w"], None), xin.grad, rtol=1e-13, atol=1e-13)
+    assert torch.allclose(R.chan_sums(d["dz"])[0], bias.grad, rtol=1e-13, atol=1e-12)
+    # the direct model with prec=None is the same unrounded expression
+    assert torch.equal(R.forward_ref(g, op, d["w"], d["b"], 0.2, None, model="direct"), R.forward_ref(g, op, d["w"], d["b"], 0.2, None))
+    # an affine on the gradient (the row-streaming data gradient's AFF instantiations): the operand is the transformed dy
+    sc, sh = d["sc"].repeat(2)[:g.cout], d["sh"].repeat(2)[:g.cout]
+    dyo = R.affine_operand(d["dz"], sc, sh)
+    want = torch.nn.grad.conv2d_input((g.n, g.cin, g.h, g.w), d["w"].double(), dyo.double(), padding=1)
+    assert torch.allclose(R.dgrad_ref(g, dyo, d["w"], None), want, rtol=1e-13, atol=1e-13)
+
+
+@pytest.mark.parametrize("prec", [None, "bf16x3", "bf16"])
+def test_padding_after_the_affine_differs_from_affine_after_padding_by_the_border_term(prec):
+    """conv(pad0(fma(x))) against conv(fma(pad0(x))): the second sees ``sh`` on the padding ring, so the difference is the
+    convolution of a tensor that is ``sh`` on the ring and zero inside -- evaluated on the same operand planes -- and it
+    vanishes away from the border"""
+    d = _affine_data(c2=0, c1=32)
+    g, F = d["g"], torch.nn.functional
+    op = R.affine_operand(d["x1"], d["sc"], d["sh"])
+    after = R.forward_ref(g, op, d["w"], None, 1.0, prec)                                 # the kernels' order
+    g0 = R.Geom(g.n, g.cin, g.cout, g.h + 2, g.w + 2, 3, 1, 0, 1)
+    padded = R.affine_operand(F.pad(d["x1"], (1, 1, 1, 1)), d["sc"], d["sh"])             # the wrong order
+    before = R.forward_ref(g0, padded, d["w"], None, 1.0, prec)
+    ring = padded.clone()
+    ring[:, :, 1:-1, 1:-1] = 0.0
+    term = R.forward_ref(g0, ring, d["w"], None, 1.0, prec)
+    assert before.shape == after.shape == term.shape
+    assert torch.allclose(before - after, term, rtol=0, atol=1e-12 * float(after.abs().max()))
+    assert float(term[:, :, 1:-1, 1:-1].abs().max()) == 0.0
+    # with shifts of 2.5 the border term is of the size of the output itself: a wrongly padded border cannot pass any bound
+    assert float(term[:, :, 0].abs().max()) > 0.5 * float(after.abs().max())
+    # the same for the weight gradient: its border term is the gradient against the ring
+    wa = R.wgrad_ref(g, op, d["dz"], prec)
+    wb = R.wgrad_ref(g0, padded, d["dz"], prec)
+    assert torch.allclose(wb - wa, R.wgrad_ref(g0, ring, d["dz"], prec), rtol=0, atol=1e-12 * float(wa.abs().max()))
+    assert R.rel_err(wb, wa) > 1e-2
+
+
+@pytest.mark.parametrize("op", ["fwd", "dgrad"])
+def test_direct_model_against_the_bf16x3_model(op):
+    """direct - bf16x3 = sum xl wl + sum r (wh + wl) <= 2^-17 (1 + 2^-8) sum |x| |w| (module docstring of conv_exact_ref), and
+    it is not zero; in bf16 mode the direct model keeps the unrounded activation: (x - xh) wh, <= 2^-9 sum |x| |wh|"""
+    d = _affine_data()
+    g, F = d["g"], torch.nn.functional
+    x = R.source_operand(d["x1"], d["sc"], d["sh"], d["x2"])
+    if op == "fwd":
+        f = lambda prec, model: R.forward_ref(g, x, d["w"], None, 1.0, prec, model=model)
+        mag = lambda wabs: F.conv2d(x.double().abs(), wabs, padding=1)
+    else:
+        f = lambda prec, model: R.dgrad_ref(g, d["dz"], d["w"], prec, model=model)
+        mag = lambda wabs: torch.nn.grad.conv2d_input((g.n, g.cin, g.h, g.w), wabs, d["dz"].double().abs(), padding=1)
+    diff = (f("bf16x3", "direct") - f("bf16x3", "mfma")).abs()
+    lim = 2.0 ** -17 * (1 + 2.0 ** -8) * mag(d["w"].double().abs())
+    assert bool((diff <= lim).all()) and float(diff.max()) > 0.0
+    assert float((diff / lim).max()) > 1e-3            # the bound is not vacuous: the terms are of that order
+    wh = R.split_hi_lo(d["w"])[0].double()
+    diff1 = (f("bf16", "direct") - f("bf16", "mfma")).abs()
+    assert bool((diff1 <= 2.0 ** -9 * mag(wh.abs())).all()) and float(diff1.max()) > 0.0
+    # and the direct model is the closer one to the unrounded convolution in bf16x3 mode: only the weight's 2^-18 is left
+    plain = f(None, "mfma")
+    assert bool(((f("bf16x3", "direct") - plain).abs() <= 2.0 ** -17 * mag(d["w"].double().abs())).all())
+    assert R.bound_of(1.0, None) == R.FACTOR      # one chain
