@@ -391,7 +391,13 @@ __global__ __launch_bounds__(256) void dice_count_kernel(const float* __restrict
     const long long n = i / hw, px = i - n * hw;
     const long long base = n * c * hw + px;
     float m = -INFINITY;
-    for (int k = 0; k < c; ++k) m = fmaxf(m, logits[base + k * hw]);
+    bool nan = false;
+    for (int k = 0; k < c; ++k) {
+      const float v = logits[base + k * hw];
+      nan |= v != v;
+      m = fmaxf(m, v);
+    }
+    if (nan) m = NAN;                        // np.max propagates NaN: such a pixel equals its maximum in no channel
     for (int k = 1; k < c; ++k) {
       const unsigned int hard = logits[base + k * hw] == m ? 1u : 0u;
       const unsigned int yk = onehot[base + k * hw];
@@ -697,7 +703,8 @@ extern "C" int pcuda_dice_metric(const float* logits, const uint8_t* onehot, int
 // ------------------------------------------------------------------------------------------
 // validation metrics (train_mscmrseg.py:85-92; metric.py:39-82): label maps and per-class Dice
 // ------------------------------------------------------------------------------------------
-// labels[n][i] = FIRST channel holding the per-pixel maximum (= np.argmax(soft_to_hard_pred(x), axis=-1))
+// labels[n][i] = FIRST channel holding the per-pixel maximum (= np.argmax(soft_to_hard_pred(x), axis=-1)); a NaN in any
+// channel makes the reference's np.max NaN, which no channel equals: label 0
 template <typename T>
 __global__ __launch_bounds__(256) void argmax_labels_kernel(const T* __restrict__ x, long long sn, long long sc, int c,
                                                             long long hw, long long npix, uint8_t* __restrict__ lab) {
@@ -706,11 +713,13 @@ __global__ __launch_bounds__(256) void argmax_labels_kernel(const T* __restrict_
     const T* px = x + n * sn + q;
     float best = (float)px[0];
     int bi = 0;
+    bool nan = best != best;
     for (int k = 1; k < c; ++k) {
       const float v = (float)px[(long long)k * sc];
+      nan |= v != v;
       if (v > best) { best = v; bi = k; }
     }
-    lab[i] = (uint8_t)bi;
+    lab[i] = (uint8_t)(nan ? 0 : bi);
   }
 }
 

@@ -1054,7 +1054,8 @@ def match_hist(images, tvalues, tquantiles, tlen, out=None):
 
 
 def argmax_labels(x):
-    """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum."""
+    """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum (a NaN in
+    any channel: label 0, as the reference's np.max leaves no channel equal to it)."""
     if x.dtype not in (torch.float32, torch.uint8):
         raise TypeError("argmax_labels: fp32 logits or a uint8 one-hot mask")
     _req(x, x.dtype)
@@ -1081,9 +1082,10 @@ def label_dice(pred_labels, gt_labels, num_classes):
     return out
 
 
-def _label_volume(t, name):
-    """a 2-D / 3-D integer label volume as the library reads it: contiguous uint8 or int32 (wider integers clamped to
-    the int32 range, which no class value lies outside of), and its (ndim, z, h, w)"""
+def _label_volume(t, name, spare=-2 ** 31):
+    """a 2-D / 3-D integer label volume as the library reads it: contiguous uint8 or int32 (int64 values outside the
+    int32 range, which no class value lies in, become ``spare``: an int32 value the caller matches nothing with), and
+    its (ndim, z, h, w)"""
     if not torch.is_tensor(t) or not t.is_cuda:
         raise RuntimeError("%s: HIP device tensors only (no CPU fallback)" % name)
     if t.dim() not in (2, 3):
@@ -1093,7 +1095,9 @@ def _label_volume(t, name):
     elif t.dtype not in (torch.uint8, torch.int32):
         if t.is_floating_point() or t.is_complex():
             raise TypeError("%s: integer label volumes only (got %s)" % (name, t.dtype))
-        t = (t.clamp(-2 ** 31, 2 ** 31 - 1) if t.dtype == torch.int64 else t).to(torch.int32)
+        if t.dtype == torch.int64:
+            t = t.masked_fill((t < -2 ** 31) | (t > 2 ** 31 - 1), spare)
+        t = t.to(torch.int32)
     shp = (1,) * (3 - t.dim()) + tuple(t.shape)
     return t.contiguous(), t.dim(), shp
 
@@ -1104,13 +1108,16 @@ def surface_metrics(pred, gt, classes, spacing=None, connectivity=1):
     hd, asd(pred -> gt), asd(gt -> pred), |pred == c|, |gt == c|, |both|, flags (1: pred empty, 2: gt empty; hd and asd
     are NaN where a flag is set).  ``spacing``: per-axis voxel spacing (None = 1); ``connectivity``: 1..ndim, the
     footprint of the erosion that extracts the borders."""
-    pred, nd, shp = _label_volume(pred, "surface_metrics")
-    gt, nd_g, shp_g = _label_volume(gt, "surface_metrics")
+    cls = [int(c) for c in classes]
+    if any(c < -2 ** 31 or c > 2 ** 31 - 1 for c in cls):
+        raise ValueError("surface_metrics: class values must fit int32 (got %s)" % (cls,))
+    spare = next(v for v in range(-2 ** 31, -2 ** 31 + len(cls) + 1) if v not in cls)      # no class: wider labels go here
+    pred, nd, shp = _label_volume(pred, "surface_metrics", spare)
+    gt, nd_g, shp_g = _label_volume(gt, "surface_metrics", spare)
     if shp != shp_g or nd != nd_g:
         raise ValueError("surface_metrics: shapes differ (%s vs %s)" % (tuple(pred.shape), tuple(gt.shape)))
     if pred.dtype != gt.dtype:
         pred, gt = pred.to(torch.int32), gt.to(torch.int32)
-    cls = [int(c) for c in classes]
     ccls = (C.c_int * max(1, len(cls)))(*cls)
     sp = None
     if spacing is not None:

@@ -57,6 +57,45 @@ def test_scipy_largest_components_matches_flood_fill():
     """)
 
 
+@needs_scipy
+def test_scipy_matches_brute_force_on_the_edge_shapes():
+    """the cases of tests/eval_shapes.py (what tests/test_eval_edges_gpu.py holds the kernels to): the brute force there
+    is the reference, and here scipy agrees with it within the same bounds, without a GPU"""
+    _in_child("""
+        sys.path.insert(0, %r)
+        import eval_shapes as S
+
+        def same(a, b, unit, what):
+            assert np.array_equal(a[:, [0, 4, 5, 6, 7]], b[:, [0, 4, 5, 6, 7]]), what
+            ok = b[:, 7] == 0
+            assert np.isnan(a[~ok, 1:4]).all() and np.isnan(b[~ok, 1:4]).all(), what
+            if unit:
+                assert np.array_equal(a[ok, 1], b[ok, 1]), (what, a, b)
+            assert np.allclose(a[ok, 1:4], b[ok, 1:4], rtol=1e-12, atol=0), (what, a, b)
+
+        n = 0
+        for shape in S.DEGENERATE_SHAPES:
+            p, t = S.degenerate_pair(G.blobs, shape)
+            assert all((p == c).any() or (t == c).any() for c in (1, 2, 3)), shape
+            for conn in range(1, len(shape) + 1):
+                for sp in (None, S.ANISO[-len(shape):]):
+                    same(G.surface(p, t, S.DEGENERATE_CLASSES, sp, conn),
+                         G.surface_brute(p, t, S.DEGENERATE_CLASSES, sp, conn), sp is None, (shape, conn, sp))
+                    n += 1
+        assert n == 50
+        for name, p, t, cls, sp, conn in S.surface_cases():
+            same(G.surface(p, t, cls, sp, conn), G.surface_brute(p, t, cls, sp, conn), sp is None, name)
+        far = G.surface_brute(*S.far_voxels((2, 3, 1030)), [1])[0]
+        assert far[1] == far[2] == far[3] == np.sqrt(1.0 + 4.0 + 1029.0 ** 2)
+        for name, m, kept in S.ccl_cases():
+            ref = G.largest_components_brute(m)
+            assert np.array_equal(G.largest_components(m), ref), name
+            assert kept is None or int(np.count_nonzero(ref)) == kept, (name, int(np.count_nonzero(ref)))
+            assert np.array_equal(G.largest_components(m.astype(bool)), G.largest_components_brute(m.astype(bool))), name
+        assert S.snake(129, 131).sum() == 8579 and S.two_snakes().sum() == 1222 and S.rings(63).size == 3969
+    """ % os.path.join(ROOT, "tests"))
+
+
 def test_closed_forms_in_the_fixture():
     g = np.load(os.path.join(GOLD, "eval_metrics.npz"))
     names = {str(g[k]): k[:-5] for k in g.files if k.endswith("_name") and k.startswith("s")}

@@ -14,6 +14,7 @@ case -> branch
   bce_const 1, 255, 257, 5000                   one workgroup striding over the input; labels 0 / 1; gscale; accuracy
   sum_all 1, 1023, 1025, 524288 + 5             one block, two blocks, SUM_BLOCKS = 512 capped; scale
   dice_metric (1, 4, 513 * 512)                 the count kernel's 1024-block cap
+  argmax_labels / dice_metric, NaN and +-inf    np.max propagates NaN: label 0, no channel counted; -0.0 == +0.0 ties
 
 Bounds: scalars within 1e-5 * max(1, |ref|); loss gradients 1e-4 (2e-4 where logits are saturated, as
 test_losses_against_oracle_large allows); entropy maps and probabilities 1e-5 (the project's bound for them);
@@ -187,3 +188,63 @@ def test_dice_metric_past_the_block_cap(dev):
     onehot = _onehot(rng, n, c, hw)
     ref = OM.dice_coef_multilabel(onehot.numpy(), OM.soft_to_hard_pred(logits.numpy(), 1), c)
     assert abs(float(K.dice_metric(logits.to(dev), onehot.to(dev))) - ref) < 1e-6
+
+
+def _nan_logits():
+    """[2, 4, 9, 11] logits with non-finite pixels, as (logits, {pixel: expected label}): np.max propagates NaN, so the
+    reference's soft_to_hard_pred marks no channel of a pixel that holds one, and its argmax gives 0"""
+    rng = np.random.default_rng(77)
+    x = rng.normal(0, 1, (2, 4, 9, 11)).astype(np.float32)
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    px = {(0, 0, 0): ([nan, 0.3, 2.0, 1.0], 0),            # NaN in channel 0
+          (0, 0, 1): ([0.1, nan, 0.5, 0.2], 0),            # in a middle channel, before the largest finite value
+          (0, 3, 4): ([0.1, 0.7, nan, 0.2], 0),            # in a middle channel, after it
+          (0, 8, 10): ([1.0, 2.0, 3.0, nan], 0),           # in the last channel
+          (1, 0, 0): ([0.0, 1.0, 2.0, nan], 0),
+          (1, 4, 5): ([nan, nan, nan, nan], 0),            # all NaN
+          (1, 8, 10): ([nan, inf, 0.0, -inf], 0),          # NaN beside +inf
+          (0, 1, 1): ([0.0, 1.0, 2.0, inf], 3),
+          (0, 2, 2): ([-inf, -1.0, -3.0, -2.0], 1),
+          (0, 5, 5): ([-inf, -inf, -inf, -inf], 0),        # a four-way tie
+          (1, 2, 3): ([1.0, inf, inf, 0.0], 1),            # a tie at +inf: the first
+          (1, 3, 3): ([-1.0, -0.0, 0.0, -2.0], 1),         # -0.0 == +0.0: a tie, the first
+          (1, 3, 4): ([-1.0, 0.0, -0.0, -2.0], 1),
+          (1, 6, 7): ([0.0, -0.0, -1.0, -1.0], 0)}
+    for (n, i, j), (v, _) in px.items():
+        x[n, :, i, j] = v
+    return x, {k: lab for k, (_, lab) in px.items()}
+
+
+def test_argmax_labels_with_nan_and_infinite_logits(dev):
+    from oracle import metrics as OM
+    from pointcloududa_amd import kernels as K
+    x, labels = _nan_logits()
+    ref = OM.argmax_labels(x)
+    for (n, i, j), lab in labels.items():
+        assert ref[n, i, j] == lab, (n, i, j)                            # the reference itself
+    got = K.argmax_labels(torch.from_numpy(x).to(dev))
+    assert got.dtype == torch.uint8 and np.array_equal(got.cpu().numpy(), ref)
+    view = torch.from_numpy(np.ascontiguousarray(np.concatenate([x, x], 1))).to(dev)[:, 4:]     # batch stride 8 channels
+    assert np.array_equal(K.argmax_labels(view).cpu().numpy(), ref)
+    rng = np.random.default_rng(78)
+    onehot = np.moveaxis(np.eye(4, dtype=np.uint8)[rng.integers(0, 4, (2, 9, 11))], -1, 1).copy()
+    got8 = K.argmax_labels(torch.from_numpy(onehot).to(dev))              # the uint8 reader: unchanged
+    assert np.array_equal(got8.cpu().numpy(), OM.argmax_labels(onehot))
+
+
+def test_dice_metric_with_nan_and_infinite_logits(dev):
+    from oracle import metrics as OM
+    from pointcloududa_amd import kernels as K
+    x, labels = _nan_logits()
+    lab = np.random.default_rng(79).integers(0, 4, (2, 9, 11))
+    for n, i, j in labels:
+        lab[n, i, j] = 1 + (i + j) % 3                                   # foreground truth under every special pixel
+    onehot = np.moveaxis(np.eye(4, dtype=np.uint8)[lab], -1, 1).copy()
+    hard = OM.soft_to_hard_pred(x, 1)
+    assert not hard[0, :, 0, 1].any() and not hard[1, :, 4, 5].any() and hard[0, :, 5, 5].all()
+    assert hard[1, :, 3, 3].tolist() == [0, 1, 1, 0]
+    ref = OM.dice_coef_multilabel(onehot, hard, 4)
+    got = float(K.dice_metric(torch.from_numpy(x).to(dev), torch.from_numpy(onehot).to(dev)))
+    assert abs(got - ref) < 1e-6, (got, ref)
+    dropped = np.where(np.isnan(x), -np.inf, x)                         # what dropping the NaN would count: far outside
+    assert abs(OM.dice_coef_multilabel(onehot, OM.soft_to_hard_pred(dropped, 1), 4) - ref) > 1e-3
