@@ -554,6 +554,19 @@ size_t pcuda_surface_metrics_workspace_size(int ndim, int z, int h, int w, int n
 int pcuda_surface_metrics(const void* pred, const void* gt, int labels_i32, int ndim, int z, int h, int w, const int* classes,
                           int ncls, int connectivity, const double* spacing, double* out, void* workspace,
                           size_t workspace_bytes, pcuda_stream_t s);
+/* pcuda_surface_metrics and four more columns: out[k][12] (device fp64) = the eight columns above (the same bits), then
+ * the percentile-th percentile (0..100; 95: medpy's hd95) of the pooled distances sd(A, B) u sd(B, A) by numpy's linear
+ * method (n values sorted ascending: v = (n - 1) * percentile / 100, lo = floor(v), hi = min(lo + 1, n - 1), t = v - lo,
+ * s[lo] + (s[hi] - s[lo]) * t, or s[hi] - (s[hi] - s[lo]) * (1 - t) where t >= 0.5; fp64, one rounding per operation),
+ * assd = (asd(pred->gt) + asd(gt->pred)) / 2 (medpy's assd), |border(A)|, |border(B)|.  Columns 8 and 9 are NaN when a
+ * flag is set.  The two order statistics are selected exactly on the device (MSB-first radix select over the stored
+ * squared distances, 8 bits per pass: 4 passes at unit spacing, 8 with spacing; integer atomics only): the same bits
+ * from run to run, no host synchronisation.  Argument checks as pcuda_surface_metrics; a percentile outside [0, 100] or
+ * NaN is PCUDA_E_BADARG.  Needs its own, larger workspace. */
+size_t pcuda_surface_metrics_ext_workspace_size(int ndim, int z, int h, int w, int ncls, const double* spacing);
+int pcuda_surface_metrics_ext(const void* pred, const void* gt, int labels_i32, int ndim, int z, int h, int w,
+                              const int* classes, int ncls, int connectivity, const double* spacing, double percentile,
+                              double* out, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* out (uint8) = for each label 1..min(nlabels, 255) of mask the largest face-connected component (among equal sizes
  * the one whose first voxel comes first in raster order), every other voxel 0 */
 size_t pcuda_largest_components_workspace_size(int ndim, int z, int h, int w);

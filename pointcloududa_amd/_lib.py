@@ -16,7 +16,7 @@ ACT_SIGMOID, ACT_SOFTMAX = 0, 1
 FAM_CONV_FWD, FAM_CONV_WGRAD, FAM_POINTWISE, FAM_DENSE_F32 = 0, 1, 2, 3
 
 c_f32p = C.c_void_p      # all device pointers travel as integers
-i32, i64, f32, vp, sz = C.c_int, C.c_longlong, C.c_float, C.c_void_p, C.c_size_t
+i32, i64, f32, f64, vp, sz = C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_void_p, C.c_size_t
 
 
 class ConvGeom(C.Structure):
@@ -137,6 +137,8 @@ _PROTOS = {
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
     "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),
     "pcuda_surface_metrics": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "pcuda_surface_metrics_ext_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),
+    "pcuda_surface_metrics_ext": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, f64, vp, vp, sz, vp]),
     "pcuda_largest_components_workspace_size": (sz, [i32, i32, i32, i32]),
     "pcuda_largest_components": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "pcuda_linear_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),

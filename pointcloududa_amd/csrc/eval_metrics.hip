@@ -13,6 +13,16 @@
 // Unit spacing keeps squared distances in int32 end to end and takes the sqrt in fp64 (what scipy computes from its
 // integer feature offsets); anisotropic spacing carries fp64 squared distances.
 //
+// Extended rows (pcuda_surface_metrics_ext: + percentile Hausdorff distance, assd, border counts).  The last axis pass
+// (MODE 3) also stores d^2 at every border voxel of the eval mask: T itself is the key (int32, or the fp64 whose bit
+// pattern orders like its value).  Two order statistics per class (ranks lo and hi of numpy's linear percentile) over
+// the union of the class's two fields are then selected exactly, MSB first, 8 bits per pass: a histogram kernel (LDS
+// histogram per block and query, flushed with integer atomic adds: the bins do not depend on block scheduling) and a
+// one-wave-per-query kernel that finds the rank's bin, extends the query's key prefix and narrows its rank.  The two
+// queries are tracked apart (they may part at any digit).  sizeof(T) passes: 4 (int) or 8 (double), every class and both
+// queries in the same launches, no host round trip.  Launches: border, ndim axis passes, 2 * sizeof(T) select, final
+// = 13 / 21 for a 3-D volume at unit / other spacing (12 / 20 in 2-D), after two memsets.
+//
 // Largest connected components: union-find on equal labels with face connectivity; the atomicMin hook makes every
 // root its component's minimum linear index (= the raster-first voxel), so a 64-bit atomic max on
 // (size << 32) | (0xFFFFFFFF - root) picks, per label, the largest component and among equal sizes the raster-first.
@@ -142,6 +152,9 @@ __device__ __forceinline__ int em_eval_bit(int f) { return (f & 1) ? (f >> 1) : 
 // MODE 0: first axis, input = the border masks (0 on the target's border, inf elsewhere), writes fout
 // MODE 1: middle axis, fin -> fout
 // MODE 2: last axis, fin -> (max d^2, sum d, count) at the eval mask's border voxels, no field written
+// MODE 3: MODE 2, and d^2 stored to fout at those voxels only (the select's keys; the other entries are never read).
+//         A field whose target is empty (all inf; its class is flagged) stores inf there and still counts them, so
+//         that the counts are the border voxel counts for every class
 template <typename T, int MODE>
 __global__ __launch_bounds__(EM_LINE_THREADS) void em_edt_pass_kernel(
     const uint16_t* __restrict__ bmask, const T* __restrict__ fin, T* __restrict__ fout, int* __restrict__ vbuf,
@@ -233,14 +246,26 @@ __global__ __launch_bounds__(EM_LINE_THREADS) void em_edt_pass_kernel(
             mx = kk > mx ? kk : mx;
             sum += sqrt((double)d);
             ++cnt;
+            if constexpr (MODE == 3) out[o] = d;
           }
         }
       }
     } else if (MODE < 2) {
       for (int q = 0; q < n; ++q) out[base + q * ln.stride] = V::inf();
+    } else if (MODE == 3) {
+      for (int q = 0; q < n; ++q) {
+        const long long o = base + q * ln.stride;
+        const uint16_t* pm = bmask + o;
+        const unsigned b = *pm;
+        PCUDA_KEEP(pm);
+        if ((b >> eb) & 1u) {
+          out[o] = V::inf();
+          ++cnt;
+        }
+      }
     }
   }
-  if constexpr (MODE == 2) {                 // one wave per block: fixed-order shuffle tree, one partial per block
+  if constexpr (MODE >= 2) {                 // one wave per block: fixed-order shuffle tree, one partial per block
     sum = wave_sum_d(sum);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -258,12 +283,17 @@ __global__ __launch_bounds__(EM_LINE_THREADS) void em_edt_pass_kernel(
 
 // out[k][8] = dice, hd, asd(pred->gt), asd(gt->pred), |A|, |B|, |A.B|, flags (1: A empty, 2: B empty); hd / asd NaN
 // when a flag is set
+struct EmRow {                 // what the extended row needs beyond the eight columns
+  double s[2];
+  unsigned long long c[2];
+  int flags;
+};
+
+// the eight columns of class k to o[0..7]: one thread, every sum in index order
 template <typename T>
-__global__ void em_final_kernel(const unsigned* __restrict__ cnt_part, int nbb, const unsigned long long* __restrict__ maxkey,
-                                const double* __restrict__ psum, const unsigned* __restrict__ pcnt, int nb2, int ncls,
-                                double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k >= ncls) return;
+__device__ __forceinline__ EmRow em_final_row(const unsigned* __restrict__ cnt_part, int nbb,
+                                              const unsigned long long* __restrict__ maxkey, const double* __restrict__ psum,
+                                              const unsigned* __restrict__ pcnt, int nb2, int ncls, int k, double* o) {
   unsigned long long a = 0, b = 0, ab = 0;
   for (int i = 0; i < nbb; ++i) {
     const unsigned* p = cnt_part + (long long)i * 3 * ncls + 3 * k;
@@ -287,7 +317,6 @@ __global__ void em_final_kernel(const unsigned* __restrict__ cnt_part, int nbb, 
   const unsigned long long mk = m0 > m1 ? m0 : m1;
   const double d2 = sizeof(T) == sizeof(int) ? (double)mk : __builtin_bit_cast(double, mk);
   const double nan = __builtin_nan("");
-  double* o = out + 8 * k;
   o[0] = dsum > 0.0 ? 2.0 * (double)ab / dsum : 0.0;
   o[1] = flags ? nan : sqrt(d2);
   o[2] = flags ? nan : s[0] / (double)c[0];
@@ -296,6 +325,175 @@ __global__ void em_final_kernel(const unsigned* __restrict__ cnt_part, int nbb, 
   o[5] = (double)b;
   o[6] = (double)ab;
   o[7] = (double)flags;
+  return EmRow{{s[0], s[1]}, {c[0], c[1]}, flags};
+}
+
+template <typename T>
+__global__ void em_final_kernel(const unsigned* __restrict__ cnt_part, int nbb, const unsigned long long* __restrict__ maxkey,
+                                const double* __restrict__ psum, const unsigned* __restrict__ pcnt, int nb2, int ncls,
+                                double* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= ncls) return;
+  em_final_row<T>(cnt_part, nbb, maxkey, psum, pcnt, nb2, ncls, k, out + 8 * k);
+}
+
+// ------------------------------------------------------------------------------------------------ percentile select
+constexpr int EM_SEL_BITS = 8;                       // digit width: 256 bins, 2 KiB of LDS for a block's two histograms
+constexpr int EM_SEL_BINS = 1 << EM_SEL_BITS;
+constexpr int EM_SEL_BLOCKS = 256;                   // grid.x of the histogram kernel (grid-stride over the voxels)
+
+struct EmSel {                                       // one query: class k, q = 0 (rank lo) / 1 (rank hi)
+  unsigned long long prefix;                         // the digits found so far, in place; after the last pass: the key
+  unsigned long long rank;                           // rank among the keys that share the prefix
+};
+
+// numpy.percentile's 'linear' method on n sorted values: v = (n - 1) * quant, lo = floor(v), hi = min(lo + 1, n - 1),
+// t = v - lo, one fp64 rounding per operation
+__device__ __forceinline__ void em_ranks(unsigned long long n, double quant, unsigned long long* lo, unsigned long long* hi,
+                                         double* t) {
+#pragma clang fp contract(off)
+  if (n == 0) {
+    *lo = 0; *hi = 0; *t = 0.0;
+    return;
+  }
+  const double v = (double)(n - 1) * quant;
+  const double fl = floor(v);
+  const unsigned long long l = (unsigned long long)fl;       // quant <= 1: l <= n - 1
+  *lo = l;
+  *hi = l + 1 < n ? l + 1 : n - 1;
+  *t = v - fl;
+}
+
+// numpy's _lerp: a + (b - a) * t, and b - (b - a) * (1 - t) where t >= 0.5; no FMA (the products are rounded first)
+__device__ __forceinline__ double em_lerp(double a, double b, double t) {
+#pragma clang fp contract(off)
+  const double diff = b - a;
+  double p = diff * t;
+  asm volatile("" : "+v"(p));
+  double r = a + p;
+  if (t >= 0.5) {
+    double p2 = diff * (1.0 - t);
+    asm volatile("" : "+v"(p2));
+    r = b - p2;
+  }
+  return r;
+}
+
+// pass with digit shift `shift`: hist[k][q][bin] += the live keys of class k (fields 2k and 2k + 1 at their eval masks'
+// border voxels) that share query q's prefix above the digit.  grid (EM_SEL_BLOCKS, ncls)
+template <typename T>
+__global__ __launch_bounds__(256) void em_sel_hist_kernel(const uint16_t* __restrict__ bmask, const T* __restrict__ keys,
+                                                          long long numel, int shift, const EmSel* __restrict__ sel,
+                                                          unsigned* __restrict__ hist) {
+  typedef EmVal<T> V;
+  __shared__ unsigned h[2 * EM_SEL_BINS];
+  for (int i = threadIdx.x; i < 2 * EM_SEL_BINS; i += 256) h[i] = 0;
+  __syncthreads();
+  const int k = blockIdx.y;
+  const EmSel* ps = sel + 2 * k;
+  const unsigned long long p0 = ps[0].prefix, p1 = ps[1].prefix;
+  PCUDA_KEEP(ps);
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < numel; i += 256ll * gridDim.x) {
+    const uint16_t* pm = bmask + i;
+    const unsigned b = *pm;
+    PCUDA_KEEP(pm);
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      const int f = 2 * k + d;
+      if ((b >> em_eval_bit(f)) & 1u) {
+        const T* pk = keys + (long long)f * numel + i;
+        const unsigned long long key = V::key(*pk);
+        PCUDA_KEEP(pk);
+        const unsigned bin = (unsigned)(key >> shift) & (EM_SEL_BINS - 1);
+        // (two shifts: shift + EM_SEL_BITS is the key's width in the first pass)
+        if ((((key ^ p0) >> shift) >> EM_SEL_BITS) == 0) atomicAdd(&h[bin], 1u);
+        if ((((key ^ p1) >> shift) >> EM_SEL_BITS) == 0) atomicAdd(&h[EM_SEL_BINS + bin], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  unsigned* g = hist + (long long)k * 2 * EM_SEL_BINS;
+  for (int i = threadIdx.x; i < 2 * EM_SEL_BINS; i += 256)
+    if (h[i]) atomicAdd(g + i, h[i]);
+}
+
+// one wave per query (grid 2 * ncls): the bin that holds the query's rank becomes its next digit.  first: the ranks
+// come from the per-block counts (n = c0 + c1, integer sums)
+__global__ __launch_bounds__(64) void em_sel_narrow_kernel(const unsigned* __restrict__ hist, int shift, int first,
+                                                           const unsigned* __restrict__ pcnt, int nb2, double quant,
+                                                           EmSel* __restrict__ sel) {
+  const int k = blockIdx.x >> 1, q = blockIdx.x & 1, lane = threadIdx.x;
+  EmSel* ps = sel + blockIdx.x;
+  unsigned long long rank;
+  if (first) {
+    unsigned long long n = 0;
+    for (int f = 2 * k + 1; f >= 2 * k; --f)
+      for (int i = lane; i < nb2; i += 64) {
+        const unsigned* pc = pcnt + (long long)f * nb2 + i;
+        n += *pc;
+        PCUDA_KEEP(pc);
+      }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    unsigned long long lo, hi;
+    double t;
+    em_ranks(n, quant, &lo, &hi, &t);
+    rank = q ? hi : lo;
+  } else {
+    rank = ps->rank;
+  }
+  const unsigned long long prefix = ps->prefix;
+  PCUDA_KEEP(ps);
+  // lane j: bins 4j .. 4j + 3; exclusive prefix sums across the wave
+  const unsigned* ph = hist + (long long)blockIdx.x * EM_SEL_BINS + 4 * lane;
+  unsigned long long c[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c[j] = ph[j];
+  PCUDA_KEEP(ph);
+  const unsigned long long mine = c[0] + c[1] + c[2] + c[3];
+  unsigned long long incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  unsigned long long excl = incl - mine;
+  if (rank >= excl && rank < incl) {             // exactly one lane (none when the class has no live key)
+    int j = 0;
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+      if (j == u && rank >= excl + c[u]) { excl += c[u]; j = u + 1; }
+    EmSel r;
+    r.prefix = prefix | ((unsigned long long)(4 * lane + j) << shift);
+    r.rank = rank - excl;
+    *ps = r;
+  }
+}
+
+// out[k][12]: the eight columns of em_final_kernel, the percentile of the pooled distances (em_ranks / em_lerp on the
+// sqrt of the two selected keys), assd = (asd(pred->gt) + asd(gt->pred)) / 2, and the border voxel counts of pred and gt;
+// columns 8 and 9 NaN when a flag is set
+template <typename T>
+__global__ void em_final_ext_kernel(const unsigned* __restrict__ cnt_part, int nbb, const unsigned long long* __restrict__ maxkey,
+                                    const double* __restrict__ psum, const unsigned* __restrict__ pcnt, int nb2, int ncls,
+                                    const EmSel* __restrict__ sel, double quant, double* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= ncls) return;
+  double* o = out + 12 * k;
+  const EmRow r = em_final_row<T>(cnt_part, nbb, maxkey, psum, pcnt, nb2, ncls, k, o);
+  unsigned long long lo, hi;
+  double t;
+  em_ranks(r.c[0] + r.c[1], quant, &lo, &hi, &t);
+  const EmSel* ps = sel + 2 * k;
+  const unsigned long long k0 = ps[0].prefix, k1 = ps[1].prefix;
+  PCUDA_KEEP(ps);
+  const double d0 = sizeof(T) == sizeof(int) ? (double)k0 : __builtin_bit_cast(double, k0);
+  const double d1 = sizeof(T) == sizeof(int) ? (double)k1 : __builtin_bit_cast(double, k1);
+  const double nan = __builtin_nan("");
+  o[8] = r.flags ? nan : em_lerp(sqrt(d0), sqrt(d1), t);
+  o[9] = r.flags ? nan : (o[2] + o[3]) / 2.0;
+  o[10] = (double)r.c[0];
+  o[11] = (double)r.c[1];
 }
 
 // ------------------------------------------------------------------------------------------------ connected components
@@ -479,9 +677,34 @@ EmLayout em_layout(int ndim, int z, int h, int w, int ncls, bool aniso) {
   return L;
 }
 
+// the extended call's workspace: the plain layout, then the select's keys (in 3-D the first axis pass's field buffer is
+// free again by the last pass and serves), its per-pass histograms [passes][ncls][2][bins] and its queries [ncls][2]
+struct EmExtLayout {
+  EmLayout base;
+  size_t keys, hist, sel, zero_bytes, total;
+  int passes;
+};
+EmExtLayout em_ext_layout(int ndim, int z, int h, int w, int ncls, bool aniso) {
+  const long long numel = (long long)z * h * w;
+  const size_t tsz = aniso ? sizeof(double) : sizeof(int);
+  EmExtLayout X;
+  X.base = em_layout(ndim, z, h, w, ncls, aniso);
+  X.passes = (int)tsz * 8 / EM_SEL_BITS;
+  size_t o = X.base.total;
+  if (ndim == 3) X.keys = X.base.fa;
+  else { X.keys = o; o += em_align((size_t)2 * ncls * numel * tsz); }
+  X.hist = o; o += em_align((size_t)X.passes * ncls * 2 * EM_SEL_BINS * sizeof(unsigned));
+  X.sel = o; o += em_align((size_t)ncls * 2 * sizeof(EmSel));
+  X.zero_bytes = o - X.hist;                 // histograms and queries: one memset
+  X.total = o;
+  return X;
+}
+
+// ext: null for the plain rows out[ncls][8]; else the extended rows out[ncls][12] at percentile 100 * quant
 template <typename T>
 int em_surface_run(const void* pred, const void* gt, int labels_i32, int ndim, int z, int h, int w, const EmClasses& cls,
-                   int conn, const double* spacing, double* out, char* ws, const EmLayout& L, hipStream_t s) {
+                   int conn, const double* spacing, double* out, char* ws, const EmLayout& L, hipStream_t s,
+                   const EmExtLayout* ext = nullptr, double quant = 0.0) {
   const long long numel = (long long)z * h * w;
   const int nf = 2 * cls.n;
   uint16_t* bmask = (uint16_t*)(ws + L.bmask);
@@ -494,6 +717,8 @@ int em_surface_run(const void* pred, const void* gt, int labels_i32, int ndim, i
   unsigned* pcnt = (unsigned*)(ws + L.pcnt);
   if (hipMemsetAsync(maxkey, 0, nf * sizeof(unsigned long long), s) != hipSuccess)
     PCUDA_FAIL(PCUDA_E_LAUNCH, "surface_metrics: memset failed");
+  if (ext && hipMemsetAsync(ws + ext->hist, 0, ext->zero_bytes, s) != hipSuccess)
+    PCUDA_FAIL(PCUDA_E_LAUNCH, "surface_metrics_ext: memset failed");
   ProfScope prof(PCUDA_FAM_POINTWISE, (double)numel * (2.0 * (labels_i32 ? 4 : 1) + 2.0 * nf * ndim * (2 * sizeof(T) + 4)), s);
   if (labels_i32)
     hipLaunchKernelGGL(em_border_kernel<int>, dim3(L.nbb), dim3(256), 0, s, (const int*)pred, (const int*)gt, z, h, w, ndim,
@@ -509,6 +734,39 @@ int em_surface_run(const void* pred, const void* gt, int labels_i32, int ndim, i
   hipLaunchKernelGGL((em_edt_pass_kernel<T, 0>), dim3(cdiv(lw.nlines, EM_LINE_THREADS), nf), dim3(EM_LINE_THREADS), 0, s,
                      bmask, (const T*)nullptr, fa, vb, numel, lw, spw, maxkey, psum, pcnt);
   PCUDA_CHECK_LAUNCH("em_edt_pass_kernel<W>");
+  if (ext) {
+    T* keys = (T*)(ws + ext->keys);
+    if (ndim == 3) {
+      hipLaunchKernelGGL((em_edt_pass_kernel<T, 1>), dim3(cdiv(lh.nlines, EM_LINE_THREADS), nf), dim3(EM_LINE_THREADS), 0,
+                         s, bmask, (const T*)fa, fb, vb, numel, lh, sph, maxkey, psum, pcnt);
+      PCUDA_CHECK_LAUNCH("em_edt_pass_kernel<H>");
+      hipLaunchKernelGGL((em_edt_pass_kernel<T, 3>), dim3(L.nb2, nf), dim3(EM_LINE_THREADS), 0, s, bmask, (const T*)fb, keys,
+                         vb, numel, lz, spz, maxkey, psum, pcnt);
+      PCUDA_CHECK_LAUNCH("em_edt_pass_kernel<Z, keys>");
+    } else {
+      hipLaunchKernelGGL((em_edt_pass_kernel<T, 3>), dim3(L.nb2, nf), dim3(EM_LINE_THREADS), 0, s, bmask, (const T*)fa, keys,
+                         vb, numel, lh, sph, maxkey, psum, pcnt);
+      PCUDA_CHECK_LAUNCH("em_edt_pass_kernel<H, keys>");
+    }
+    unsigned* hist = (unsigned*)(ws + ext->hist);
+    EmSel* sel = (EmSel*)(ws + ext->sel);
+    const int nbx = (int)(cdiv(numel, 256) < EM_SEL_BLOCKS ? cdiv(numel, 256) : EM_SEL_BLOCKS);
+    for (int p = 0; p < ext->passes; ++p) {
+      const int shift = (ext->passes - 1 - p) * EM_SEL_BITS;
+      unsigned* hp = hist + (size_t)p * cls.n * 2 * EM_SEL_BINS;
+      hipLaunchKernelGGL(em_sel_hist_kernel<T>, dim3(nbx, cls.n), dim3(256), 0, s, (const uint16_t*)bmask, (const T*)keys,
+                         numel, shift, (const EmSel*)sel, hp);
+      PCUDA_CHECK_LAUNCH("em_sel_hist_kernel");
+      hipLaunchKernelGGL(em_sel_narrow_kernel, dim3(2 * cls.n), dim3(64), 0, s, (const unsigned*)hp, shift, p == 0 ? 1 : 0,
+                         (const unsigned*)pcnt, L.nb2, quant, sel);
+      PCUDA_CHECK_LAUNCH("em_sel_narrow_kernel");
+    }
+    hipLaunchKernelGGL(em_final_ext_kernel<T>, dim3(1), dim3(64), 0, s, (const unsigned*)cntp, L.nbb,
+                       (const unsigned long long*)maxkey, (const double*)psum, (const unsigned*)pcnt, L.nb2, cls.n,
+                       (const EmSel*)sel, quant, out);
+    PCUDA_CHECK_LAUNCH("em_final_ext_kernel");
+    return PCUDA_OK;
+  }
   if (ndim == 3) {
     hipLaunchKernelGGL((em_edt_pass_kernel<T, 1>), dim3(cdiv(lh.nlines, EM_LINE_THREADS), nf), dim3(EM_LINE_THREADS), 0, s,
                        bmask, (const T*)fa, fb, vb, numel, lh, sph, maxkey, psum, pcnt);
@@ -561,6 +819,43 @@ int em_ccl_run(const T* mask, int z, int h, int w, int nl, uint8_t* out, char* w
 extern "C" size_t pcuda_surface_metrics_workspace_size(int ndim, int z, int h, int w, int ncls, const double* spacing) {
   if (em_check_shape("surface_metrics_workspace_size", ndim, z, h, w) != PCUDA_OK || ncls < 1 || ncls > EM_MAXCLS) return 0;
   return em_layout(ndim, z, h, w, ncls, em_anisotropic(ndim, spacing)).total;
+}
+
+extern "C" size_t pcuda_surface_metrics_ext_workspace_size(int ndim, int z, int h, int w, int ncls, const double* spacing) {
+  if (em_check_shape("surface_metrics_ext_workspace_size", ndim, z, h, w) != PCUDA_OK || ncls < 1 || ncls > EM_MAXCLS)
+    return 0;
+  return em_ext_layout(ndim, z, h, w, ncls, em_anisotropic(ndim, spacing)).total;
+}
+
+extern "C" int pcuda_surface_metrics_ext(const void* pred, const void* gt, int labels_i32, int ndim, int z, int h, int w,
+                                         const int* classes, int ncls, int connectivity, const double* spacing,
+                                         double percentile, double* out, void* workspace, size_t workspace_bytes,
+                                         pcuda_stream_t s) {
+  const int rc = em_check_shape("surface_metrics_ext", ndim, z, h, w);
+  if (rc != PCUDA_OK) return rc;
+  if (!pred || !gt || !out || !classes) PCUDA_FAIL(PCUDA_E_BADARG, "surface_metrics_ext: null pointer");
+  if (ncls < 1 || ncls > EM_MAXCLS) PCUDA_FAIL(PCUDA_E_BADARG, "surface_metrics_ext: %d classes (1..%d)", ncls, EM_MAXCLS);
+  if (connectivity < 1 || connectivity > ndim)
+    PCUDA_FAIL(PCUDA_E_BADARG, "surface_metrics_ext: connectivity %d outside 1..%d", connectivity, ndim);
+  if (spacing)
+    for (int a = 0; a < ndim; ++a)
+      if (!(spacing[a] > 0.0) || !isfinite(spacing[a]))
+        PCUDA_FAIL(PCUDA_E_BADARG, "surface_metrics_ext: spacing[%d] = %g is not a positive finite number", a, spacing[a]);
+  if (!(percentile >= 0.0 && percentile <= 100.0))
+    PCUDA_FAIL(PCUDA_E_BADARG, "surface_metrics_ext: percentile %g outside 0..100", percentile);
+  const bool aniso = em_anisotropic(ndim, spacing);
+  const EmExtLayout X = em_ext_layout(ndim, z, h, w, ncls, aniso);
+  if (!workspace || workspace_bytes < X.total)
+    PCUDA_FAIL(PCUDA_E_WORKSPACE, "surface_metrics_ext: workspace %zu bytes, needs %zu", workspace_bytes, X.total);
+  EmClasses cls = {};
+  for (int k = 0; k < ncls; ++k) cls.c[k] = classes[k];
+  cls.n = ncls;
+  const double quant = percentile / 100.0;
+  if (aniso)
+    return em_surface_run<double>(pred, gt, labels_i32, ndim, z, h, w, cls, connectivity, spacing, out, (char*)workspace,
+                                  X.base, (hipStream_t)s, &X, quant);
+  return em_surface_run<int>(pred, gt, labels_i32, ndim, z, h, w, cls, connectivity, nullptr, out, (char*)workspace, X.base,
+                             (hipStream_t)s, &X, quant);
 }
 
 extern "C" int pcuda_surface_metrics(const void* pred, const void* gt, int labels_i32, int ndim, int z, int h, int w,

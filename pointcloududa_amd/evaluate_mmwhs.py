@@ -22,6 +22,18 @@ def metrics_from_rows(rows, ifhd=True, ifasd=True):
     return res
 
 
+def metrics_from_rows_ext(rows, ifhd=True, ifasd=True):
+    """[dice, hd, asd, hd95, assd] per class from ``M.class_metrics_ext(gt, pred, CLASSES)`` rows, with the conventions of
+    ``metrics_from_rows``: hd and hd95 go with ``ifhd``, asd and assd with ``ifasd``; -1 where not asked for and where
+    medpy would raise (a class empty on either side)"""
+    res = []
+    for row in rows:
+        ok_hd, ok_asd = ifhd and not row[7], ifasd and not row[7]
+        res += [row[0], row[1] if ok_hd else -1, row[2] if ok_asd else -1, row[8] if ok_hd else -1,
+                row[9] if ok_asd else -1]
+    return res
+
+
 def metrics(img_gt, img_pred, ifhd=True, ifasd=True):
     """``evaluate_mmwhs.py:32-62``"""
     return metrics_from_rows(M.class_metrics(img_gt, img_pred, CLASSES).tolist(), ifhd, ifasd)

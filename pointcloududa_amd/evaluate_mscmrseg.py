@@ -26,6 +26,25 @@ def metrics_from_rows(rows, ifhd=True, ifasd=True):
     return res
 
 
+def metrics_from_rows_ext(rows, ifhd=True, ifasd=True):
+    """[dice, hd, asd, hd95, assd] per class from ``M.class_metrics_ext(gt, pred, CLASSES)`` rows, with the conventions of
+    ``metrics_from_rows``: hd and hd95 go with ``ifhd``, asd and assd with ``ifasd``; -1 where not asked for, and five
+    times -1 for a class empty on either side when any of them is asked for"""
+    res = []
+    for row in rows:
+        vals = [row[0], -1, -1, -1, -1]
+        if ifhd or ifasd:
+            if row[7]:
+                vals = [-1, -1, -1, -1, -1]
+            else:
+                if ifhd:
+                    vals[1], vals[3] = row[1], row[8]
+                if ifasd:
+                    vals[2], vals[4] = row[2], row[9]
+        res += vals
+    return res
+
+
 def metrics(img_gt, img_pred, ifhd=True, ifasd=True):
     """[Dice endo, HD endo, ASD endo, Dice RV, HD RV, ASD RV, Dice Myo, HD Myo, ASD Myo] (``metric.py:126-169``)"""
     return metrics_from_rows(M.class_metrics(img_gt, img_pred, CLASSES).tolist(), ifhd, ifasd)

@@ -1,8 +1,8 @@
 """Metrics of ``src/utils/metric.py`` on the device.
 
 Per-step training metrics (``metric.py:5-36`` + ``src/utils/utils.py:32-40``), and the evaluation metrics the reference
-takes from ``medpy.metric.binary``: ``dc``, ``hd`` and ``asd`` with medpy's signatures and definitions, and the
-reference's ``evaluate`` / ``metrics2`` (``metric.py:39-113``).  All of them run on the HIP kernels
+takes from ``medpy.metric.binary``: ``dc``, ``hd`` and ``asd`` with medpy's signatures and definitions (and medpy's
+``hd95`` and ``assd``, which the reference does not print but the field's tables do), and the reference's ``evaluate`` / ``metrics2`` (``metric.py:39-113``).  All of them run on the HIP kernels
 (``kernels.surface_metrics``: border extraction, exact Euclidean distance transform, deterministic reductions); numpy
 inputs are copied to the current device and the results come back as Python floats.  There is no CPU fallback."""
 from __future__ import annotations
@@ -95,17 +95,50 @@ def asd(result, reference, voxelspacing=None, connectivity=1) -> float:
     return r[2]
 
 
-def class_metrics(img_gt, img_pred, classes) -> torch.Tensor:
-    """``surface_metrics(gt, pred, classes)`` on the device (no synchronisation): per class (dice, hd, asd(gt -> pred) =
-    what medpy's ``asd(gt_c, pred_c)`` returns, ...), the argument order of the reference's ``dc(gt_c_i, pred_c_i)`` /
-    ``hd(gt_c_i, pred_c_i)`` / ``asd(gt_c_i, pred_c_i)`` calls: flag 1 means an empty gt class (medpy's 'first')."""
+def _pair_ext(result, reference, voxelspacing, connectivity, percentile=95.0):
+    r = K.surface_metrics_ext(_binary(result), _binary(reference), [1], voxelspacing, connectivity, percentile)
+    return r[0].tolist()                                  # one synchronisation
+
+
+def hd95(result, reference, voxelspacing=None, connectivity=1) -> float:
+    """medpy.metric.binary.hd95: ``numpy.percentile`` (95, linear) of the surface distances of both directions pooled,
+    result -> reference and reference -> result; RuntimeError if either is empty"""
+    r = _pair_ext(result, reference, voxelspacing, connectivity)
+    raise_if_empty(r[7])
+    return r[8]
+
+
+def assd(result, reference, voxelspacing=None, connectivity=1) -> float:
+    """medpy.metric.binary.assd: the mean of ``asd(result, reference)`` and ``asd(reference, result)``; RuntimeError if
+    either is empty"""
+    r = _pair_ext(result, reference, voxelspacing, connectivity)
+    raise_if_empty(r[7])
+    return r[9]
+
+
+def _gt_pred(img_gt, img_pred):
     gt, pred = to_device(img_gt), to_device(img_pred)
     if gt.dim() != pred.dim():
         raise ValueError("The arrays 'img_gt' and 'img_pred' should have the "
                          "same dimension, {} against {}".format(gt.dim(), pred.dim()))
     if pred.device != gt.device:
         pred = pred.to(gt.device)
+    return gt, pred
+
+
+def class_metrics(img_gt, img_pred, classes) -> torch.Tensor:
+    """``surface_metrics(gt, pred, classes)`` on the device (no synchronisation): per class (dice, hd, asd(gt -> pred) =
+    what medpy's ``asd(gt_c, pred_c)`` returns, ...), the argument order of the reference's ``dc(gt_c_i, pred_c_i)`` /
+    ``hd(gt_c_i, pred_c_i)`` / ``asd(gt_c_i, pred_c_i)`` calls: flag 1 means an empty gt class (medpy's 'first')."""
+    gt, pred = _gt_pred(img_gt, img_pred)
     return K.surface_metrics(gt, pred, classes)
+
+
+def class_metrics_ext(img_gt, img_pred, classes, percentile=95.0) -> torch.Tensor:
+    """``surface_metrics_ext(gt, pred, classes)`` on the device (no synchronisation), with ``class_metrics``' argument
+    order: its eight columns, then the percentile distance (hd95), assd and the border counts of gt and pred"""
+    gt, pred = _gt_pred(img_gt, img_pred)
+    return K.surface_metrics_ext(gt, pred, classes, percentile=percentile)
 
 
 def _named(img_gt, img_pred, classes, names, apply_hd, apply_asd):

@@ -108,12 +108,14 @@ def valid_model_with_one_dataset(seg_model, batches: Iterable, d4: bool = True, 
 
 @torch.no_grad()
 def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd: bool = True, ifasd: bool = True,
-                    variant: str = "mmwhs"):
+                    variant: str = "mmwhs", extended: bool = False):
     """The device-side core of ``evaluate_segmentation`` (``evaluate_mmwhs.py:118-132``; ``evaluate_mscmrseg.py:132-169``
     without its crop / resize): eval forward in batches of ``bs`` -> argmax -> ``keep_largest_connected_components``
     (``klc``) -> the variant's ``metrics`` list ([dice, hd, asd] per class), with one synchronisation per volume.
     ``x``: the volume's slices [Z,C,H,W] (fp32, device tensor or numpy); ``gt_labels``: its label volume [Z,H,W] (MM-WHS
-    1..4; MS-CMRSeg codes 200 / 500 / 600, which the predicted labels 1 / 2 / 3 are mapped to after ``klc``)."""
+    1..4; MS-CMRSeg codes 200 / 500 / 600, which the predicted labels 1 / 2 / 3 are mapped to after ``klc``).
+    ``extended``: [dice, hd, asd, hd95, assd] per class (``metrics_from_rows_ext``) from the one call per volume to the
+    extended kernel; the first three are the bits the default call returns."""
     if variant not in ("mmwhs", "mscmrseg"):
         raise ValueError("evaluate_volume: variant 'mmwhs' or 'mscmrseg'")
     dev = next(seg_model.parameters()).device
@@ -136,5 +138,8 @@ def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd
         lut = torch.arange(256, dtype=torch.int32, device=dev)
         lut[1:4] = torch.tensor([200, 500, 600], dtype=torch.int32, device=dev)
         pred = lut[pred.long()]
+    if extended:
+        rows = M.class_metrics_ext(M.to_device(gt_labels, dev), pred, mod.CLASSES).tolist()    # one sync
+        return mod.metrics_from_rows_ext(rows, ifhd, ifasd)
     rows = M.class_metrics(M.to_device(gt_labels, dev), pred, mod.CLASSES).tolist()        # one sync
     return mod.metrics_from_rows(rows, ifhd, ifasd)
