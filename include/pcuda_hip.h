@@ -530,6 +530,56 @@ size_t pcuda_match_hist_workspace_size(int b, int h, int w, int c, int is_u8);
 int pcuda_match_hist(const void* in, void* out, int is_u8, int b, int h, int w, int c, const double* tvalues,
                      const double* tquantiles, const int* tlen, int tstride, void* workspace, size_t workspace_bytes,
                      pcuda_stream_t s);
+/* device-side slice preparation of the MS-CMRSeg data (utils/read_nii_image.py:60-74 preprocess_volume, used at :100, 137,
+ * 176 behind RescaleIntensity -> uint8, the nearest resize to 256 and the centre crop to 224; csrc/preprocess.hip).  Parity
+ * with OpenCV / ITK is unpinned: the convention below is this build's own, written after OpenCV's clahe.cpp and ITK's
+ * RescaleIntensityImageFilter, and pinned by two independent restatements in tests/golden/preprocess.npz.
+ *
+ * pcuda_clahe: cv2.createCLAHE(clipLimit, tileGridSize=(tiles_x, tiles_y)).apply on uint8 slices in[n][h][w].
+ *   histSize = 256.  Extended size: w % tiles_x == 0 and h % tiles_y == 0: (eh, ew) = (h, w); otherwise eh = h + (tiles_y -
+ *   h % tiles_y) and ew = w + (tiles_x - w % tiles_x) (OpenCV's quirk: a divisible axis still grows by a whole `tiles` when
+ *   the other one is indivisible), BORDER_REFLECT_101 at the bottom / right (index reflection in the histogram kernel: no
+ *   padded copy is written).  th = eh / tiles_y, tw = ew / tiles_x, T = th tw; clip = 0 if clip_limit <= 0 else
+ *   max(int(clip_limit T / 256), 1) (double, on the host); lutScale = float(255) / float(T), inv_tw = 1.0f / float(tw),
+ *   inv_th likewise (fp32, on the host).
+ *   Per tile: the 256-bin histogram; if clip > 0: clipped = sum(max(hist[i] - clip, 0)), hist = min(hist, clip), batch =
+ *   clipped / 256, residual = clipped - 256 batch (integers), every bin gains batch, and if residual != 0, step = max(256 /
+ *   residual, 1) and bin i gains 1 iff i % step == 0 and i / step < residual (the closed form of OpenCV's loop);
+ *   lut[i] = clamp(rint(float(cumsum_i) lutScale), 0, 255), rint to nearest even.
+ *   Per pixel (y, x) of value v: txf = float(x) inv_tw - 0.5f, tx1 = floor(txf), xa = txf - float(tx1), xa1 = 1.0f - xa, then
+ *   tx2 = min(tx1 + 1, tiles_x - 1), tx1 = max(tx1, 0); y likewise; res = (L[ty1][tx1][v] xa1 + L[ty1][tx2][v] xa) ya1 +
+ *   (L[ty2][tx1][v] xa1 + L[ty2][tx2][v] xa) ya, every operation rounded separately in fp32 (-ffp-contract=off); the output
+ *   is clamp(rint(res), 0, 255).
+ *   out_mode PCUDA_CLAHE_U8: uint8 out[n][h][w]; PCUDA_CLAHE_F32X3: fp32 out[n][3][h][w] = float(u8) / 255.0f in all three
+ *   channels (cv2.imread of a grey PNG, / 255., moveaxis: what the networks take).
+ *   1 <= tiles <= 16 per axis, h, w >= 2 (up to 32768), every pad <= dim - 1 (the reflection is defined), T < 2^24, else
+ *   PCUDA_E_BADARG.  workspace: pcuda_clahe_workspace_size bytes (the LUTs [n][tiles_y][tiles_x][256]), 16-byte aligned.
+ *
+ * pcuda_rescale_resize_crop_u8: the front of read_*_nii_save_png in one pass over the output: in[n][sh][sw] of in_dtype
+ * (PCUDA_PRE_F32 / _I16 / _U8) -> uint8 out[n][oh][ow].  lo / hi = the volume's minimum / maximum, reduced on the device
+ * (integer atomics on order-preserving keys, no host round trip).  Rescale after ITK, in double, every operation rounded
+ * separately: scale = 255 / (hi - lo) if hi != lo, else 255 / hi if hi != 0, else 0; shift = -lo scale;
+ * u8 = clamp(trunc(double(v) scale + shift), 0, 255).  Nearest resize after cv2.INTER_NEAREST: sy = min(int(floor(y ify)),
+ * sh - 1), ify = 1.0 / (double(resize_h) / double(sh)), x likewise (the identity when resize == source size).  Centre crop
+ * (crop_volume): rows resize_h / 2 - crop / 2 .. resize_h / 2 + crop / 2 of the resized slice, columns likewise, so
+ * oh = ow = 2 (crop / 2); crop = 0: none, (oh, ow) = (resize_h, resize_w).  A crop window outside the resized slice is
+ * PCUDA_E_BADARG.  NaN in the volume is unsupported.  PCUDA_PRE_U8_RAW: a uint8 volume whose values are kept as they are
+ * (no rescale: resize_volume / crop_volume on their own).  workspace: pcuda_rescale_resize_crop_u8_workspace_size bytes.
+ *
+ * Both: never allocate, never synchronise; `in` is never written and in == out is rejected; n == 0 is a no-op returning 0;
+ * integer atomics only: the same bits from run to run. */
+#define PCUDA_CLAHE_U8 0
+#define PCUDA_CLAHE_F32X3 1
+#define PCUDA_PRE_F32 0
+#define PCUDA_PRE_I16 1
+#define PCUDA_PRE_U8 2
+#define PCUDA_PRE_U8_RAW 3
+size_t pcuda_clahe_workspace_size(int n, int tiles_x, int tiles_y);
+int pcuda_clahe(const uint8_t* in, void* out, int n, int h, int w, double clip_limit, int tiles_x, int tiles_y, int out_mode,
+                void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+size_t pcuda_rescale_resize_crop_u8_workspace_size(void);
+int pcuda_rescale_resize_crop_u8(const void* in, int in_dtype, int n, int sh, int sw, int resize_h, int resize_w, int crop,
+                                 uint8_t* out, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

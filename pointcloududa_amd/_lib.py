@@ -133,6 +133,10 @@ _PROTOS = {
     "pcuda_stylize": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_match_hist_workspace_size": (sz, [i32, i32, i32, i32, i32]),
     "pcuda_match_hist": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp]),
+    "pcuda_clahe_workspace_size": (sz, [i32, i32, i32]),
+    "pcuda_clahe": (i32, [vp, vp, i32, i32, i32, f64, i32, i32, i32, vp, sz, vp]),
+    "pcuda_rescale_resize_crop_u8_workspace_size": (sz, []),
+    "pcuda_rescale_resize_crop_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "pcuda_argmax_labels": (i32, [vp, i32, i64, i64, i32, i32, i64, vp, vp]),
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
     "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),

@@ -1053,6 +1053,65 @@ def match_hist(images, tvalues, tquantiles, tlen, out=None):
     return out
 
 
+def clahe(images_u8, clip_limit=2.0, tiles_x=4, tiles_y=4, to_float=False, out=None):
+    """CLAHE of uint8 ``[N,H,W]`` slices (``pcuda_clahe``: the convention of include/pcuda_hip.h, written after OpenCV's
+    ``createCLAHE(clip_limit, (tiles_x, tiles_y)).apply``) -> a new uint8 ``[N,H,W]`` tensor, or fp32 ``[N,3,H,W]`` holding
+    ``u8 / 255`` in all three channels when ``to_float`` (the input is never written)."""
+    _req(images_u8, torch.uint8)
+    if images_u8.dim() != 3:
+        raise TypeError("clahe: uint8 [N,H,W] slices")
+    images_u8 = images_u8.contiguous()
+    n, h, w = images_u8.shape
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=images_u8.device) if to_float else torch.empty_like(images_u8)
+    else:
+        _req(out, torch.float32 if to_float else torch.uint8)
+        if tuple(out.shape) != ((n, 3, h, w) if to_float else (n, h, w)) or not out.is_contiguous():
+            raise ValueError("clahe: out does not match the result's shape")
+    nbytes = L.lib().pcuda_clahe_workspace_size(n, int(tiles_x), int(tiles_y))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    check(L.lib().pcuda_clahe(images_u8.data_ptr(), out.data_ptr(), n, h, w, float(clip_limit), int(tiles_x), int(tiles_y),
+                              int(bool(to_float)), _ptr(ws), nbytes, _stream()), "clahe")
+    return out
+
+
+_PRE_DTYPES = {torch.float32: 0, torch.int16: 1, torch.uint8: 2}      # PCUDA_PRE_F32 / _I16 / _U8 (3: _U8_RAW)
+
+
+def rescale_resize_crop_u8(volume, resize_h=None, resize_w=None, crop=0, out=None, raw=False):
+    """A fp32, int16 or uint8 ``[N,H,W]`` volume -> uint8 (``pcuda_rescale_resize_crop_u8``): its own minimum / maximum (reduced on
+    the device) stretched to 0..255 in float64 and truncated, a nearest-neighbour resize to ``(resize_h, resize_w)`` (None: the
+    source size) and the centre crop of ``crop`` (0: none; else ``2 * (crop // 2)`` rows and columns) in one pass over the
+    output -> a new tensor (the input is never written).  ``raw`` (uint8 volumes only): the values are kept as they are, no
+    rescale (``PCUDA_PRE_U8_RAW``)."""
+    if raw and volume.dtype != torch.uint8:
+        raise TypeError("rescale_resize_crop_u8: raw takes a uint8 volume, got %s" % (volume.dtype,))
+    if volume.dtype not in _PRE_DTYPES:
+        raise TypeError("rescale_resize_crop_u8: a fp32, int16 or uint8 volume, got %s" % (volume.dtype,))
+    _req(volume, volume.dtype)
+    if volume.dim() != 3:
+        raise TypeError("rescale_resize_crop_u8: an [N,H,W] volume")
+    volume = volume.contiguous()
+    n, sh, sw = volume.shape
+    resize_h = sh if resize_h is None else int(resize_h)
+    resize_w = sw if resize_w is None else int(resize_w)
+    crop = int(crop)
+    if crop < 0 or (crop > 0 and (crop // 2 < 1 or resize_h // 2 - crop // 2 < 0 or resize_w // 2 - crop // 2 < 0)):
+        raise ValueError("rescale_resize_crop_u8: the crop window of %d leaves the %dx%d slice" % (crop, resize_h, resize_w))
+    oh, ow = (2 * (crop // 2),) * 2 if crop > 0 else (resize_h, resize_w)
+    if out is None:
+        out = torch.empty((n, oh, ow), dtype=torch.uint8, device=volume.device)
+    else:
+        _req(out, torch.uint8)
+        if tuple(out.shape) != (n, oh, ow) or not out.is_contiguous():
+            raise ValueError("rescale_resize_crop_u8: out does not match the result's shape")
+    nbytes = L.lib().pcuda_rescale_resize_crop_u8_workspace_size()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=volume.device)
+    check(L.lib().pcuda_rescale_resize_crop_u8(volume.data_ptr(), 3 if raw else _PRE_DTYPES[volume.dtype], n, sh, sw, resize_h, resize_w, crop,
+                                               out.data_ptr(), _ptr(ws), nbytes, _stream()), "rescale_resize_crop_u8")
+    return out
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum (a NaN in
     any channel: label 0, as the reference's np.max leaves no channel equal to it)."""
