@@ -580,6 +580,57 @@ int pcuda_clahe(const uint8_t* in, void* out, int n, int h, int w, double clip_l
 size_t pcuda_rescale_resize_crop_u8_workspace_size(void);
 int pcuda_rescale_resize_crop_u8(const void* in, int in_dtype, int n, int sh, int sw, int resize_h, int resize_w, int crop,
                                  uint8_t* out, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* device-side spacing resample of the MS-CMRSeg data: the .npy path of utils/read_nii_image.py (read_*_nii_save_npy :202-231,
+ * read_*_nii_label_save_npy :234-271; csrc/resample.hip).  The arithmetic is scipy.ndimage.zoom(order=1)'s, pinned bit for bit:
+ * the expected arrays of tests/golden/resample.npz are the outputs of scipy 1.15.3 / numpy themselves
+ * (scripts/make_resample_golden.py), next to a plain restatement of the rule below.
+ *
+ * pcuda_zoom_linear_crop: ndimage.zoom(vol, [1, zh / sh, zw / sw], order=1) of in[n][sh][sw] (dtype PCUDA_PRE_F32 / _I16 / _U8;
+ *   the caller passes the zoomed size (zh, zw) = round(dim factor)), then crop_volume -> out[n][oh][ow] of the same dtype.  Only
+ *   the crop window is computed: rows zh / 2 - crop / 2 .. zh / 2 + crop / 2 of the zoomed slice, columns likewise, so
+ *   oh = ow = 2 (crop / 2); crop = 0: none, (oh, ow) = (zh, zw).
+ *   Per axis, in float64: z = (in - 1) / (out - 1) (1.0 when out == 1), cc = double(k) z for the output index k of the zoomed
+ *   slice, i0 = floor(cc), t = cc - i0, w0 = 1 - t, w1 = t.  Per pixel: acc = (c00 wy0) wx0, += (c01 wy0) wx1, += (c10 wy1) wx0,
+ *   += (c11 wy1) wx1 in that order, every operation rounded on its own (-ffp-contract=off); c01 = in[i0y][i0x + 1] and so on.
+ *   mode='constant', cval=0: a tap whose index equals the input size is 0 (it is never read), and a pixel with cc > in - 1 on
+ *   either axis -- the last coordinate of some (in, out) pairs, (8, 26) the smallest, overshoots by an ulp -- is 0 altogether
+ *   (scipy does not interpolate beyond the last sample).  fp32: out = float(acc); integers: r = acc > 0 ? acc + 0.5 : acc - 0.5,
+ *   clamped to the dtype's range, truncated toward zero (scipy's round half away from zero).  The slice axis has factor 1 and
+ *   drops out (its second tap has weight 0).
+ *   workspace: pcuda_zoom_linear_crop_workspace_size bytes: (i0, t) per output row and column, written by a small kernel.
+ *
+ * pcuda_zoom_standardize: the image chain in one call: the zoom and crop above, mean and std of the zoomed cropped values of
+ *   the whole volume, then out = float((double(x) - mean) / std) (a true float64 division), fp32 out[n][channels][oh][ow] with
+ *   channels 1 or 3 (3: the same value in all three channels, what predict_labels takes; compare PCUDA_CLAHE_F32X3).  The
+ *   statistics stay on the device (no host round trip) and are left in stats[0] = mean, stats[1] = std (device, two doubles).
+ *   Integer volumes, exact: Sx and Sxx in 64-bit integers (per-workgroup partials, then one workgroup; no atomics),
+ *   mean = double(Sx) / double(n), std = sqrt(double(n Sxx - Sx Sx) / (double(n) double(n))) with the numerator in 128-bit
+ *   integers, converted once (nearest even): mean equals numpy.mean bit for bit, std is within 2e-16 relative of numpy.std.
+ *   fp32 volumes: THIS BUILD'S OWN convention: statistics of the fp32-rounded zoomed values accumulated in float64 in a fixed
+ *   reduction order, in two passes (mean = S / n; std = sqrt(sum((x - mean)^2) / n)); numpy's float32 pairwise accumulation of
+ *   a float32 array is not reproduced.  No float atomics.  std == 0 gives inf / NaN as numpy does; NaN in the input is
+ *   unsupported.  workspace: pcuda_zoom_standardize_workspace_size bytes (the table, the partials, the zoomed values).
+ *
+ * pcuda_zoom_labels: the label chain fused, no one-hot tensor: raw codes in[n][sh][sw] (PCUDA_PRE_I16 or _U8); remap: num_remap
+ *   <= 8 (from, to) pairs (host array of 2 num_remap ints), applied in order like the reference's chained np.where; for each
+ *   class c < num_classes (2..8) the four taps above over [label == c] as 0.0 / 1.0, rounded as for uint8; the label is the
+ *   first class whose rounded channel is largest (argmax; every channel 0: class 0) -> uint8 out[n][oh][ow].  A remapped
+ *   value outside [0, num_classes) matches no class; the number of such values in the WHOLE input volume is left in the first
+ *   8 bytes of the workspace (uint64; the reference asserts on it in to_categorical).
+ *   workspace: pcuda_zoom_labels_workspace_size bytes (the counter, then the table).
+ *
+ * All three: never allocate, never synchronise; `in` is never written and in == out is rejected; n == 0 is a no-op returning
+ * 0; sides 1..32768, zh, zw >= 1, a crop window inside the zoomed slice and fewer than 2^31 output values, else
+ * PCUDA_E_BADARG before any launch; the same bits from run to run. */
+size_t pcuda_zoom_linear_crop_workspace_size(int zh, int zw, int crop);
+int pcuda_zoom_linear_crop(const void* in, int dtype, int n, int sh, int sw, int zh, int zw, int crop, void* out,
+                           void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+size_t pcuda_zoom_standardize_workspace_size(int dtype, int n, int zh, int zw, int crop);
+int pcuda_zoom_standardize(const void* in, int dtype, int n, int sh, int sw, int zh, int zw, int crop, int channels,
+                           float* out, double* stats, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+size_t pcuda_zoom_labels_workspace_size(int zh, int zw, int crop);
+int pcuda_zoom_labels(const void* in, int dtype, int n, int sh, int sw, int zh, int zw, int crop, int num_classes,
+                      const int* remap, int num_remap, uint8_t* out, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

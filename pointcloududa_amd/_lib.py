@@ -137,6 +137,12 @@ _PROTOS = {
     "pcuda_clahe": (i32, [vp, vp, i32, i32, i32, f64, i32, i32, i32, vp, sz, vp]),
     "pcuda_rescale_resize_crop_u8_workspace_size": (sz, []),
     "pcuda_rescale_resize_crop_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "pcuda_zoom_linear_crop_workspace_size": (sz, [i32, i32, i32]),
+    "pcuda_zoom_linear_crop": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "pcuda_zoom_standardize_workspace_size": (sz, [i32, i32, i32, i32, i32]),
+    "pcuda_zoom_standardize": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "pcuda_zoom_labels_workspace_size": (sz, [i32, i32, i32]),
+    "pcuda_zoom_labels": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
     "pcuda_argmax_labels": (i32, [vp, i32, i64, i64, i32, i32, i64, vp, vp]),
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
     "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),

@@ -1112,6 +1112,83 @@ def rescale_resize_crop_u8(volume, resize_h=None, resize_w=None, crop=0, out=Non
     return out
 
 
+def _zoom_geometry(what, volume, zoomed_hw, crop, dtypes=_PRE_DTYPES):
+    """the shared host checks of the zoom wrappers -> (contiguous volume, n, sh, sw, zh, zw, crop, oh, ow)"""
+    if volume.dtype not in dtypes:
+        raise TypeError("%s: a %s volume, got %s" % (what, " / ".join(str(d).replace("torch.", "") for d in dtypes), volume.dtype))
+    _req(volume, volume.dtype)
+    if volume.dim() != 3:
+        raise TypeError("%s: an [N,H,W] volume" % what)
+    volume = volume.contiguous()
+    n, sh, sw = volume.shape
+    zh, zw = int(zoomed_hw[0]), int(zoomed_hw[1])
+    crop = int(crop)
+    if zh < 1 or zw < 1:
+        raise ValueError("%s: a zoomed slice of at least 1x1, got %dx%d" % (what, zh, zw))
+    if crop < 0 or (crop > 0 and (crop // 2 < 1 or zh // 2 - crop // 2 < 0 or zw // 2 - crop // 2 < 0)):
+        raise ValueError("%s: the crop window of %d leaves the %dx%d slice" % (what, crop, zh, zw))
+    oh, ow = (2 * (crop // 2),) * 2 if crop > 0 else (zh, zw)
+    return volume, n, sh, sw, zh, zw, crop, oh, ow
+
+
+def _zoom_out(what, out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req(out, dtype)
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError("%s: out does not match the result's shape" % what)
+    return out
+
+
+def zoom_linear_crop(volume, zoomed_hw, crop=0, out=None):
+    """``scipy.ndimage.zoom(volume, [1, zh / H, zw / W], order=1)`` of a fp32, int16 or uint8 ``[N,H,W]`` volume and the centre crop
+    of ``crop`` (0: none; else ``2 * (crop // 2)`` rows and columns), only the crop window computed (``pcuda_zoom_linear_crop``)
+    -> a new tensor of the volume's dtype (the input is never written)."""
+    volume, n, sh, sw, zh, zw, crop, oh, ow = _zoom_geometry("zoom_linear_crop", volume, zoomed_hw, crop)
+    out = _zoom_out("zoom_linear_crop", out, (n, oh, ow), volume.dtype, volume.device)
+    nbytes = L.lib().pcuda_zoom_linear_crop_workspace_size(zh, zw, crop)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=volume.device)
+    check(L.lib().pcuda_zoom_linear_crop(volume.data_ptr(), _PRE_DTYPES[volume.dtype], n, sh, sw, zh, zw, crop, out.data_ptr(),
+                                         _ptr(ws), nbytes, _stream()), "zoom_linear_crop")
+    return out
+
+
+def zoom_standardize(volume, zoomed_hw, crop=0, channels=1, out=None, stats=None):
+    """The image chain of the reference's ``.npy`` preparation in one call (``pcuda_zoom_standardize``): zoom, crop, the volume's
+    mean and standard deviation over the cropped zoomed values (on the device), ``(x - mean) / std`` in float64 -> fp32
+    ``[N,oh,ow]`` (``channels=1``) or ``[N,3,oh,ow]``.  -> ``(out, stats)``; ``stats``: float64 ``[2]`` on the device, mean and std."""
+    volume, n, sh, sw, zh, zw, crop, oh, ow = _zoom_geometry("zoom_standardize", volume, zoomed_hw, crop)
+    if channels not in (1, 3):
+        raise ValueError("zoom_standardize: channels is 1 or 3, got %r" % (channels,))
+    out = _zoom_out("zoom_standardize", out, (n, oh, ow) if channels == 1 else (n, 3, oh, ow), torch.float32, volume.device)
+    stats = _zoom_out("zoom_standardize", stats, (2,), torch.float64, volume.device)
+    nbytes = L.lib().pcuda_zoom_standardize_workspace_size(_PRE_DTYPES[volume.dtype], n, zh, zw, crop)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=volume.device) if nbytes else None
+    check(L.lib().pcuda_zoom_standardize(volume.data_ptr(), _PRE_DTYPES[volume.dtype], n, sh, sw, zh, zw, crop, int(channels),
+                                         out.data_ptr(), stats.data_ptr(), _ptr(ws), nbytes, _stream()), "zoom_standardize")
+    return out, stats
+
+
+def zoom_labels(labels, zoomed_hw, num_classes=4, remap=(), crop=0, out=None):
+    """The label chain of the reference's ``.npy`` preparation fused (``pcuda_zoom_labels``): int16 or uint8 raw codes ``[N,H,W]``,
+    the ``(from, to)`` pairs of ``remap`` applied in order, then ``argmax(zoom(onehot, order=1))`` without the one-hot tensor, and the
+    crop -> ``(uint8 [N,oh,ow], counter)``; ``counter``: int64 ``[1]`` on the device, the number of input values that are no class."""
+    labels, n, sh, sw, zh, zw, crop, oh, ow = _zoom_geometry("zoom_labels", labels, zoomed_hw, crop,
+                                                             {torch.int16: 1, torch.uint8: 2})
+    pairs = [(int(a), int(b)) for a, b in remap]
+    if not 2 <= int(num_classes) <= 8:
+        raise ValueError("zoom_labels: 2..8 classes, got %r" % (num_classes,))
+    if len(pairs) > 8:
+        raise ValueError("zoom_labels: a remap table of at most 8 (from, to) pairs, got %d" % len(pairs))
+    out = _zoom_out("zoom_labels", out, (n, oh, ow), torch.uint8, labels.device)
+    nbytes = L.lib().pcuda_zoom_labels_workspace_size(zh, zw, crop)
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=labels.device)
+    table = (C.c_int * max(2 * len(pairs), 1))(*[v for p in pairs for v in p])
+    check(L.lib().pcuda_zoom_labels(labels.data_ptr(), _PRE_DTYPES[labels.dtype], n, sh, sw, zh, zw, crop, int(num_classes),
+                                    C.cast(table, C.c_void_p), len(pairs), out.data_ptr(), _ptr(ws), nbytes, _stream()), "zoom_labels")
+    return out, ws[:8].view(torch.int64)
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum (a NaN in
     any channel: label 0, as the reference's np.max leaves no channel equal to it)."""

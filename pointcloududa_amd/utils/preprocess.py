@@ -13,8 +13,7 @@ the convention (``include/pcuda_hip.h``) is this build's own, written after Open
 ``RescaleIntensityImageFilter``.  It is pinned by two independent restatements in a committed golden file
 (``scripts/make_preprocess_golden.py`` -> ``tests/golden/preprocess.npz``), and the device equals them bit for bit.  NaN in
 a volume is unsupported.  Not here: ``albumentations.CLAHE`` of the evaluation script (the L channel of LAB, a random clip
-limit), 16-bit CLAHE, the ``.npy`` path of ``read_nii_image.py`` (``ndimage.zoom(order=1)`` plus standardisation), and
-NIfTI / PNG file I/O."""
+limit), 16-bit CLAHE, and NIfTI / PNG file I/O (the ``.npy`` path of ``read_nii_image.py`` is ``utils/resample.py``)."""
 from __future__ import annotations
 
 import math
