@@ -631,6 +631,50 @@ int pcuda_zoom_standardize(const void* in, int dtype, int n, int sh, int sw, int
 size_t pcuda_zoom_labels_workspace_size(int zh, int zw, int crop);
 int pcuda_zoom_labels(const void* in, int dtype, int n, int sh, int sw, int zh, int zw, int crop, int num_classes,
                       const int* remap, int num_remap, uint8_t* out, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* test volumes of the evaluate scripts on the device (csrc/evalprep.hip): read_img's
+ * np.moveaxis(vol, 2, 0)[:, ::-1, ::-1], its 2.5-D stack and to_categorical (evaluate_mmwhs.py:19-29), the nimg.T of
+ * evaluate_mscmrseg.py:147, and the way back from a prediction to the volume's own axis order.  Casts only: numpy pins every bit.
+ *
+ * One index map, in ELEMENTS of the caller's array, serves all three:
+ *   src(z, r, c) = base + z sz + (flip_r ? r_size - 1 - r : r) sr + (flip_c ? c_size - 1 - c : c) sc
+ * C order, Fortran order and any permuted view are strides only (nimg.T swaps strides; moveaxis(2, 0)[:, ::-1, ::-1] is strides
+ * plus both flips).  base >= 0; a stride is positive on every axis longer than 1 (an axis of length 1 ignores its stride); the
+ * caller guarantees that every address of the map lies inside its array.  z, r, c (the sizes) >= 0; an empty volume returns 0
+ * without a launch.  All offsets are 64-bit.  The kernel form follows the strides: sc == 1: a pass along the rows, four
+ * columns per lane where c % 4 == 0 and pointers and pitches are aligned to the group; sr == 1 or sz == 1: a 64 x 64 tile
+ * through LDS, so that reads and writes both run along their own fastest axis; no unit stride: a plain gather / scatter.
+ *
+ * pcuda_volume_slices: in of PCUDA_VOL_F32 / _F64 / _I16 / _U8 -> contiguous fp32 out[z][window][r][c]; float64 rounds to
+ *   nearest even (numpy's astype(float32)).  window 1: the reoriented slices.  window 3: channel k of sample i is slice
+ *   (i + k - 1) mod z, wrapping at both ends (img[[i - 1, i, (i + 1) % D]]; z = 1 gives three copies of the slice).  Every
+ *   source value is read once and stored `window` times.
+ * pcuda_volume_labels: in of PCUDA_VOL_U8 / _I16 / _I32 / _F32 / _F64; remap: num_remap <= 8 (from, to) pairs (host array of
+ *   2 num_remap ints) applied in order, like chained np.where; -> uint8 labels[z][r][c] and, if onehot is not null, uint8
+ *   onehot[z][num_classes][r][c] in the same pass (num_classes 2..255).  A value that after the remap is not an integer in
+ *   [0, num_classes) (NaN included) is written as label 0 with an all-zero one-hot pixel and counted: the count is left in the
+ *   first 8 bytes of the workspace (uint64, integer atomics; the reference's to_categorical asserts there).
+ *   workspace: pcuda_volume_labels_workspace_size bytes, 8-byte aligned (an empty volume leaves it as it is).  raw != 0: labels is int32 labels[z][r][c] holding
+ *   int32(value) (truncation toward zero for floating point), no remap, no range check, no one-hot, no workspace needed (the
+ *   MS-CMRSeg ground truth keeps its 200 / 500 / 600 codes).
+ * pcuda_volume_restore: the inverse scatter: uint8 in[z][r][c] -> out (PCUDA_VOL_U8 or _I16) through the same map, so that
+ *   labels(restore(x)) == x; lut: null, or 256 int16 values ON THE DEVICE looked up first (MS-CMRSeg's 1 / 2 / 3 -> 200 / 500 /
+ *   600; cast to the output dtype).  Elements of out the map does not reach are left as they are.
+ *
+ * All three: never allocate, never synchronise, launch on s; in is never written and in == out is rejected; bad arguments are
+ * PCUDA_E_BADARG before any launch; the same bits from run to run. */
+#define PCUDA_VOL_F32 0
+#define PCUDA_VOL_I16 1
+#define PCUDA_VOL_U8 2
+#define PCUDA_VOL_F64 4
+#define PCUDA_VOL_I32 5
+int pcuda_volume_slices(const void* in, int dtype, long long base, long long sz, long long sr, long long sc, int z, int r, int c,
+                        int flip_r, int flip_c, int window, float* out, pcuda_stream_t s);
+size_t pcuda_volume_labels_workspace_size(void);
+int pcuda_volume_labels(const void* in, int dtype, long long base, long long sz, long long sr, long long sc, int z, int r, int c,
+                        int flip_r, int flip_c, int num_classes, const int* remap, int num_remap, int raw, void* labels,
+                        uint8_t* onehot, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+int pcuda_volume_restore(const uint8_t* in, int z, int r, int c, void* out, int out_dtype, long long base, long long sz,
+                         long long sr, long long sc, int flip_r, int flip_c, const int16_t* lut, pcuda_stream_t s);
 /* validation metrics (train_mscmrseg.py:85-92, metric.py:39-82): labels[n][i] = first channel holding the
  * per-pixel maximum of x[n][c][i] (fp32 logits, or a uint8 one-hot mask when x_is_u8); strides in elements */
 int pcuda_argmax_labels(const void* x, int x_is_u8, long long sn, long long sc, int n, int c, long long hw,

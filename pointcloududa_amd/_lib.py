@@ -143,6 +143,10 @@ _PROTOS = {
     "pcuda_zoom_standardize": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "pcuda_zoom_labels_workspace_size": (sz, [i32, i32, i32]),
     "pcuda_zoom_labels": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
+    "pcuda_volume_slices": (i32, [vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "pcuda_volume_labels_workspace_size": (sz, []),
+    "pcuda_volume_labels": (i32, [vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "pcuda_volume_restore": (i32, [vp, i32, i32, i32, vp, i32, i64, i64, i64, i64, i32, i32, vp, vp]),
     "pcuda_argmax_labels": (i32, [vp, i32, i64, i64, i32, i32, i64, vp, vp]),
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
     "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),

@@ -4,6 +4,8 @@ file I/O of ``evaluate_segmentation`` (NIfTI, cv2 resize, pandas) is not part of
 is its device-side core."""
 from __future__ import annotations
 
+import torch
+
 from .utils import metric as M
 
 CLASSES = [500, 600, 200]
@@ -55,3 +57,30 @@ def compute_metrics_on_files(gt, pred, ifhd=True, ifasd=True):
     res = metrics(gt, pred, ifhd=ifhd, ifasd=ifasd)
     print(FORMAT.format(*["{:.3f}".format(r) for r in res]))
     return res
+
+
+_CODES = [0, 200, 500, 600] + list(range(4, 256))
+_codes_lut = {}      # device -> the int16 [256] table 1 / 2 / 3 -> 200 / 500 / 600 (uploaded once: an upload makes the host wait)
+
+
+def read_labels(nimg):
+    """The ground truth of ``evaluate_mscmrseg.py:147``: ``nimg.T`` -- a NIfTI label volume ``[X,Y,Z]`` (device tensor of any
+    stride or numpy array, uploaded in its own memory order; uint8, int16, int32, float32 or float64) -> int32 ``[Z,Y,X]`` on the
+    device with the codes 200 / 500 / 600 kept, what ``validate.evaluate_volume(.., variant="mscmrseg")`` takes.  No resize."""
+    from . import kernels as K
+    from .utils import volume as VOL
+    t = VOL.as_device_volume(nimg, "read_labels")
+    if t.dtype not in (torch.uint8, torch.int16, torch.int32, torch.float32, torch.float64):
+        raise TypeError("read_labels: a uint8 / int16 / int32 / float32 / float64 volume, got %s" % (t.dtype,))
+    return K.volume_labels(t.permute(2, 1, 0), raw=True)[0]
+
+
+def restore_prediction(pred, nimg_shape):
+    """A uint8 prediction ``[Z,Y,X]`` with labels 1 / 2 / 3 (at the network's resolution) -> int16 of shape ``nimg_shape`` =
+    ``[X,Y,Z]``, in the file's axis order and memory order (first axis fastest), with the codes 200 / 500 / 600: the inverse of
+    ``read_labels``' orientation.  No resize."""
+    from .utils import volume as VOL
+    if torch.is_tensor(pred) and pred.is_cuda and pred.device not in _codes_lut:
+        _codes_lut[pred.device] = torch.tensor(_CODES, dtype=torch.int16).to(pred.device)
+    lut = _codes_lut.get(getattr(pred, "device", None), _CODES)
+    return VOL.restore_volume(pred, nimg_shape, flip=(False, False), transpose=True, lut=lut, dtype=torch.int16)

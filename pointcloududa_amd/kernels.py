@@ -1189,6 +1189,85 @@ def zoom_labels(labels, zoomed_hw, num_classes=4, remap=(), crop=0, out=None):
     return out, ws[:8].view(torch.int64)
 
 
+_VOL_DTYPES = {torch.float32: 0, torch.int16: 1, torch.uint8: 2, torch.float64: 4, torch.int32: 5}    # PCUDA_VOL_*
+_VOL_NAMES = {torch.float32: "float32", torch.int16: "int16", torch.uint8: "uint8", torch.float64: "float64", torch.int32: "int32"}
+
+
+def _volume_view(what, view, dtypes):
+    """the host checks of the volume wrappers: a 3-D device view [Z,R,C] of any stride -> (Z, R, C, sz, sr, sc)"""
+    if not torch.is_tensor(view) or view.dtype not in dtypes:
+        raise TypeError("%s: a %s volume, got %s" % (what, " / ".join(_VOL_NAMES[d] for d in dtypes), getattr(view, "dtype", type(view))))
+    if view.dim() != 3:
+        raise ValueError("%s: a [Z,R,C] view, got %d dimensions" % (what, view.dim()))
+    _req(view, view.dtype)
+    (z, r, c), (sz, sr, sc) = view.shape, view.stride()
+    if z * r * c and any(n > 1 and s <= 0 for n, s in ((z, sz), (r, sr), (c, sc))):
+        raise ValueError("%s: a positive stride on every axis longer than 1 (an expanded view?), got strides %r" % (what, (sz, sr, sc)))
+    if max(z, r, c) >= 2 ** 31:
+        raise ValueError("%s: sides below 2^31, got %r" % (what, (z, r, c)))
+    return z, r, c, sz, sr, sc
+
+
+def volume_slices(view, flip_r=False, flip_c=False, window=3, out=None):
+    """A fp32, float64, int16 or uint8 device view ``[Z,R,C]`` of ANY stride (``pcuda_volume_slices``) -> contiguous fp32
+    ``[Z,window,R,C]``: rows and columns mirrored where ``flip_r`` / ``flip_c``; ``window=3``: channel ``k`` of sample ``i`` is slice
+    ``(i + k - 1) mod Z`` (the reference's 2.5-D stack), ``window=1``: the slices themselves.  The input is never written."""
+    z, r, c, sz, sr, sc = _volume_view("volume_slices", view, (torch.float32, torch.float64, torch.int16, torch.uint8))
+    if window not in (1, 3):
+        raise ValueError("volume_slices: window is 1 or 3, got %r" % (window,))
+    out = _zoom_out("volume_slices", out, (z, window, r, c), torch.float32, view.device)
+    check(L.lib().pcuda_volume_slices(view.data_ptr(), _VOL_DTYPES[view.dtype], 0, sz, sr, sc, z, r, c, int(bool(flip_r)),
+                                      int(bool(flip_c)), window, out.data_ptr(), _stream()), "volume_slices")
+    return out
+
+
+def volume_labels(view, flip_r=False, flip_c=False, num_classes=5, remap=(), onehot=False, raw=False):
+    """A uint8, int16, int32, fp32 or float64 device view ``[Z,R,C]`` of any stride (``pcuda_volume_labels``): the ``(from, to)``
+    pairs of ``remap`` in order, then -> ``(labels uint8 [Z,R,C], onehot uint8 [Z,K,R,C] or None, counter)``; ``counter``: int64
+    ``[1]`` on the device, the number of values that are no integer in ``[0, num_classes)`` (written as background).  ``raw``:
+    ``(int32 [Z,R,C] holding the values themselves, None, None)``, no remap and no range check."""
+    z, r, c, sz, sr, sc = _volume_view("volume_labels", view, (torch.uint8, torch.int16, torch.int32, torch.float32, torch.float64))
+    pairs = [(int(a), int(b)) for a, b in remap]
+    if raw:
+        if onehot or pairs:
+            raise ValueError("volume_labels: raw output takes no remap and has no one-hot form")
+        out = torch.empty((z, r, c), dtype=torch.int32, device=view.device)
+        check(L.lib().pcuda_volume_labels(view.data_ptr(), _VOL_DTYPES[view.dtype], 0, sz, sr, sc, z, r, c, int(bool(flip_r)),
+                                          int(bool(flip_c)), 0, None, 0, 1, out.data_ptr(), None, None, 0, _stream()), "volume_labels")
+        return out, None, None
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 255:
+        raise ValueError("volume_labels: 2..255 classes, got %r" % (num_classes,))
+    if len(pairs) > 8:
+        raise ValueError("volume_labels: a remap table of at most 8 (from, to) pairs, got %d" % len(pairs))
+    lab = torch.empty((z, r, c), dtype=torch.uint8, device=view.device)
+    hot = torch.empty((z, num_classes, r, c), dtype=torch.uint8, device=view.device) if onehot else None
+    nbytes = L.lib().pcuda_volume_labels_workspace_size()
+    ws = torch.zeros(nbytes // 8, dtype=torch.int64, device=view.device)
+    table = (C.c_int * max(2 * len(pairs), 1))(*[v for p in pairs for v in p])
+    check(L.lib().pcuda_volume_labels(view.data_ptr(), _VOL_DTYPES[view.dtype], 0, sz, sr, sc, z, r, c, int(bool(flip_r)),
+                                      int(bool(flip_c)), num_classes, C.cast(table, C.c_void_p), len(pairs), 0, lab.data_ptr(),
+                                      _ptr(hot), ws.data_ptr(), nbytes, _stream()), "volume_labels")
+    return lab, hot, ws[:1]
+
+
+def volume_restore(pred, out_view, flip_r=False, flip_c=False, lut=None):
+    """The inverse scatter (``pcuda_volume_restore``): uint8 ``pred [Z,R,C]`` into ``out_view``, a uint8 or int16 device view
+    ``[Z,R,C]`` of any stride over the caller's array, through the same map, so that ``volume_labels(out_view) == pred``;
+    ``lut``: an int16 ``[256]`` device table looked up first.  -> ``out_view``."""
+    _req(pred, torch.uint8)
+    z, r, c, sz, sr, sc = _volume_view("volume_restore", out_view, (torch.uint8, torch.int16))
+    if tuple(pred.shape) != (z, r, c):
+        raise ValueError("volume_restore: pred %r does not match the view %r" % (tuple(pred.shape), (z, r, c)))
+    if lut is not None:
+        _req(lut, torch.int16)
+        if tuple(lut.shape) != (256,) or not lut.is_contiguous():
+            raise ValueError("volume_restore: lut is a contiguous int16 [256] tensor")
+    pred = pred.contiguous()
+    check(L.lib().pcuda_volume_restore(pred.data_ptr(), z, r, c, out_view.data_ptr(), _VOL_DTYPES[out_view.dtype], 0, sz, sr, sc,
+                                       int(bool(flip_r)), int(bool(flip_c)), _ptr(lut), _stream()), "volume_restore")
+    return out_view
+
+
 def argmax_labels(x):
     """[N,C,H,W] fp32 logits or uint8 one-hot -> uint8 label map [N,H,W]: first channel holding the maximum (a NaN in
     any channel: label 0, as the reference's np.max leaves no channel equal to it)."""

@@ -143,3 +143,36 @@ def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd
         return mod.metrics_from_rows_ext(rows, ifhd, ifasd)
     rows = M.class_metrics(M.to_device(gt_labels, dev), pred, mod.CLASSES).tolist()        # one sync
     return mod.metrics_from_rows(rows, ifhd, ifasd)
+
+
+@torch.no_grad()
+def evaluate_volume_rows(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, variant: str = "mmwhs", extended: bool = False):
+    """``evaluate_volume`` up to its synchronisation: the same stages on the same kernels, returning the DEVICE rows
+    (``M.class_metrics`` / ``M.class_metrics_ext`` of the variant's classes, float64) that ``metrics_from_rows`` /
+    ``metrics_from_rows_ext`` turn into ``evaluate_volume``'s list.  Nothing synchronises, so a loop over patients can keep its
+    rows on the device and read them all at once (``evaluate_mmwhs.evaluate_segmentation``)."""
+    if variant not in ("mmwhs", "mscmrseg"):
+        raise ValueError("evaluate_volume_rows: variant 'mmwhs' or 'mscmrseg'")
+    dev = next(seg_model.parameters()).device
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    x = x.to(dev)
+    was_training = seg_model.training
+    seg_model.eval()
+    try:
+        preds = []
+        for i in range(0, x.shape[0], bs):
+            out = seg_model(x[i:i + bs])
+            preds.append(M.argmax_labels(out[0] if isinstance(out, tuple) else out))
+    finally:
+        seg_model.train(was_training)
+    pred = torch.cat(preds)
+    if klc:
+        pred = U.keep_largest_connected_components(pred)
+    mod = EW if variant == "mmwhs" else EM
+    if variant == "mscmrseg":
+        lut = torch.arange(256, dtype=torch.int32, device=dev)
+        lut[1:4] = torch.tensor([200, 500, 600], dtype=torch.int32, device=dev)
+        pred = lut[pred.long()]
+    if extended:
+        return M.class_metrics_ext(M.to_device(gt_labels, dev), pred, mod.CLASSES)
+    return M.class_metrics(M.to_device(gt_labels, dev), pred, mod.CLASSES)
