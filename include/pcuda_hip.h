@@ -510,6 +510,39 @@ size_t pcuda_stylize_workspace_size(int b, int h, int w, int c);
 int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode, const int* iarg,
                   const double* farg, const double* table, const unsigned long long* seed, void* workspace,
                   size_t workspace_bytes, pcuda_stream_t s);
+/* device-side CropAndPad with every defined mode of numpy.pad: iaa.CropAndPad(percent=(-0.05, 0.1), pad_mode=ia.ALL,
+ * pad_cval=(0, 255)) of both heavy recipes (data_generator_mscmrseg.py:28-32, 91-95; csrc/croppad.hip) on uint8 images
+ * [b][h][w][c], c = 1..4, h, w >= 2, and optional int32 labels [b][h][w], as a per-sample program in device memory: opcode [b]
+ * (0 copy, 1 crop-and-pad; anything else copies) and iarg [b][6] = (top, right, bottom, left, mode, cval): signed pixels per
+ * side, positive pads (at most 64), negative crops; mode PCUDA_PAD_*; cval 0..255.  For a live sample
+ *   xc = x[ct : h - cb, cl : w - cr] (the negative sides), I = numpy.pad(xc, ((pt, pb), (pl, pr), (0, 0)), mode), Hi x Wi, with
+ *   constant_values = cval (constant), end_values = cval (linear_ramp), the statistics over the whole axis; bit for bit numpy's
+ *   (tests/golden/croppad.npz): axis 0 is padded first and axis 1 on the padded array (a corner is a statistic of statistics,
+ *   or a ramp whose edge value is a ramp); mean and median round half to even; a ramp is floor(end + k step), k = 0 outermost,
+ *   step = (edge - end) / width, unless some edge value of that side (all columns and channels of the numpy call) equals end:
+ *   then floor(end + (k / width) (edge - end)), numpy.linspace's any_step_zero branch
+ *   out = I resized to h x w: ax = Wi / w, sx = (x + 0.5) ax - 0.5 (float64, every operation rounded on its own), x0 = floor(sx),
+ *   wx1 = sx - x0, neighbour indices clamped into I, y likewise; v = 0; v += p00 wy0 wx0; v += p01 wy0 wx1; v += p10 wy1 wx0;
+ *   v += p11 wy1 wx1; floor(v + 0.5) clipped to [0, 255].  Hi == h and Wi == w give I itself
+ *   labels: the same crop, constant 0, the texel at floor(s + 0.5), whatever the image's mode is
+ * I is never materialised.  Sides and modes are clamped on the device before any load (the host validates programs).  The
+ * result depends on (image, program) only.  `in` (labels_in) is never written and in == out is rejected; labels_in and
+ * labels_out are both NULL or both given.  workspace: pcuda_crop_pad_workspace_size bytes, 16-byte aligned, always needed (per
+ * sample and channel the column and row statistics, per sample the four ramp flags); 0 for dims the entry point refuses.
+ * Three launches; nothing allocates or synchronises. */
+#define PCUDA_PAD_CONSTANT 0
+#define PCUDA_PAD_EDGE 1
+#define PCUDA_PAD_LINEAR_RAMP 2
+#define PCUDA_PAD_MAXIMUM 3
+#define PCUDA_PAD_MEAN 4
+#define PCUDA_PAD_MEDIAN 5
+#define PCUDA_PAD_MINIMUM 6
+#define PCUDA_PAD_REFLECT 7
+#define PCUDA_PAD_SYMMETRIC 8
+#define PCUDA_PAD_WRAP 9
+size_t pcuda_crop_pad_workspace_size(int b, int h, int w, int c);
+int pcuda_crop_pad(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w, int c,
+                   const int* opcode, const int* iarg, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* device-side histogram matching: match_histograms(img, reference_img, multichannel=True) of the MM-WHS generator
  * (data_generator_mmwhs.py:174-176, 236-237; train_mmwhs.py -mh) on images [b][h][w][c], c = 1..4, fp32 or uint8 (is_u8),
  * against a template that is fixed for the run and arrives as tables in device memory: tvalues / tquantiles [c][tstride]

@@ -1027,6 +1027,45 @@ def stylize(images_u8, opcode, iarg, farg, table, seed, out=None):
     return out
 
 
+def crop_pad(images_u8, labels, opcode, iarg, out=None, labels_out=None):
+    """CropAndPad with numpy's pad modes over uint8 ``[B,H,W,C]`` images and optional int32 ``[B,H,W]`` labels (``pcuda_crop_pad``):
+    ``opcode`` int32 ``[B]`` (0 copy, 1 crop-and-pad), ``iarg`` int32 ``[B,6]`` = (top, right, bottom, left, mode, cval), both on the
+    device -> ``(images, labels or None)``, new tensors unless ``out`` / ``labels_out`` are given (the inputs are never written)."""
+    _req(images_u8, torch.uint8)
+    if images_u8.dim() != 4:
+        raise TypeError("crop_pad: uint8 [B,H,W,C] images")
+    images_u8 = images_u8.contiguous()
+    b, h, w, c = images_u8.shape
+    _req(opcode, torch.int32); _req(iarg, torch.int32)
+    if tuple(opcode.shape) != (b,) or tuple(iarg.shape) != (b, 6):
+        raise ValueError("crop_pad: the program's arrays do not match the batch of %d" % b)
+    if labels is not None:
+        _req(labels, torch.int32)
+        labels = labels.contiguous()
+        if tuple(labels.shape) != (b, h, w):
+            raise ValueError("crop_pad: label shape %r does not match the images" % (tuple(labels.shape),))
+        if labels_out is None:
+            labels_out = torch.empty_like(labels)
+        else:
+            _req(labels_out, torch.int32)
+            if tuple(labels_out.shape) != (b, h, w) or not labels_out.is_contiguous():
+                raise ValueError("crop_pad: labels_out must be a contiguous int32 [B,H,W] tensor")
+    else:
+        labels_out = None
+    if out is None:
+        out = torch.empty_like(images_u8)
+    else:
+        _req(out, torch.uint8)
+        if out.shape != images_u8.shape or not out.is_contiguous():
+            raise ValueError("crop_pad: out must be a contiguous uint8 tensor of the images' shape")
+    nbytes = L.lib().pcuda_crop_pad_workspace_size(b, h, w, c)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    check(L.lib().pcuda_crop_pad(images_u8.data_ptr(), out.data_ptr(), _ptr(labels), _ptr(labels_out), b, h, w, c,
+                                 opcode.contiguous().data_ptr(), iarg.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()),
+          "crop_pad")
+    return out, labels_out
+
+
 def match_hist(images, tvalues, tquantiles, tlen, out=None):
     """Histogram matching of ``[B,H,W,C]`` fp32 or uint8 images against a template's tables (``pcuda_match_hist``): ``tvalues`` and
     ``tquantiles`` float64 ``[C,T]`` (per channel the template's sorted distinct values and ``cumsum(counts) / M``), ``tlen`` int32

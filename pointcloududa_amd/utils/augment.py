@@ -28,7 +28,10 @@ pipeline (``CropAndPad``, the +/-45 degree ``Affine`` with every border mode, el
 images and the masks in front of the f6 launch.  ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
 ``AddToHueAndSaturation`` live in ``utils/stylize.py`` (f9) and are re-exported here as well: the presets
 ``"heavy_full_device"`` and ``"mscmrseg_aug2_full_device"`` hold all fifteen / twelve ``SomeOf`` entries of the two recipes, while
-``"heavy_device"`` and ``"mscmrseg_aug2_device"`` keep drawing what they drew without the three.  Histogram matching against a
+``"heavy_device"`` and ``"mscmrseg_aug2_device"`` keep drawing what they drew without the three.  ``CropAndPad`` with all ten
+modes of ``numpy.pad`` (``pad_mode=ia.ALL``) lives in ``utils/croppad.py`` (f14) and is re-exported here (``CropPadProgram``,
+``crop_pad_aug``, ``MODE_NAMES``): the presets ``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` are the two full
+recipes with it.  Histogram matching against a
 fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
 ``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
 in front of everything else."""
@@ -50,6 +53,8 @@ from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, Hea
 from .stylize import (AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, directed_edge_weights, edge_detect_weights,  # noqa: F401
                       sample_style_program, simplex_grid, stylize_aug, superpixel_grid, upload_style_program)
 from .histmatch import HistReference, match_histograms, reference_tables  # noqa: F401
+from .croppad import (AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, MODE_NAMES, CropPadProgram, crop_pad_aug,  # noqa: F401
+                      upload_crop_pad_program)
 
 OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
 
@@ -318,7 +323,8 @@ class AugmentedBatches:
     (``DeviceBatches``); the parameters of each batch are drawn from ``rng`` on the host and ride along through pinned,
     non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
-    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"`` or their ``_full_`` twins) ``preset`` must
+    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"``, their ``_full_`` or
+    their ``_refpad_`` twins) ``preset`` must
     be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters.  With
     ``match_hist_reference`` (an ``[H,W,C]`` numpy image) its tables are built and uploaded once (``match_hist``) and every batch
     is histogram-matched against it first."""
@@ -330,7 +336,8 @@ class AugmentedBatches:
         if preset == "heavy" or photometric_preset == "heavy" or heavy_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
         if heavy_preset is not None:
-            if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET, HEAVY_FULL_PRESET, AUG2_FULL_PRESET):
+            if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET, HEAVY_FULL_PRESET, AUG2_FULL_PRESET,
+                                    HEAVY_REFPAD_PRESET, AUG2_REFPAD_PRESET):
                 raise ValueError("unknown heavy preset %r" % (heavy_preset,))
             if preset is not None or photometric_preset is not None:
                 raise ValueError("AugmentedBatches: a heavy preset is the whole recipe (preset and photometric_preset must be None)")

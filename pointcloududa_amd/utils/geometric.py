@@ -32,9 +32,11 @@ interpolation order 0 / 1, border mode, cval 0..255, one opcode argument), ``far
 
 imgaug / skimage / cv2 are not vendored by the reference: parity with imgaug is unpinned, the convention is this build's own
 and is pinned by ``tests/golden/geometric.npz`` (``scripts/make_geometric_golden.py``: a scipy ``map_coordinates`` and a
-plain-numpy restatement).  Two divergences from the reference's recipe: numpy's statistical pad modes (``linear_ramp``,
-``maximum``, ``mean``, ``median``, ``minimum``) are not built, so ``CropAndPad`` draws from the five border modes above, and
-imgaug's parameter stream is not reproduced.  NOT built: interpolation orders above 1; the string ``"heavy"``
+plain-numpy restatement).  One divergence from the reference's recipe is left: imgaug's parameter stream is not reproduced.
+``CropAndPad`` with all ten modes of ``numpy.pad`` (``pad_mode=ia.ALL``: the five above plus ``linear_ramp``, ``maximum``,
+``mean``, ``median``, ``minimum``) lives in ``utils/croppad.py`` (f14) as a program of its own: the presets
+``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` of ``sample_heavy_plan`` draw it, while ``set_crop_and_pad`` here
+and the four older presets keep the five modes above.  NOT built: interpolation orders above 1; the string ``"heavy"``
 keeps raising ``NotImplementedError``.  ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
 ``AddToHueAndSaturation`` live in ``utils/stylize.py`` (f9): the presets ``"heavy_full_device"`` and
 ``"mscmrseg_aug2_full_device"`` of ``sample_heavy_plan`` interleave them with the entries of this file and f7's."""
@@ -49,6 +51,7 @@ import torch
 from .. import kernels as K
 from . import photometric as P
 from . import stylize as St
+from .croppad import AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, CropPadProgram, crop_pad_aug
 from .photometric import PhotoProgram, gaussian_weights, photometric_aug
 from .stylize import AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, stylize_aug
 
@@ -309,6 +312,11 @@ _PRESETS = {
         block=_FULL_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
     # data_generator_mscmrseg.py:89-130, all twelve
     AUG2_FULL_PRESET: dict(outer=(("g", ENTRY_CROP_AND_PAD), "block"), block=_FULL_BLOCK),
+    # the two full recipes with CropAndPad over all ten modes of numpy.pad, a CropPadProgram stage of its own (f14)
+    HEAVY_REFPAD_PRESET: dict(
+        outer=(("g", ENTRY_FLIPLR), ("g", ENTRY_FLIPUD), ("c", ENTRY_CROP_AND_PAD), ("g", ENTRY_AFFINE), "block"),
+        block=_FULL_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
+    AUG2_REFPAD_PRESET: dict(outer=(("c", ENTRY_CROP_AND_PAD), "block"), block=_FULL_BLOCK),
 }
 _SOMETIMES = {("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE), ("s", St.ENTRY_SUPERPIXELS)}
 _OUTER_P = {ENTRY_FLIPLR: FLIP_LR_P, ENTRY_FLIPUD: FLIP_UD_P, ENTRY_CROP_AND_PAD: SOMETIMES_P, ENTRY_AFFINE: SOMETIMES_P}
@@ -438,7 +446,9 @@ def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int
     five) and, out of the ``SomeOf((0, 5))`` block of twelve built entries, ``sometimes`` ElasticTransformation (alpha
     0.5-3.5, sigma 0.25), PiecewiseAffine (G = 4, jitter N(0, scale size), scale 0.01-0.05) and PerspectiveTransform (jitter
     N(0, scale), scale 0.01-0.1, clipped to 0.45), in one random order per batch.  ``"mscmrseg_aug2_device"``
-    (``:89-130``), 1 slot: ``sometimes`` CropAndPad.  imgaug's own parameter stream is not reproduced (parity unpinned)."""
+    (``:89-130``), 1 slot: ``sometimes`` CropAndPad.  On ``"heavy_refpad_device"`` the six entries without CropAndPad (which is
+    a ``CropPadProgram`` there, f14); ``"mscmrseg_aug2_refpad_device"`` holds no geometric entry (0 slots).  imgaug's own
+    parameter stream is not reproduced (parity unpinned)."""
     spec = _check_preset(preset)
     entries, on = _select(batch, spec, rng)
     d = _draw_geo(batch, rng, h, w)
@@ -455,10 +465,11 @@ def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int
 
 @dataclass
 class HeavyPlan:
-    """The ordered stages of one batch: ``PhotoProgram``, ``GeoProgram`` and (f9) ``StyleProgram`` stages, no two neighbours of
-    one kind; every stage covers the whole batch (a sample without an active entry in a stage holds NOPs there)."""
+    """The ordered stages of one batch: ``PhotoProgram``, ``GeoProgram``, (f9) ``StyleProgram`` and (f14) ``CropPadProgram``
+    stages, no two neighbours of one kind; every stage covers the whole batch (a sample without an active entry in a stage
+    holds NOPs there)."""
     batch: int
-    stages: List[Union[PhotoProgram, GeoProgram, StyleProgram]] = field(default_factory=list)
+    stages: List[Union[PhotoProgram, GeoProgram, StyleProgram, CropPadProgram]] = field(default_factory=list)
 
     def is_identity(self) -> bool:
         return all(st.is_identity() for st in self.stages)
@@ -476,11 +487,17 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
 
     ``"heavy_full_device"`` and ``"mscmrseg_aug2_full_device"`` (f9): the same two recipes with all fifteen / twelve ``SomeOf``
     entries -- ``sometimes`` Superpixels, SimplexNoiseAlpha and AddToHueAndSaturation (``utils/stylize.py``) sit in the block
-    at the reference's list positions, and consecutive stylize entries form one ``StyleProgram``."""
+    at the reference's list positions, and consecutive stylize entries form one ``StyleProgram``.
+
+    ``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` (f14): the two full recipes with CropAndPad as a
+    ``CropPadProgram`` stage of its own (``utils/croppad.py``), its mode uniform over the ten of ``numpy.pad``.  Everything the
+    ``_full_`` twin draws is drawn in the same order, then one ``rng.integers(0, 10, batch)`` for the mode; the sides and cval
+    are ``_draw_geo``'s ``crop`` / ``crop_cval`` (its ``crop_mode`` draw is consumed and unused)."""
     spec = _check_preset(preset)
     entries, on = _select(batch, spec, rng)
     dg, dp = _draw_geo(batch, rng, h, w), _draw_photo(batch, rng)
     ds = St.draw_style(batch, rng) if any(e[0] == "s" for e in entries) else None
+    pad_mode = rng.integers(0, 10, batch) if any(e[0] == "c" for e in entries) else None
     used = [k for k in range(len(entries)) if on[:, k].any()]      # (an entry nobody drew does not split a stage)
     entries, on = [entries[k] for k in used], on[:, used]
     plan = HeavyPlan(batch)
@@ -492,7 +509,10 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
             e += 1
         used = int(on[:, k:e].sum(1).max()) if batch else 0
         if used:
-            prog = {"p": PhotoProgram, "g": GeoProgram, "s": StyleProgram}[kind].identity(batch, used)
+            if kind == "c":
+                prog = CropPadProgram.identity(batch)
+            else:
+                prog = {"p": PhotoProgram, "g": GeoProgram, "s": StyleProgram}[kind].identity(batch, used)
             for i in range(batch):
                 s = 0
                 for q in range(k, e):
@@ -501,6 +521,10 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
                             _encode_photo(prog, i, s, entries[q][1], dp)
                         elif kind == "s":
                             St.encode_style(prog, i, s, entries[q][1], ds, h, w)
+                        elif kind == "c":
+                            t, r, bt, l = dg["crop"][i]
+                            prog.set_crop_and_pad(i, crop_pad_pixels(t, h), crop_pad_pixels(r, w), crop_pad_pixels(bt, h),
+                                                  crop_pad_pixels(l, w), int(pad_mode[i]), int(dg["crop_cval"][i]))
                         else:
                             _encode_geo(prog, i, s, entries[q][1], dg, h, w)
                         s += 1
@@ -525,6 +549,9 @@ def heavy_aug(images: torch.Tensor, masks: Optional[torch.Tensor], plan: Optiona
             images = stylize_aug(images, stage)
         elif isinstance(stage, GeoProgram):
             images, masks = geometric_aug(images, masks, stage)
+        elif isinstance(stage, CropPadProgram):
+            images, masks = crop_pad_aug(images, masks, stage)
         else:
-            raise TypeError("heavy_aug: a stage is a PhotoProgram, a GeoProgram or a StyleProgram, got %s" % type(stage).__name__)
+            raise TypeError("heavy_aug: a stage is a PhotoProgram, a GeoProgram, a StyleProgram or a CropPadProgram, got %s"
+                            % type(stage).__name__)
     return images, masks
