@@ -19,7 +19,8 @@ What numpy.pad does (checked against numpy 2.2.6), and the restatement follows:
 
     python scripts/make_croppad_golden.py            # writes the file
     python scripts/make_croppad_golden.py --check    # regenerates and compares the array contents with the file
-    python scripts/make_croppad_golden.py --digests  # writes tests/golden/heavy_plan_digests.json (see plan_digest)"""
+    python scripts/make_croppad_golden.py --digests  # writes tests/golden/heavy_plan_digests.json (see plan_digest)
+    python scripts/make_croppad_golden.py --edges    # writes tests/golden/croppad_edges.json (see edges)"""
 import hashlib
 import json
 import math
@@ -346,7 +347,40 @@ def digests():
                 for s in range(DIGEST_SEEDS)] for p in DIGEST_PRESETS}
 
 
+# ---------------------------------------------------------------------------------------------- the edge shapes
+EDGES = os.path.join(ROOT, "tests", "golden", "croppad_edges.json")
+
+
+def edges():
+    """tests/croppad_edge_cases.py's table (shapes above one tile, C = 2 and 4, lines above 64, pads of 64, 256 x 256): per
+    row the sha256 of the restated output, per side set that of the restated labels.  Nothing is recorded unless I equals
+    numpy.pad bit for bit and, below 100 x 100, the two restatements of the resize agree"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("croppad_edge_cases", os.path.join(ROOT, "tests", "croppad_edge_cases.py"))
+    t = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(t)
+    cases = {}
+    for cs in t.CASES:
+        x = t.image_of(cs)
+        for row, (big, res) in zip(cs.rows, t.expected_rows(cs)):
+            pt, pb, pl, pr = split_sides(cs.h, cs.w, *row[:4])[4:]
+            ref = numpy_pad(crop(x, *row[:4]), pt, pb, pl, pr, row[4], row[5])
+            if big.dtype != ref.dtype or big.shape != ref.shape or not np.array_equal(big, ref):
+                raise SystemExit("the restatement differs from numpy.pad on %s, row %r" % (cs.name, row))
+            if max(cs.h, cs.w) < t.LOOPS_BELOW and not np.array_equal(res, resize_loops(ref, cs.h, cs.w)):
+                raise SystemExit("the two restatements of the resize differ on %s, row %r" % (cs.name, row))
+        cases[cs.name] = t.digests_of(cs)
+    return {"numpy_version": np.__version__, "cases": cases}
+
+
 def main():
+    if "--edges" in sys.argv:
+        data = edges()
+        with open(EDGES, "w") as fh:
+            json.dump(data, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+        print("wrote %s: %d bytes" % (EDGES, os.path.getsize(EDGES)))
+        return
     if "--digests" in sys.argv:
         with open(DIGESTS, "w") as fh:
             json.dump(digests(), fh, indent=1, sort_keys=True)
