@@ -718,6 +718,30 @@ int pcuda_label_dice(const uint8_t* pred, const uint8_t* gt, long long numel, in
                      size_t workspace_bytes, pcuda_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * native-size evaluation of MS-CMRSeg (evaluate_mscmrseg.py:139-145; utils/utils.py:83-92 resize_volume =
+ * cv2.resize(.., INTER_AREA) per fp32 plane).  The rule is this build's own, written after OpenCV's resize.cpp; its parity
+ * with OpenCV is NOT pinned (DESIGN.md f15 states the rule).  Per axis, source size S, destination size D, scale = S / D and
+ * inv = D / S in fp64; every fp32 operation rounded on its own.
+ *   scale_x >= 1 and scale_y >= 1: the area table per axis (f1 = d * scale, f2 = f1 + scale, cell = min(scale, S - f1),
+ *     s1 = ceil(f1), s2 = min(floor(f2), S - 1), s1 = min(s1, s2); tap s1 - 1 with (s1 - f1) / cell if s1 - f1 > 1e-3, taps
+ *     s1 .. s2 - 1 with 1 / cell, tap s2 with min(min(f2 - s2, 1), cell) / cell if f2 - s2 > 1e-3; weights rounded to fp32);
+ *     per source row in order the row sum h = w0 * v0, h += w * v over the taps in order, then out = wy0 * h0, out += wy * h.
+ *   otherwise (an axis enlarges) two-tap linear on both axes: sx = floor(d * scale), fx = (d + 1) - (sx + 1) * inv, fx = 0 if
+ *     fx <= 0 else fx - floor(fx); sx >= S - 1: sx = S - 1, fx = 0; h = v[sx] * (float)(1 - fx) + v[sx + 1] * (float)fx, h =
+ *     v[sx] when fx == 0; the rows are combined the same way.
+ * pcuda_area_resize: in[n] at in + n * sn, rows sr elements apart, unit column stride, [sh][sw] -> out[n][dh][dw] dense.
+ * pcuda_reconstruct_resize_argmax: logits[n][c][h][w] (strides sn, sc, sr in elements, unit column stride; c 1..8, h = w =
+ *   2 * crop) pasted at origin / 2 - crop of a zero origin x origin canvas that is never written, each class plane resized to
+ *   [dh][dw] by the rule above, labels[n][dh][dw] = first class holding the maximum, 0 when any class is NaN (the rule of
+ *   pcuda_argmax_labels); the resized planes are never written either.
+ * Both: every size 1..16384, n <= 65535; never allocate, never synchronise, launch on s; bad arguments are PCUDA_E_BADARG
+ * before any launch; the same bits from run to run. */
+int pcuda_area_resize(const float* in, long long sn, long long sr, int n, int sh, int sw, float* out, int dh, int dw,
+                      pcuda_stream_t s);
+int pcuda_reconstruct_resize_argmax(const float* logits, long long sn, long long sc, long long sr, int n, int c, int h, int w,
+                                    int crop, int origin, uint8_t* labels, int dh, int dw, pcuda_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * evaluation metrics (utils/metric.py evaluate / metrics2, evaluate_*.py; medpy.metric.binary dc / hd / asd and
  * utils.py keep_largest_connected_components) on integer label volumes [z][h][w] (ndim 2: z = 1, [h][w]), uint8 or
  * int32 (labels_i32); every dimension 1..16384, z*h*w < 2^31.

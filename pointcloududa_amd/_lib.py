@@ -151,6 +151,8 @@ _PROTOS = {
     "pcuda_volume_restore": (i32, [vp, i32, i32, i32, vp, i32, i64, i64, i64, i64, i32, i32, vp, vp]),
     "pcuda_argmax_labels": (i32, [vp, i32, i64, i64, i32, i32, i64, vp, vp]),
     "pcuda_label_dice": (i32, [vp, vp, i64, i32, vp, vp, sz, vp]),
+    "pcuda_area_resize": (i32, [vp, i64, i64, i32, i32, i32, vp, i32, i32, vp]),
+    "pcuda_reconstruct_resize_argmax": (i32, [vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
     "pcuda_surface_metrics_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),
     "pcuda_surface_metrics": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
     "pcuda_surface_metrics_ext_workspace_size": (sz, [i32, i32, i32, i32, i32, vp]),

@@ -1323,6 +1323,63 @@ def argmax_labels(x):
     return lab
 
 
+def _out_size(name, h, w):
+    for v in (h, w):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16384:
+            raise ValueError("%s: the output size (h, w) = (%r, %r) must be integers in 1..16384" % (name, h, w))
+
+
+def area_resize(x, h, w):
+    """``pcuda_area_resize``: fp32 planes ``[N,S_h,S_w]`` (or one plane ``[S_h,S_w]``; unit column stride, any row and plane
+    stride) -> fp32 ``[N,h,w]`` by the build's INTER_AREA rule (parity with OpenCV not pinned): the area table
+    where both axes shrink or stay, two taps per axis where one enlarges."""
+    _out_size("area_resize", h, w)
+    if not torch.is_tensor(x) or x.dim() not in (2, 3):
+        raise ValueError("area_resize: fp32 planes [N,H,W] or one plane [H,W]")
+    _req(x)
+    v = x.unsqueeze(0) if x.dim() == 2 else x
+    n, sh, sw = v.shape
+    if sh < 1 or sw < 1:
+        raise ValueError("area_resize: empty planes")
+    if v.stride(2) != 1 or v.stride(1) < sw or v.stride(0) < 0 or (n > 1 and v.stride(0) == 0):
+        v = v.contiguous()
+    out = torch.empty((n, h, w), dtype=torch.float32, device=x.device)
+    for i in range(0, n, 65535):
+        m = min(65535, n - i)
+        check(L.lib().pcuda_area_resize(v[i:i + m].data_ptr(), v.stride(0), v.stride(1), m, sh, sw, out[i:i + m].data_ptr(), h, w,
+                                        _stream()), "area_resize")
+    return out[0] if x.dim() == 2 else out
+
+
+def reconstruct_resize_argmax(logits, h, w, crop_size=112, origin_size=256):
+    """``pcuda_reconstruct_resize_argmax``: fp32 logits ``[N,C,2 crop,2 crop]`` as the network leaves them (C <= 8) -> uint8
+    labels ``[N,h,w]``: ``reconstuct_volume`` into a zero ``origin_size`` canvas, ``resize_volume`` of every class plane to
+    ``(h, w)`` and ``argmax`` (``evaluate_mscmrseg.py:139-145``) in one pass; neither the canvas nor the resized planes are
+    written.  Ties and NaN as ``argmax_labels``."""
+    _out_size("reconstruct_resize_argmax", h, w)
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise ValueError("reconstruct_resize_argmax: fp32 logits [N,C,H,W]")
+    n, c, lh, lw = logits.shape
+    if not 1 <= c <= 8:
+        raise ValueError("reconstruct_resize_argmax: 1..8 classes, got %d" % c)
+    o = int(origin_size / 2)
+    if crop_size < 1 or o - crop_size < 0 or o + crop_size > origin_size:
+        raise ValueError("reconstruct_resize_argmax: the window %d +- %d does not fit a canvas of %d" % (o, crop_size, origin_size))
+    if (lh, lw) != (2 * crop_size, 2 * crop_size):
+        raise ValueError("reconstruct_resize_argmax: logits of %dx%d, the window is %dx%d" % (lh, lw, 2 * crop_size, 2 * crop_size))
+    _req(logits)
+    if logits.stride(3) != 1 or logits.stride(2) < lw or min(logits.stride(0), logits.stride(1)) < 0 or \
+            (c > 1 and logits.stride(1) == 0) or (n > 1 and logits.stride(0) == 0):
+        logits = logits.contiguous()
+    lab = torch.empty((n, h, w), dtype=torch.uint8, device=logits.device)
+    for i in range(0, n, 65535):
+        m = min(65535, n - i)
+        check(L.lib().pcuda_reconstruct_resize_argmax(logits[i:i + m].data_ptr(), logits.stride(0), logits.stride(1), logits.stride(2),
+                                                      m, c, lh, lw, crop_size, origin_size, lab[i:i + m].data_ptr(), h, w, _stream()),
+              "reconstruct_resize_argmax")
+    return lab
+
+
 def label_dice(pred_labels, gt_labels, num_classes):
     """per-class Dice (medpy dc) of two uint8 label maps -> fp32 [num_classes] on the device"""
     _req(pred_labels, torch.uint8); _req(gt_labels, torch.uint8)

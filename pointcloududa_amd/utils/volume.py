@@ -8,8 +8,9 @@ read as it lies -- C order, Fortran order (what a NIfTI reader returns) or any p
 result is written along its own fastest axis.  ``restore_volume`` is the way back from a prediction ``[D,H,W]`` to the volume's
 own axis order.  Nothing is computed but casts, so numpy pins every output bit for bit.
 
-Not here: NIfTI and CSV file I/O (the caller brings the array), the cv2 ``INTER_AREA`` resize and ``reconstuct_volume`` of the
-MS-CMRSeg script, slice axes other than the one given by strides, windows other than 1 and 3."""
+Not here: NIfTI and CSV file I/O (the caller brings the array), slice axes other than the one given by strides, windows other
+than 1 and 3.  The ``INTER_AREA`` resize and ``reconstuct_volume`` of the MS-CMRSeg script live in ``csrc/area_resize.hip``
+(``utils.utils.resize_volume``, ``evaluate_mscmrseg.evaluate_segmentation``)."""
 from __future__ import annotations
 
 from typing import Sequence, Tuple

@@ -106,19 +106,20 @@ def valid_model_with_one_dataset(seg_model, batches: Iterable, d4: bool = True, 
     return {"dice": host[0], "loss": host[1], "valid_vert_loss": host[2], "hd": float(np.mean(np.array(hd_list)))}
 
 
-@torch.no_grad()
-def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd: bool = True, ifasd: bool = True,
-                    variant: str = "mmwhs", extended: bool = False):
-    """The device-side core of ``evaluate_segmentation`` (``evaluate_mmwhs.py:118-132``; ``evaluate_mscmrseg.py:132-169``
-    without its crop / resize): eval forward in batches of ``bs`` -> argmax -> ``keep_largest_connected_components``
-    (``klc``) -> the variant's ``metrics`` list ([dice, hd, asd] per class), with one synchronisation per volume.
-    ``x``: the volume's slices [Z,C,H,W] (fp32, device tensor or numpy); ``gt_labels``: its label volume [Z,H,W] (MM-WHS
-    1..4; MS-CMRSeg codes 200 / 500 / 600, which the predicted labels 1 / 2 / 3 are mapped to after ``klc``).
-    ``extended``: [dice, hd, asd, hd95, assd] per class (``metrics_from_rows_ext``) from the one call per volume to the
-    extended kernel; the first three are the bits the default call returns."""
-    if variant not in ("mmwhs", "mscmrseg"):
-        raise ValueError("evaluate_volume: variant 'mmwhs' or 'mscmrseg'")
-    dev = next(seg_model.parameters()).device
+def _native_size(name, native_shape, variant):
+    """``native_shape = (X, Y)``, the first two axes of the label file -> the (rows, columns) = (Y, X) of a predicted slice"""
+    if native_shape is None:
+        return None
+    if variant != "mscmrseg":
+        raise ValueError("%s: native_shape is the resize of evaluate_mscmrseg.py (variant='mscmrseg')" % name)
+    if len(native_shape) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in native_shape):
+        raise ValueError("%s: native_shape = (X, Y), two positive integers, got %r" % (name, native_shape))
+    return int(native_shape[1]), int(native_shape[0])
+
+
+def _predict_volume(seg_model, x, bs, dev, native, crop_size, origin_size):
+    """eval forward in batches of ``bs`` -> uint8 labels: ``argmax`` at the network's size, or with ``native = (rows, columns)``
+    the fused ``reconstuct_volume`` / ``resize_volume`` / ``argmax`` of ``evaluate_mscmrseg.py:139-145``"""
     x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     x = x.to(dev)
     was_training = seg_model.training
@@ -127,17 +128,41 @@ def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd
         preds = []
         for i in range(0, x.shape[0], bs):
             out = seg_model(x[i:i + bs])
-            preds.append(M.argmax_labels(out[0] if isinstance(out, tuple) else out))
+            logits = out[0] if isinstance(out, tuple) else out
+            if native is None:
+                preds.append(M.argmax_labels(logits))
+            else:
+                preds.append(K.reconstruct_resize_argmax(logits, native[0], native[1], crop_size, origin_size))
     finally:
         seg_model.train(was_training)
-    pred = torch.cat(preds)
+    return torch.cat(preds)
+
+
+@torch.no_grad()
+def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd: bool = True, ifasd: bool = True,
+                    variant: str = "mmwhs", extended: bool = False, native_shape=None, crop_size: int = 112,
+                    origin_size: int = 256):
+    """The device-side core of ``evaluate_segmentation`` (``evaluate_mmwhs.py:118-132``; ``evaluate_mscmrseg.py:132-169``;
+    its resize with ``native_shape``): eval forward in batches of ``bs`` -> argmax -> ``keep_largest_connected_components``
+    (``klc``) -> the variant's ``metrics`` list ([dice, hd, asd] per class), with one synchronisation per volume.
+    ``x``: the volume's slices [Z,C,H,W] (fp32, device tensor or numpy); ``gt_labels``: its label volume [Z,H,W] (MM-WHS
+    1..4; MS-CMRSeg codes 200 / 500 / 600, which the predicted labels 1 / 2 / 3 are mapped to after ``klc``).
+    ``extended``: [dice, hd, asd, hd95, assd] per class (``metrics_from_rows_ext``) from the one call per volume to the
+    extended kernel; the first three are the bits the default call returns.
+    ``native_shape=(X, Y)`` (``variant="mscmrseg"``): the tail of ``evaluate_mscmrseg.py:139-153`` at the label file's own size:
+    the logits pasted at ``origin_size // 2 +- crop_size`` of a zero ``origin_size`` canvas, every class plane resized to ``X``
+    columns by ``Y`` rows (``resize_volume``, the build's INTER_AREA rule: DESIGN.md f15) and ``argmax``, in one kernel that
+    writes the labels ``[Z,Y,X]`` only; then ``klc``, the codes and the metrics against ``gt_labels [Z,Y,X]``
+    (``evaluate_mscmrseg.read_labels``).  With the default ``None`` nothing is resized."""
+    if variant not in ("mmwhs", "mscmrseg"):
+        raise ValueError("evaluate_volume: variant 'mmwhs' or 'mscmrseg'")
+    dev = next(seg_model.parameters()).device
+    pred = _predict_volume(seg_model, x, bs, dev, _native_size("evaluate_volume", native_shape, variant), crop_size, origin_size)
     if klc:
         pred = U.keep_largest_connected_components(pred)
     mod = EW if variant == "mmwhs" else EM
     if variant == "mscmrseg":
-        lut = torch.arange(256, dtype=torch.int32, device=dev)
-        lut[1:4] = torch.tensor([200, 500, 600], dtype=torch.int32, device=dev)
-        pred = lut[pred.long()]
+        pred = EM.codes_table(dev)[pred.long()]      # (uploaded once per device: an upload makes the host wait)
     if extended:
         rows = M.class_metrics_ext(M.to_device(gt_labels, dev), pred, mod.CLASSES).tolist()    # one sync
         return mod.metrics_from_rows_ext(rows, ifhd, ifasd)
@@ -146,33 +171,22 @@ def evaluate_volume(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, ifhd
 
 
 @torch.no_grad()
-def evaluate_volume_rows(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, variant: str = "mmwhs", extended: bool = False):
+def evaluate_volume_rows(seg_model, x, gt_labels, bs: int = 8, klc: bool = True, variant: str = "mmwhs", extended: bool = False,
+                         native_shape=None, crop_size: int = 112, origin_size: int = 256):
     """``evaluate_volume`` up to its synchronisation: the same stages on the same kernels, returning the DEVICE rows
     (``M.class_metrics`` / ``M.class_metrics_ext`` of the variant's classes, float64) that ``metrics_from_rows`` /
     ``metrics_from_rows_ext`` turn into ``evaluate_volume``'s list.  Nothing synchronises, so a loop over patients can keep its
-    rows on the device and read them all at once (``evaluate_mmwhs.evaluate_segmentation``)."""
+    rows on the device and read them all at once (``evaluate_mmwhs.evaluate_segmentation``,
+    ``evaluate_mscmrseg.evaluate_segmentation``).  ``native_shape``, ``crop_size``, ``origin_size``: as in ``evaluate_volume``."""
     if variant not in ("mmwhs", "mscmrseg"):
         raise ValueError("evaluate_volume_rows: variant 'mmwhs' or 'mscmrseg'")
     dev = next(seg_model.parameters()).device
-    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-    x = x.to(dev)
-    was_training = seg_model.training
-    seg_model.eval()
-    try:
-        preds = []
-        for i in range(0, x.shape[0], bs):
-            out = seg_model(x[i:i + bs])
-            preds.append(M.argmax_labels(out[0] if isinstance(out, tuple) else out))
-    finally:
-        seg_model.train(was_training)
-    pred = torch.cat(preds)
+    pred = _predict_volume(seg_model, x, bs, dev, _native_size("evaluate_volume_rows", native_shape, variant), crop_size, origin_size)
     if klc:
         pred = U.keep_largest_connected_components(pred)
     mod = EW if variant == "mmwhs" else EM
     if variant == "mscmrseg":
-        lut = torch.arange(256, dtype=torch.int32, device=dev)
-        lut[1:4] = torch.tensor([200, 500, 600], dtype=torch.int32, device=dev)
-        pred = lut[pred.long()]
+        pred = EM.codes_table(dev)[pred.long()]      # (uploaded once per device: an upload makes the host wait)
     if extended:
         return M.class_metrics_ext(M.to_device(gt_labels, dev), pred, mod.CLASSES)
     return M.class_metrics(M.to_device(gt_labels, dev), pred, mod.CLASSES)
