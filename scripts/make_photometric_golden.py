@@ -18,7 +18,8 @@ of a rounding boundary the pixel may differ by one grey level, and in a chain ev
 such a pixel is excusable too.  The builder asserts that they are at most 1e-5 of all pixels and that the chains have
 none.  The integer operators (average, median, dropouts, invert, add) have no band.
 
-    python scripts/make_photometric_golden.py        # writes tests/golden/photometric.npz"""
+    python scripts/make_photometric_golden.py        # writes tests/golden/photometric.npz
+    python scripts/make_photometric_golden.py --edges    # writes tests/golden/photometric_edges.json (see edges)"""
 from __future__ import annotations
 
 import os
@@ -445,7 +446,39 @@ def load_cases(g):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the edge shapes
+EDGES = os.path.join(ROOT, "tests", "golden", "photometric_edges.json")
+
+
+def edges():
+    """tests/photometric_edge_cases.py's table (more than one tile, C = 2 and 4, both store paths, images below the halo, 224 x 224 x 1):
+    per case the shape, the batch and one sha256 of the expected batch.  Nothing is recorded unless the scipy backend equals the
+    numpy backend on every case and no case has an excusable pixel in either: the table is band-free, and the GPU test
+    demands equality"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("photometric_edge_cases", os.path.join(ROOT, "tests", "photometric_edge_cases.py"))
+    t = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(t)
+    recorded = {}
+    for cs in t.CASES:
+        (a, ea), (n, en) = t.expected(cs, "scipy"), t.expected(cs, "numpy")
+        if not np.array_equal(a, n):
+            raise SystemExit("the scipy and the numpy backend differ on %s: %d elements" % (cs.name, int((a != n).sum())))
+        if ea.any() or en.any():
+            raise SystemExit("%s has %d excusable pixels: change its seed" % (cs.name, int((ea | en).sum())))
+        recorded[cs.name] = t.digests_of(cs)
+    return {"numpy_version": np.__version__, "cases": recorded}
+
+
 if __name__ == "__main__":
+    if "--edges" in sys.argv:
+        import json
+        data = edges()
+        with open(EDGES, "w") as fh:
+            json.dump(data, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+        print("wrote %s: %d cases, %d bytes" % (EDGES, len(data["cases"]), os.path.getsize(EDGES)))
+        sys.exit(0)
     print("restatement: %d pixels, %d excusable" % check_restatement())
     g = build()
     np.savez_compressed(OUT, **g)
