@@ -563,6 +563,38 @@ size_t pcuda_match_hist_workspace_size(int b, int h, int w, int c, int is_u8);
 int pcuda_match_hist(const void* in, void* out, int is_u8, int b, int h, int w, int c, const double* tvalues,
                      const double* tquantiles, const int* tlen, int tstride, void* workspace, size_t workspace_bytes,
                      pcuda_stream_t s);
+/* histogram matching against a BANK of r references kept on the device (csrc/histmatch_bank.hip): sample i of the batch is
+ * matched to reference ref_index[i] -- a source image against a target image drawn from a pool, or against this step's target
+ * batch.  Same definition and the same bits as pcuda_match_hist with the tables of that reference; no host sort, no upload.
+ *
+ * pcuda_hist_bank_build: refs[r][rh][rw][c] (fp32, or uint8 when is_u8), c = 1..4 -> bank, pcuda_hist_bank_size bytes:
+ *   fp32: per plane (r, c) of M = rh rw values its SORTED order-preserving 32-bit keys k[0..M) (4 bytes per value; one
+ *   workgroup per plane, the sort of pcuda_match_hist; workspace: pcuda_hist_bank_workspace_size bytes, the second buffer of
+ *   the sort's ping-pong, free after the call's kernels ran).  -0.0 is stored as +0.0.  uint8: per plane 256 uint32 counts, no
+ *   workspace.  Non-finite reference values are unsupported: *flag (device int32) is set to 0 by the call and to 1 by the
+ *   kernel when it meets one; the call never reads it.  A bank is rebuilt in place by calling again.
+ * pcuda_match_hist_bank: in[b][h][w][c] -> out of the same dtype (is_u8: uint8 images AND a uint8 bank; else fp32 images and
+ *   an fp32 bank); ref_index: device int32 [b], every entry clamped into [0, r) on the device.  rh rw need not equal h w.
+ *   fp32, per value after its own rank search (cnt, q = double(cnt) / double(N) as above), with E(p) = double(p) / double(M)
+ *   and val(key) = the float the key came from, widened to float64:
+ *     e* = max{e in [0, M] : E(e) <= q} (decided by the division; trunc(q M) is only a first guess);
+ *     p = e* if e* == 0, e* == M or k[e*-1] != k[e*], else lower_bound(k, k[e*]) (the last run end at or below e*);
+ *     p == 0: r = val(k[0]);  p == M: r = val(k[M-1]);  otherwise q0 = E(p), v0 = val(k[p-1]); q0 == q: r = v0; else
+ *     p1 = upper_bound(k, k[p]), q1 = E(p1), v1 = val(k[p]), slope = (v1 - v0) / (q1 - q0), r = slope (q - q0) + v0,
+ *   every operation rounded separately in float64; the store is float(r), nearest even.  uint8: the image plane's histogram
+ *   and scan as pcuda_match_hist; the 256 counts of the sample's reference are scanned and compacted into tq / tv in LDS, then
+ *   the same interpolation, truncation into a 256-entry LUT, one gather.
+ *   workspace: pcuda_match_hist_bank_workspace_size bytes (8 per fp32 image value; 0 for uint8), 16-byte aligned.
+ * Both: integer atomics only, the same bits from run to run; never allocate, never synchronise; inputs are never written
+ * (in == out, refs == bank are rejected); an empty batch (b h w == 0) or an empty set (r rh rw == 0 in the build) is a no-op
+ * returning 0; a bank or workspace that is short or not 16-byte aligned is PCUDA_E_WORKSPACE. */
+size_t pcuda_hist_bank_size(int r, int rh, int rw, int c, int is_u8);
+size_t pcuda_hist_bank_workspace_size(int r, int rh, int rw, int c, int is_u8);
+int pcuda_hist_bank_build(const void* refs, int is_u8, int r, int rh, int rw, int c, void* bank, size_t bank_bytes, int* flag,
+                          void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+size_t pcuda_match_hist_bank_workspace_size(int b, int h, int w, int c, int is_u8);
+int pcuda_match_hist_bank(const void* in, void* out, int is_u8, int b, int h, int w, int c, const void* bank, int r, int rh,
+                          int rw, const int* ref_index, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* device-side slice preparation of the MS-CMRSeg data (utils/read_nii_image.py:60-74 preprocess_volume, used at :100, 137,
  * 176 behind RescaleIntensity -> uint8, the nearest resize to 256 and the centre crop to 224; csrc/preprocess.hip).  Parity
  * with OpenCV / ITK is unpinned: the convention below is this build's own, written after OpenCV's clahe.cpp and ITK's

@@ -1092,6 +1092,66 @@ def match_hist(images, tvalues, tquantiles, tlen, out=None):
     return out
 
 
+def hist_bank_storage(r, rh, rw, c, is_u8, device):
+    """``(bank, workspace or None, flag)`` device tensors sized for ``hist_bank_build`` of ``[r,rh,rw,c]`` references"""
+    lib = L.lib()
+    bank = torch.empty(lib.pcuda_hist_bank_size(r, rh, rw, c, int(is_u8)), dtype=torch.uint8, device=device)
+    nbytes = lib.pcuda_hist_bank_workspace_size(r, rh, rw, c, int(is_u8))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+    return bank, ws, torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def hist_bank_build(references, bank=None, workspace=None, flag=None):
+    """The bank of ``[R,H,W,C]`` fp32 or uint8 reference images (``pcuda_hist_bank_build``): fp32 -> the sorted keys of every
+    plane, uint8 -> 256 counts per plane.  ``bank`` / ``workspace`` / ``flag`` (``hist_bank_storage``) are filled in place
+    when given, so a rebuild allocates nothing; ``flag`` is 1 afterwards when a reference value is not finite.  Returns
+    ``(bank, workspace, flag)``; the references are never written."""
+    if references.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("hist_bank_build: fp32 or uint8 references, got %s" % (references.dtype,))
+    _req(references, references.dtype)
+    if references.dim() != 4 or not references.is_contiguous():
+        raise TypeError("hist_bank_build: contiguous [R,H,W,C] references")
+    r, rh, rw, c = references.shape
+    is_u8 = int(references.dtype == torch.uint8)
+    if bank is None:
+        bank, workspace, flag = hist_bank_storage(r, rh, rw, c, is_u8, references.device)
+    _req(bank, torch.uint8); _req(flag, torch.int32)
+    nbytes = 0 if workspace is None else workspace.numel()
+    check(L.lib().pcuda_hist_bank_build(references.data_ptr(), is_u8, r, rh, rw, c, bank.data_ptr(), bank.numel(), flag.data_ptr(),
+                                        _ptr(workspace), nbytes, _stream()), "hist_bank_build")
+    return bank, workspace, flag
+
+
+def match_hist_bank(images, bank, ref_shape, ref_index, out=None):
+    """Histogram matching of ``[B,H,W,C]`` fp32 or uint8 images against a bank (``pcuda_match_hist_bank``): ``bank`` as
+    ``hist_bank_build`` left it for references of ``ref_shape = (R, RH, RW, C)`` and the images' dtype, ``ref_index`` int32
+    ``[B]`` on the device (sample i takes reference ``ref_index[i]``, clamped into ``[0, R)``) -> a new tensor of the images'
+    dtype (the input is never written)."""
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("match_hist_bank: fp32 or uint8 images, got %s" % (images.dtype,))
+    _req(images, images.dtype)
+    if images.dim() != 4:
+        raise TypeError("match_hist_bank: [B,H,W,C] images")
+    images = images.contiguous()
+    b, h, w, c = images.shape
+    r, rh, rw, rc = (int(v) for v in ref_shape)
+    is_u8 = int(images.dtype == torch.uint8)
+    _req(bank, torch.uint8); _req(ref_index, torch.int32)
+    if rc != c:
+        raise ValueError("match_hist_bank: the bank has %d channels, the images %d" % (rc, c))
+    if tuple(ref_index.shape) != (b,) or not ref_index.is_contiguous():
+        raise ValueError("match_hist_bank: ref_index must be a contiguous int32 [%d] tensor" % b)
+    if bank.numel() < L.lib().pcuda_hist_bank_size(r, rh, rw, c, is_u8):
+        raise ValueError("match_hist_bank: the bank is smaller than %r references of the images' dtype need" % (tuple(ref_shape),))
+    if out is None:
+        out = torch.empty_like(images)
+    nbytes = L.lib().pcuda_match_hist_bank_workspace_size(b, h, w, c, is_u8)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device) if nbytes else None
+    check(L.lib().pcuda_match_hist_bank(images.data_ptr(), out.data_ptr(), is_u8, b, h, w, c, bank.data_ptr(), r, rh, rw,
+                                        ref_index.data_ptr(), _ptr(ws), nbytes, _stream()), "match_hist_bank")
+    return out
+
+
 def clahe(images_u8, clip_limit=2.0, tiles_x=4, tiles_y=4, to_float=False, out=None):
     """CLAHE of uint8 ``[N,H,W]`` slices (``pcuda_clahe``: the convention of include/pcuda_hip.h, written after OpenCV's
     ``createCLAHE(clip_limit, (tiles_x, tiles_y)).apply``) -> a new uint8 ``[N,H,W]`` tensor, or fp32 ``[N,3,H,W]`` holding

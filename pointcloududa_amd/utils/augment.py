@@ -34,12 +34,13 @@ modes of ``numpy.pad`` (``pad_mode=ia.ALL``) lives in ``utils/croppad.py`` (f14)
 recipes with it.  Histogram matching against a
 fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
 ``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
-in front of everything else."""
+in front of everything else.  A reference per sample, drawn from a ``HistReferenceBank`` that stays on the device (f10b):
+``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``."""
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Iterable, Optional, Tuple
+from typing import Iterable, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -52,7 +53,7 @@ from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, Hea
                         sample_geo_program, sample_heavy_plan, upload_geo_program)
 from .stylize import (AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, directed_edge_weights, edge_detect_weights,  # noqa: F401
                       sample_style_program, simplex_grid, stylize_aug, superpixel_grid, upload_style_program)
-from .histmatch import HistReference, match_histograms, reference_tables  # noqa: F401
+from .histmatch import HistReference, HistReferenceBank, match_histograms, reference_tables  # noqa: F401
 from .croppad import (AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, MODE_NAMES, CropPadProgram, crop_pad_aug,  # noqa: F401
                       upload_crop_pad_program)
 
@@ -215,7 +216,7 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
                   crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
                   firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True,
                   photometric: Optional[PhotoProgram] = None, heavy: Optional[HeavyPlan] = None,
-                  match_hist: Optional[HistReference] = None):
+                  match_hist: Optional[Union[HistReference, HistReferenceBank]] = None, match_hist_index=None):
     """``data_generator_mmwhs.py:245-274`` after the file reads (``rescale="minmax"``, fp32 images), or
     ``data_generator_mscmrseg.py:305-317`` (``rescale="div255"``, uint8 images), on the device: images ``[B,H,W,C]``,
     integer masks ``[B,H,W]`` (or ``[B,H,W,1]``) ->
@@ -243,9 +244,13 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
     ``match_hist``: a ``HistReference``; the raw images (fp32 or uint8) are histogram-matched against it before anything else
     (``match_histograms``: ``data_generator_mmwhs.py:236-237``, the generator's ``-mh``), so the batch min / max of
     ``rescale="minmax"`` are those of the matched images and a heavy plan or a photometric program sees the matched uint8
-    images; masks and vertices are untouched.  ``params=None, rescale=None`` is then the generator's ``aug=''`` branch."""
+    images; masks and vertices are untouched.  ``params=None, rescale=None`` is then the generator's ``aug=''`` branch.  With a
+    ``HistReferenceBank`` sample ``i`` is matched to reference ``match_hist_index[i]`` (``match_histograms``' ``index``: a host
+    sequence, an int32 device tensor, or ``None`` for a bank of ``B`` or of one)."""
     if match_hist is not None:
-        images_hwc = match_histograms(images_hwc, match_hist)
+        images_hwc = match_histograms(images_hwc, match_hist, index=match_hist_index)
+    elif match_hist_index is not None:
+        raise TypeError("augment_batch: match_hist_index goes with match_hist (a HistReferenceBank)")
     if heavy is not None:
         if rescale == "minmax" or images_hwc.dtype != torch.uint8:
             raise TypeError("augment_batch: a heavy plan takes uint8 images (rescale='div255' or None)")
@@ -327,12 +332,18 @@ class AugmentedBatches:
     their ``_refpad_`` twins) ``preset`` must
     be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters.  With
     ``match_hist_reference`` (an ``[H,W,C]`` numpy image) its tables are built and uploaded once (``match_hist``) and every batch
-    is histogram-matched against it first."""
+    is histogram-matched against it first.  With ``match_hist_bank`` (a ``HistReferenceBank``) every sample is matched to a
+    reference drawn from the bank: ``rng.integers(R, size=B)`` is the FIRST draw of a batch (``last_match_index``), made only
+    when a bank is given, so without one the generator is consumed exactly as before."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
                  photometric_preset: Optional[str] = None, heavy_preset: Optional[str] = None,
-                 match_hist_reference: Optional[np.ndarray] = None):
+                 match_hist_reference: Optional[np.ndarray] = None, match_hist_bank: Optional[HistReferenceBank] = None):
+        if match_hist_reference is not None and match_hist_bank is not None:
+            raise ValueError("AugmentedBatches: match_hist_reference (one image for every sample) or match_hist_bank, not both")
+        if match_hist_bank is not None and not isinstance(match_hist_bank, HistReferenceBank):
+            raise TypeError("AugmentedBatches: match_hist_bank is a HistReferenceBank")
         if preset == "heavy" or photometric_preset == "heavy" or heavy_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
         if heavy_preset is not None:
@@ -355,6 +366,10 @@ class AugmentedBatches:
         self.num_classes, self.crop_size, self.rescale, self.resample_verts = num_classes, crop_size, rescale, resample_verts
         self.photometric_preset, self.heavy_preset = photometric_preset, heavy_preset
         self.match_hist = None if match_hist_reference is None else HistReference(match_hist_reference, device)
+        self.match_hist_bank = match_hist_bank
+        if match_hist_bank is not None:
+            self.match_hist = match_hist_bank
+        self.last_match_index: Optional[np.ndarray] = None
         self.last_plan: Optional[HeavyPlan] = None
         self.last_params: Optional[AugmentParams] = None
         self.last_program: Optional[PhotoProgram] = None
@@ -366,15 +381,18 @@ class AugmentedBatches:
         item = next(self.batches)
         images, masks = item[0], item[1]
         verts = item[2] if len(item) > 2 else None
+        index = None
+        if self.match_hist_bank is not None:
+            index = self.last_match_index = self.rng.integers(self.match_hist_bank.size, size=images.shape[0])
         if self.heavy_preset is not None:
             self.last_params = AugmentParams.identity(images.shape[0])
             self.last_plan = sample_heavy_plan(images.shape[0], self.heavy_preset, self.rng, images.shape[1], images.shape[2])
             return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
                                  resample_verts=self.resample_verts, verts=verts, heavy=self.last_plan,
-                                 match_hist=self.match_hist)
+                                 match_hist=self.match_hist, match_hist_index=index)
         self.last_params = sample_params(images.shape[0], self.preset, self.rng)
         if self.photometric_preset is not None:
             self.last_program = sample_program(images.shape[0], self.photometric_preset, self.rng)
         return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
                              resample_verts=self.resample_verts, verts=verts, photometric=self.last_program,
-                             match_hist=self.match_hist)
+                             match_hist=self.match_hist, match_hist_index=index)
