@@ -510,6 +510,28 @@ size_t pcuda_stylize_workspace_size(int b, int h, int w, int c);
 int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode, const int* iarg,
                   const double* farg, const double* table, const unsigned long long* seed, void* workspace,
                   size_t workspace_bytes, pcuda_stream_t s);
+/* connected superpixels (csrc/spx_connect.hip): pcuda_stylize with an opt-in connectivity pass behind SUPERPIXELS slots, the
+ * counterpart of skimage's enforce_connectivity = True with min_size_factor = 0.5 under iaa.Superpixels.  Same parameters and
+ * status codes as pcuda_stylize; a SUPERPIXELS slot additionally reads iarg[5] = min_size (pcuda_stylize never does):
+ *   iarg[5] <= 0  the slot is pcuda_stylize's, bit for bit; so is every slot of another opcode
+ *   iarg[5] >= 1  (values above h w act as h w) on the label plane of the last assignment: the 4-connected components of equal
+ *                 labels (label 0 is an ordinary label) get as id the index r = y w + x of their raster-first pixel; a
+ *                 component is small iff its own pixel count < min_size and r != 0; a small component's target is the
+ *                 component of pixel r - 1 if x > 0, else of pixel r - w (another component, id below r); targets are followed
+ *                 until a component that is not small: the final id of the pixels on the way (merged pixels count towards
+ *                 nobody's size).  All pixels of one final id form a 4-connected segment; it takes rdiv(sum, n) of the slot's
+ *                 input per channel iff the first word of Philox4x32-10(key = seed, counter = final id) < iarg[4], else its
+ *                 pixels are copied.  min_size = 1 merges nothing and recolours per piece.  Integers only; this build's own
+ *                 convention (parity with skimage's _enforce_label_connectivity_cython is unpinned; no max_size split, no
+ *                 8-connectivity, no downscale to 128 pixels)
+ * h w <= 2^24 (32-bit segment sums; PCUDA_E_BADARG above).  workspace: pcuda_stylize_connect_workspace_size bytes, 16-byte
+ * aligned, needed for slots > 0, each part rounded up to 16 bytes: [pcuda_stylize_workspace_size bytes, laid out as
+ * pcuda_stylize's] [parents int32 b h w] [component sizes uint32 b h w] [segment sums uint32 b h w (c + 1): colour sums, then the
+ * pixel count, at the index of the final id]; 0 for non-positive dims. */
+size_t pcuda_stylize_connect_workspace_size(int b, int h, int w, int c);
+int pcuda_stylize_connect(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
+                          const int* iarg, const double* farg, const double* table, const unsigned long long* seed,
+                          void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* device-side CropAndPad with every defined mode of numpy.pad: iaa.CropAndPad(percent=(-0.05, 0.1), pad_mode=ia.ALL,
  * pad_cval=(0, 255)) of both heavy recipes (data_generator_mscmrseg.py:28-32, 91-95; csrc/croppad.hip) on uint8 images
  * [b][h][w][c], c = 1..4, h, w >= 2, and optional int32 labels [b][h][w], as a per-sample program in device memory: opcode [b]

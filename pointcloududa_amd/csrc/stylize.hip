@@ -24,7 +24,8 @@
 //     (v - centre)^2, ds2 = squared pixel distance, S2 = max(1, (H W) / (gy gx))), a tie goes to the lowest k.  Update: centre =
 //     rdiv(sum, n) for colour, y and x; a centre with n = 0 stays.  After `iters` updates and one last assignment segment k
 //     takes its mean colour rdiv(sum_ch, n) iff the first word of Philox4x32-10(key = seed, counter = (k, 0, 0, 0)) is below
-//     the threshold, else its pixels are copied.  No connectivity pass, no 128-pixel downscale.
+//     the threshold, else its pixels are copied.  No connectivity pass (spx_connect.hip adds one behind this kernel for slots
+//     that ask for it, through pcuda_stylize_connect; pcuda_stylize never reads iarg[5]), no 128-pixel downscale.
 //
 // One slot = three launches, and each workgroup reads its sample's opcode with scalar loads and leaves at once when the
 // slot belongs to another kernel (the branch on the opcode is wave-uniform):
@@ -40,6 +41,7 @@
 // (or the table) BEFORE the load, an unknown opcode copies, and every in-flight load's address stays alive (PCUDA_KEEP, VMEM
 // address rule, common.h).
 #include "common.h"
+#include "stylize_host.h"
 
 namespace {
 
@@ -432,9 +434,9 @@ extern "C" size_t pcuda_stylize_workspace_size(int b, int h, int w, int c) {
   return round16((size_t)b * h * w) + round16((size_t)b * h * w * c);      // the label plane, then the ping-pong image
 }
 
-extern "C" int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
-                             const int* iarg, const double* farg, const double* table, const unsigned long long* seed,
-                             void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
+int stylize_run(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode, const int* iarg,
+                const double* farg, const double* table, const unsigned long long* seed, void* workspace, size_t workspace_bytes,
+                size_t workspace_need, pcuda_stream_t s, StyleSlotHook hook, void* ctx) {
   if (!in || !out) PCUDA_FAIL(PCUDA_E_BADARG, "stylize: null pointer");
   if (in == out) PCUDA_FAIL(PCUDA_E_BADARG, "stylize: in == out (the input is never written)");
   if (b <= 0 || b > 65535 || h <= 0 || w <= 0 || h > 32768 || w > 32768 || c <= 0 || c > kMaxC ||
@@ -443,7 +445,7 @@ extern "C" int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int 
   if (slots < 0 || slots > kMaxSlots) PCUDA_FAIL(PCUDA_E_BADARG, "stylize: slots outside 0..8");
   if (slots > 0 && (!opcode || !iarg || !farg || !table || !seed)) PCUDA_FAIL(PCUDA_E_BADARG, "stylize: null pointer (program)");
   const size_t bytes = (size_t)b * h * w * c;
-  if (slots > 0 && (!workspace || workspace_bytes < pcuda_stylize_workspace_size(b, h, w, c)))
+  if (slots > 0 && (!workspace || workspace_bytes < workspace_need || workspace_bytes < pcuda_stylize_workspace_size(b, h, w, c)))
     PCUDA_FAIL(PCUDA_E_WORKSPACE, "stylize: workspace too small");
   StyleArgs a;
   memset(&a, 0, sizeof(a));
@@ -472,8 +474,19 @@ extern "C" int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int 
       PCUDA_CHECK_LAUNCH("stylize_noise_alpha_kernel");
       hipLaunchKernelGGL(stylize_superpixels_kernel, grid_s, dim3(kSpxThreads), 0, (hipStream_t)s, a);
       PCUDA_CHECK_LAUNCH("stylize_superpixels_kernel");
+      if (hook) {
+        const int rc = hook(ctx, i, cur, dst, a.labels);
+        if (rc != PCUDA_OK) return rc;
+      }
     }
     cur = dst;
   }
   return PCUDA_OK;
+}
+
+extern "C" int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
+                             const int* iarg, const double* farg, const double* table, const unsigned long long* seed,
+                             void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
+  return stylize_run(in, out, b, h, w, c, slots, opcode, iarg, farg, table, seed, workspace, workspace_bytes, 0, s, nullptr,
+                     nullptr);
 }

@@ -1003,10 +1003,12 @@ def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=
     return out, labels_out
 
 
-def stylize(images_u8, opcode, iarg, farg, table, seed, out=None):
+def stylize(images_u8, opcode, iarg, farg, table, seed, out=None, connect=False):
     """A per-sample stylize program over uint8 ``[B,H,W,C]`` images (``pcuda_stylize``): ``opcode`` int32 ``[B,S]``, ``iarg`` int32
     ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed`` int64 ``[B,S]`` (the bits of the 64-bit
-    Philox key), all on the device, ``S`` = 0..8 -> a new uint8 tensor (the input is never written)."""
+    Philox key), all on the device, ``S`` = 0..8 -> a new uint8 tensor (the input is never written).  ``connect=True`` goes
+    through ``pcuda_stylize_connect`` (and its larger workspace): SUPERPIXELS slots with ``iarg[5] > 0`` get the connectivity
+    pass; without it ``iarg[5]`` is never read."""
     _req(images_u8, torch.uint8)
     if images_u8.dim() != 4:
         raise TypeError("stylize: uint8 [B,H,W,C] images")
@@ -1019,11 +1021,13 @@ def stylize(images_u8, opcode, iarg, farg, table, seed, out=None):
         raise ValueError("stylize: the program's arrays do not match the batch of %d" % b)
     if out is None:
         out = torch.empty_like(images_u8)
-    nbytes = L.lib().pcuda_stylize_workspace_size(b, h, w, c) if slots > 0 else 0
+    size_fn, run_fn = (L.lib().pcuda_stylize_connect_workspace_size, L.lib().pcuda_stylize_connect) if connect else \
+        (L.lib().pcuda_stylize_workspace_size, L.lib().pcuda_stylize)
+    nbytes = size_fn(b, h, w, c) if slots > 0 else 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
-    check(L.lib().pcuda_stylize(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, opcode.contiguous().data_ptr(),
-                                iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(), table.contiguous().data_ptr(),
-                                seed.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()), "stylize")
+    check(run_fn(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, opcode.contiguous().data_ptr(),
+                 iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(), table.contiguous().data_ptr(),
+                 seed.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()), "stylize_connect" if connect else "stylize")
     return out
 
 

@@ -51,8 +51,9 @@ from .photometric import (PHOTOMETRIC_PRESET, PhotoProgram, emboss_weights, gaus
                           sample_program, sharpen_weights, upload_program)
 from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, HeavyPlan, geometric_aug, heavy_aug,  # noqa: F401
                         sample_geo_program, sample_heavy_plan, upload_geo_program)
-from .stylize import (AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, directed_edge_weights, edge_detect_weights,  # noqa: F401
-                      sample_style_program, simplex_grid, stylize_aug, superpixel_grid, upload_style_program)
+from .stylize import (AUG2_CONNECTED_PRESET, AUG2_FULL_PRESET, HEAVY_CONNECTED_PRESET, HEAVY_FULL_PRESET, StyleProgram,  # noqa: F401
+                      directed_edge_weights, edge_detect_weights, sample_style_program, simplex_grid, stylize_aug, superpixel_grid,
+                      superpixel_min_size, upload_style_program)
 from .histmatch import HistReference, HistReferenceBank, match_histograms, reference_tables  # noqa: F401
 from .croppad import (AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, MODE_NAMES, CropPadProgram, crop_pad_aug,  # noqa: F401
                       upload_crop_pad_program)
@@ -328,8 +329,8 @@ class AugmentedBatches:
     (``DeviceBatches``); the parameters of each batch are drawn from ``rng`` on the host and ride along through pinned,
     non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
-    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"``, their ``_full_`` or
-    their ``_refpad_`` twins) ``preset`` must
+    uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"``, their ``_full_``,
+    ``_refpad_`` or ``_connected_`` twins) ``preset`` must
     be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters.  With
     ``match_hist_reference`` (an ``[H,W,C]`` numpy image) its tables are built and uploaded once (``match_hist``) and every batch
     is histogram-matched against it first.  With ``match_hist_bank`` (a ``HistReferenceBank``) every sample is matched to a
@@ -348,7 +349,7 @@ class AugmentedBatches:
             raise NotImplementedError(HEAVY_MESSAGE)
         if heavy_preset is not None:
             if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET, HEAVY_FULL_PRESET, AUG2_FULL_PRESET,
-                                    HEAVY_REFPAD_PRESET, AUG2_REFPAD_PRESET):
+                                    HEAVY_REFPAD_PRESET, AUG2_REFPAD_PRESET, HEAVY_CONNECTED_PRESET, AUG2_CONNECTED_PRESET):
                 raise ValueError("unknown heavy preset %r" % (heavy_preset,))
             if preset is not None or photometric_preset is not None:
                 raise ValueError("AugmentedBatches: a heavy preset is the whole recipe (preset and photometric_preset must be None)")

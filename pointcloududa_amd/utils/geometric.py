@@ -53,7 +53,8 @@ from . import photometric as P
 from . import stylize as St
 from .croppad import AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, CropPadProgram, crop_pad_aug
 from .photometric import PhotoProgram, gaussian_weights, photometric_aug
-from .stylize import AUG2_FULL_PRESET, HEAVY_FULL_PRESET, StyleProgram, stylize_aug
+from .stylize import (AUG2_CONNECTED_PRESET, AUG2_FULL_PRESET, HEAVY_CONNECTED_PRESET, HEAVY_FULL_PRESET, StyleProgram,
+                      stylize_aug)
 
 OP_NOP, OP_HOMOGRAPHY, OP_ELASTIC, OP_PIECEWISE = range(4)
 OP_NAMES = ("NOP", "HOMOGRAPHY", "ELASTIC", "PIECEWISE_AFFINE")
@@ -318,6 +319,10 @@ _PRESETS = {
         block=_FULL_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
     AUG2_REFPAD_PRESET: dict(outer=(("c", ENTRY_CROP_AND_PAD), "block"), block=_FULL_BLOCK),
 }
+# the two _refpad_ recipes, draw for draw, with connected superpixels: min_size = superpixel_min_size(..) on every Superpixels
+# slot (f9b)
+_PRESETS[HEAVY_CONNECTED_PRESET] = dict(_PRESETS[HEAVY_REFPAD_PRESET], connected=True)
+_PRESETS[AUG2_CONNECTED_PRESET] = dict(_PRESETS[AUG2_REFPAD_PRESET], connected=True)
 _SOMETIMES = {("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE), ("s", St.ENTRY_SUPERPIXELS)}
 _OUTER_P = {ENTRY_FLIPLR: FLIP_LR_P, ENTRY_FLIPUD: FLIP_UD_P, ENTRY_CROP_AND_PAD: SOMETIMES_P, ENTRY_AFFINE: SOMETIMES_P}
 
@@ -492,7 +497,11 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
     ``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` (f14): the two full recipes with CropAndPad as a
     ``CropPadProgram`` stage of its own (``utils/croppad.py``), its mode uniform over the ten of ``numpy.pad``.  Everything the
     ``_full_`` twin draws is drawn in the same order, then one ``rng.integers(0, 10, batch)`` for the mode; the sides and cval
-    are ``_draw_geo``'s ``crop`` / ``crop_cval`` (its ``crop_mode`` draw is consumed and unused)."""
+    are ``_draw_geo``'s ``crop`` / ``crop_cval`` (its ``crop_mode`` draw is consumed and unused).
+
+    ``"heavy_connected_device"`` and ``"mscmrseg_aug2_connected_device"`` (f9b): the ``_refpad_`` presets, draw for draw, with
+    ``min_size = superpixel_min_size(gy, gx, h, w)`` in ``iarg[5]`` of every Superpixels slot (connected segments,
+    ``csrc/spx_connect.hip``); every other array of the plan equals the ``_refpad_`` plan of the same generator state."""
     spec = _check_preset(preset)
     entries, on = _select(batch, spec, rng)
     dg, dp = _draw_geo(batch, rng, h, w), _draw_photo(batch, rng)
@@ -520,7 +529,7 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
                         if kind == "p":
                             _encode_photo(prog, i, s, entries[q][1], dp)
                         elif kind == "s":
-                            St.encode_style(prog, i, s, entries[q][1], ds, h, w)
+                            St.encode_style(prog, i, s, entries[q][1], ds, h, w, connected=bool(spec.get("connected")))
                         elif kind == "c":
                             t, r, bt, l = dg["crop"][i]
                             prog.set_crop_and_pad(i, crop_pad_pixels(t, h), crop_pad_pixels(r, w), crop_pad_pixels(bt, h),

@@ -37,13 +37,26 @@ A program has ``S`` slots per sample (``S <= 8``); slot ``s`` of sample ``i`` is
                             word of f7's Philox4x32-10 (key = ``seed``, counter = k) is below the threshold, else it is copied
 ==========================  ==================================================================================
 
+Connected superpixels (f9b, ``csrc/spx_connect.hip``, opt-in): ``iarg[5]`` = ``min_size`` of a SUPERPIXELS slot.  0 is the slot
+above, bit for bit.  With ``min_size >= 1`` the 4-connected components of equal labels (label 0 is an ordinary label) get as id
+the index ``r = y W + x`` of their raster-first pixel; a component is small iff its own pixel count is below ``min_size`` and
+``r != 0``; a small component's target is the component of pixel ``r - 1`` if ``x > 0``, else of pixel ``r - W``; targets are
+followed until a component that is not small, which gives every pixel its final id (merged pixels count towards nobody's
+size).  A final segment is 4-connected; it takes ``rdiv(sum, n)`` over its pixels iff the first Philox word for counter = final
+id is below the threshold.  ``superpixel_min_size(gy, gx, H, W) = max(1, (H W) // (2 gy gx))`` is skimage's
+``min_size_factor = 0.5``; the presets ``"heavy_connected_device"`` and ``"mscmrseg_aug2_connected_device"`` are the ``_refpad_``
+presets with it on every Superpixels slot.  ``stylize_aug`` takes the connected entry point iff ``program.needs_connect()``.
+skimage is not installed next to the reference: parity with ``_enforce_label_connectivity_cython`` is unpinned, the rule is
+this build's own (``tests/golden/spx_connect.npz``, ``scripts/make_spx_connect_golden.py``); skimage's ``max_size_factor`` split,
+8-connectivity and imgaug's downscale to 128 pixels are not built.
+
 The value is uint8 again between two slots.  imgaug / cv2 / skimage are not vendored by the reference: parity with imgaug is
 unpinned, the convention is this build's own and is pinned by ``tests/golden/stylize.npz`` (``scripts/make_stylize_golden.py``:
 a vectorised numpy restatement and an independent one -- plain Python integers for hue and superpixels, scipy for
 noise-alpha).  Divergences from imgaug: hue / saturation follow the integer formulas above (cv2's uint8 HSV tables differ by
 a grey level in places) and one value moves both (``per_channel`` is not built); the simplex noise is this file's (gradient
 from Philox, grids of at most 16 x 16, nearest and bilinear upscale only -- no cubic); the superpixels are a grid SLIC without
-a connectivity pass and without imgaug's downscale to 128 pixels.  The string ``"heavy"`` keeps raising (imgaug's parameter
+imgaug's downscale to 128 pixels, and without a connectivity pass unless ``min_size`` asks for one (above).  The string ``"heavy"`` keeps raising (imgaug's parameter
 stream is not reproduced)."""
 from __future__ import annotations
 
@@ -64,7 +77,9 @@ TABLE = MAX_GRIDS * GRID_VALUES
 UPSCALE_NEAREST, UPSCALE_BILINEAR = 0, 1
 AGG_MIN, AGG_MEAN, AGG_MAX = 0, 1, 2
 MAX_SEGMENTS, MAX_UPDATES = 256, 10
+MAX_CONNECT_PIXELS = 1 << 24      # connected slots: the segment sums are 32-bit
 HEAVY_FULL_PRESET, AUG2_FULL_PRESET = "heavy_full_device", "mscmrseg_aug2_full_device"
+HEAVY_CONNECTED_PRESET, AUG2_CONNECTED_PRESET = "heavy_connected_device", "mscmrseg_aug2_connected_device"
 
 # data_generator_mscmrseg.py:46, 57-60, 69
 (ENTRY_SUPERPIXELS, ENTRY_NOISE_ALPHA, ENTRY_HUE) = range(3)
@@ -205,6 +220,11 @@ def superpixel_grid(n_segments: int, h: int, w: int):
     return gy, gx
 
 
+def superpixel_min_size(gy: int, gx: int, h: int, w: int) -> int:
+    """``max(1, (H W) // (2 gy gx))``: half the mean segment size, skimage's ``min_size_factor = 0.5`` (f9b)"""
+    return max(1, (int(h) * int(w)) // (2 * int(gy) * int(gx)))
+
+
 @dataclass
 class StyleProgram:
     """``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed``
@@ -260,18 +280,26 @@ class StyleProgram:
         self.farg[i, s, :9] = np.asarray(weights3x3, dtype=np.float64).reshape(9)
         self.farg[i, s, 9] = thresh
 
-    def set_superpixels(self, i, s, gy, gx, p_replace, seed, iters=SUPERPIXELS_UPDATES, compactness=SUPERPIXELS_COMPACTNESS):
+    def set_superpixels(self, i, s, gy, gx, p_replace, seed, iters=SUPERPIXELS_UPDATES, compactness=SUPERPIXELS_COMPACTNESS,
+                        min_size=0):
+        """``min_size`` (``iarg[5]``): 0 = f9's slot; >= 1 = connected segments (f9b, ``superpixel_min_size``)"""
         self._clear(i, s, OP_SUPERPIXELS)
         self.iarg[i, s, :4] = (int(gy), int(gx), int(iters), int(math.floor(float(compactness) ** 2 + 0.5)))
+        self.iarg[i, s, 5] = int(min_size)
         self.farg[i, s, 0], self.farg[i, s, 1] = p_replace, compactness
         self.seed[i, s] = seed
+
+    def needs_connect(self) -> bool:
+        """any SUPERPIXELS slot with ``iarg[5] > 0`` (a host-side look at the program)"""
+        return bool(np.any((self.opcode == OP_SUPERPIXELS) & (self.iarg[..., 5] > 0)))
 
     def validate(self, h: Optional[int] = None, w: Optional[int] = None, channels: Optional[int] = None) -> None:
         """Raises ``ValueError`` (naming the field) for a program the kernels are not defined on: shapes and dtypes, more
         than 8 slots, unknown opcodes, non-finite ``farg`` / ``table``; hue on C other than 3, dh outside [-180, 180] or ds
         outside [-255, 255]; a grid count outside 1..3, a grid side outside 2..16, an unknown upscale or aggregation, a sigmoid
         flag that is not 0 / 1, table values outside [0, 1], a threshold beyond +/-1000; gy or gx below 1 or above H / W,
-        ``gy gx > 256``, updates outside 0..10, M2 outside 0..2^20, p_replace outside [0, 1]."""
+        ``gy gx > 256``, updates outside 0..10, M2 outside 0..2^20, p_replace outside [0, 1], min_size outside 0..H W, or
+        min_size > 0 on more than 2^24 pixels."""
         op, ia, fa, tb, sd = self.opcode, self.iarg, self.farg, self.table, self.seed
         if getattr(op, "ndim", 0) != 2 or op.dtype != np.int32:
             raise ValueError("StyleProgram.opcode must be int32 [B,S]")
@@ -331,6 +359,11 @@ class StyleProgram:
                 raise ValueError("StyleProgram: SUPERPIXELS M2 (iarg[3], compactness squared) must be in 0..2^20")
             if np.any((f[:, 0] < 0) | (f[:, 0] > 1)):
                 raise ValueError("StyleProgram: SUPERPIXELS p_replace (farg[0]) must be in [0, 1]")
+            if np.any(i[:, 5] < 0) or (h is not None and w is not None and np.any(i[:, 5].astype(np.int64) > h * w)):
+                raise ValueError("StyleProgram: SUPERPIXELS min_size (iarg[5]) must be in 0..H W")
+            if h is not None and w is not None and h * w > MAX_CONNECT_PIXELS and np.any(i[:, 5] > 0):
+                raise ValueError("StyleProgram: SUPERPIXELS min_size (iarg[5]) > 0 takes images of at most 2^24 pixels, got %d x %d"
+                                 % (h, w))
 
     def kernel_arrays(self, h: int, w: int, channels: Optional[int] = None):
         """(opcode, iarg, farg, table, seed as int64 bits) as the kernel takes them: validated for ``h x w x channels``
@@ -358,10 +391,12 @@ def draw_style(b: int, rng: np.random.Generator):
         hue=rng.integers(HUE_VALUE[0], HUE_VALUE[1] + 1, b))
 
 
-def encode_style(prog: StyleProgram, i: int, s: int, entry: int, d, h: int, w: int) -> None:
+def encode_style(prog: StyleProgram, i: int, s: int, entry: int, d, h: int, w: int, connected: bool = False) -> None:
+    """``connected``: Superpixels slots get ``min_size = superpixel_min_size(gy, gx, h, w)`` (the ``_connected_`` presets)"""
     if entry == ENTRY_SUPERPIXELS:
         gy, gx = superpixel_grid(int(d["sp_n"][i]), h, w)
-        prog.set_superpixels(i, s, gy, gx, d["sp_p"][i], d["sp_seed"][i])
+        prog.set_superpixels(i, s, gy, gx, d["sp_p"][i], d["sp_seed"][i],
+                             min_size=superpixel_min_size(gy, gx, h, w) if connected else 0)
     elif entry == ENTRY_NOISE_ALPHA:
         wts = edge_detect_weights(d["na_alpha"][i]) if d["na_kind"][i] == 0 else directed_edge_weights(d["na_alpha"][i], d["na_dir"][i])
         grids = [simplex_grid(int(d["na_size"][i, k, 0]), int(d["na_size"][i, k, 1]), int(d["na_seed"][i, k]))
@@ -379,7 +414,8 @@ def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: i
     ``superpixel_grid``, 5 updates, compactness 10), SimplexNoiseAlpha (alpha U(0.5, 1), OneOf EdgeDetect | DirectedEdgeDetect
     with direction U(0, 1); 1..3 grids of 2..16 cells per side, nearest | bilinear, min | mean | max, sigmoid with a threshold
     from N(0, 5)) and AddToHueAndSaturation (v integer in -20..20: ds = v, dh = floor(v 180 / 255 + 0.5)), each only for the
-    samples whose ``SomeOf((0, 5))`` drew it."""
+    samples whose ``SomeOf((0, 5))`` drew it.  The ``_connected_`` presets draw what their ``_refpad_`` twins draw and give every
+    Superpixels slot ``min_size = superpixel_min_size(gy, gx, h, w)``."""
     from . import geometric as Geo
     spec = Geo._check_preset(preset)
     entries, on = Geo._select(batch, spec, rng)
@@ -392,7 +428,7 @@ def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: i
         s = 0
         for k in sty:
             if on[i, k]:
-                encode_style(prog, i, s, entries[k][1], d, h, w)
+                encode_style(prog, i, s, entries[k][1], d, h, w, connected=bool(spec.get("connected")))
                 s += 1
     return prog
 
@@ -418,4 +454,4 @@ def stylize_aug(images: torch.Tensor, program: Optional[StyleProgram] = None) ->
     if images.dtype != torch.uint8 or images.dim() != 4:
         raise TypeError("stylize_aug: uint8 [B,H,W,C] images")
     b, h, w, c = images.shape
-    return K.stylize(images, *upload_style_program(program, b, h, w, c, images.device))
+    return K.stylize(images, *upload_style_program(program, b, h, w, c, images.device), connect=program.needs_connect())

@@ -171,8 +171,9 @@ def threshold(p):
     return min(int(np.floor(float(p) * 2.0 ** 32)), 2 ** 32 - 1)
 
 
-def superpixels_numpy(img, gy, gx, iters, m2, thr, seed):
-    """-> (int64 [H,W,C], pixels per centre after the last assignment, centres without a pixel in any pass)"""
+def slic_numpy(img, gy, gx, iters, m2):
+    """the grid SLIC alone -> (labels int64 [H,W] of the last assignment, mean colours int64 [K,C], pixels per centre, centres
+    without a pixel in any pass)"""
     h, w, c = img.shape
     v = img.astype(np.int64)
     k_all = gy * gx
@@ -206,6 +207,13 @@ def superpixels_numpy(img, gy, gx, iters, m2, thr, seed):
             np.add.at(sy, flat, yy.ravel())
             np.add.at(sx, flat, xx.ravel())
             cy[has], cx[has] = rdiv(sy[has], n[has]), rdiv(sx[has], n[has])
+    return lab, cc, n, empties
+
+
+def superpixels_numpy(img, gy, gx, iters, m2, thr, seed):
+    """-> (int64 [H,W,C], pixels per centre after the last assignment, centres without a pixel in any pass)"""
+    lab, cc, n, empties = slic_numpy(img, gy, gx, iters, m2)
+    k_all, v = gy * gx, img.astype(np.int64)
     rep = philox4x32_10(seed, np.arange(k_all, dtype=np.uint32))[0] < np.uint32(thr) if thr else np.zeros(k_all, dtype=bool)
     return np.where(rep[lab][..., None], cc[lab], v), n, empties
 
@@ -220,7 +228,8 @@ def _philox_word0_python(key, c0):
     return c0
 
 
-def superpixels_python(img, gy, gx, iters, m2, thr, seed):
+def slic_python(img, gy, gx, iters, m2):
+    """the grid SLIC alone in plain Python integers -> (labels: list of H W, mean colours: list of K lists, pixels per centre)"""
     h, w, c = img.shape
     px = img.reshape(h * w, c).tolist()
     k_all = gy * gx
@@ -264,6 +273,14 @@ def superpixels_python(img, gy, gx, iters, m2, thr, seed):
                 cc[k] = [(2 * sc[k][ch] + n[k]) // (2 * n[k]) for ch in chans]
                 if it < iters:
                     cy[k], cx[k] = (2 * sy[k] + n[k]) // (2 * n[k]), (2 * sx[k] + n[k]) // (2 * n[k])
+    return lab, cc, n
+
+
+def superpixels_python(img, gy, gx, iters, m2, thr, seed):
+    h, w, c = img.shape
+    px = img.reshape(h * w, c).tolist()
+    k_all = gy * gx
+    lab, cc, n = slic_python(img, gy, gx, iters, m2)
     rep = [_philox_word0_python(int(seed), k) < thr for k in range(k_all)]
     out = [cc[lab[p]] if rep[lab[p]] else px[p] for p in range(h * w)]
     return np.array(out, dtype=np.int64).reshape(h, w, c), np.array(n, dtype=np.int64), None
