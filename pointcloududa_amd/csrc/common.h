@@ -131,3 +131,4 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }

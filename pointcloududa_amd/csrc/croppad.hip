@@ -29,6 +29,7 @@
 // program reads wrong texels, never out of bounds; the host validates), and every in-flight load's address stays alive behind
 // the code that consumes the data (PCUDA_KEEP, VMEM address rule, common.h).
 #include "common.h"
+#include "image_device.h"
 
 namespace {
 
@@ -57,8 +58,9 @@ struct Samp {
   int hc, wc, hi, wi;        // the crop and the padded array I
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ uint32_t round_u8(double v) {
+using imgdev::clampi;
+// imgdev::round_u8 in a 32-bit word, as the packed store takes it (the uint8_t form costs a mask here)
+__device__ __forceinline__ uint32_t round_u8_word(double v) {
   const double r = fmin(fmax(floor(v + 0.5), 0.0), 255.0);
   return (uint32_t)(int)r;
 }
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(256) void croppad_sample_kernel(const CpArgs a) {
       v += p[1] * wy0 * wx1;
       v += p[2] * wy1 * wx0;
       v += p[3] * wy1 * wx1;
-      const uint32_t res = round_u8(v);
+      const uint32_t res = round_u8_word(v);
       const int e = j * c + ch;
       words[e >> 2] |= res << (8 * (e & 3));
 #pragma unroll
@@ -367,7 +369,6 @@ __global__ __launch_bounds__(256) void croppad_sample_kernel(const CpArgs a) {
   }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline int table_stride(int h, int w) { return (w + h + 2 * kMaxPad + 3) & ~3; }
 inline bool dims_ok(int b, int h, int w, int c) {
   return b > 0 && b <= 65535 && c > 0 && c <= kMaxC && h >= 2 && w >= 2 && (long long)h * w * c < (1ll << 31) - 8192;

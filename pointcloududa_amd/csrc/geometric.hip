@@ -32,6 +32,7 @@
 // of bounds), an unknown opcode copies, and every in-flight load's address stays alive behind the code that consumes the
 // data (PCUDA_KEEP, VMEM address rule, common.h).
 #include "common.h"
+#include "image_device.h"
 
 namespace {
 
@@ -58,8 +59,9 @@ struct GeoArgs {
   int vec_out, vec_lab;      // 4-byte image stores / 16-byte label stores are aligned
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ uint32_t round_u8(double v) {
+using imgdev::clampi;
+// imgdev::round_u8 in a 32-bit word, as the packed store takes it (the uint8_t form costs a mask here)
+__device__ __forceinline__ uint32_t round_u8_word(double v) {
   const double r = fmin(fmax(floor(v + 0.5), 0.0), 255.0);      // (fmax returns the other operand for a NaN: 0)
   return (uint32_t)(int)r;
 }
@@ -176,7 +178,7 @@ __device__ __forceinline__ void sample_store(const GeoArgs& a, int n, int xg, in
         v += p[ORD ? 1 : 0] * wy0 * wx1;
         v += p[ORD ? 2 : 0] * wy1 * wx0;
         v += p[ORD ? 3 : 0] * wy1 * wx1;
-        res = round_u8(v);
+        res = round_u8_word(v);
       }
       const int e = j * c + ch;
       words[e >> 2] |= res << (8 * (e & 3));
@@ -321,7 +323,6 @@ __global__ __launch_bounds__(256) void geometric_kernel(const GeoArgs a) {
   else sample_store<0>(a, n, xg, y, sx, sy, mode, cv);
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 

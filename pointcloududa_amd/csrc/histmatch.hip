@@ -134,7 +134,6 @@ __global__ __launch_bounds__(kU8Threads) void histmatch_u8_kernel(const HistArgs
   }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 

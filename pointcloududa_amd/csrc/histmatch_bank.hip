@@ -246,7 +246,6 @@ __global__ __launch_bounds__(kU8Threads) void histbank_match_u8_kernel(const Ban
   }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 inline bool bad_plane_dims(int count, int h, int w, int c) {
   return count < 0 || h < 0 || w < 0 || c <= 0 || c > kMaxC || count > 65535 || h > 32768 || w > 32768 ||

@@ -26,6 +26,7 @@
 // bounds), an unknown opcode copies, and every in-flight load's address stays alive (PCUDA_KEEP, VMEM address rule,
 // common.h).
 #include "common.h"
+#include "image_device.h"
 
 namespace {
 
@@ -55,19 +56,9 @@ struct PhotoArgs {
 };
 
 __device__ __forceinline__ bool is_neighbourhood(int op) { return op >= OP_GAUSSIAN_BLUR && op <= OP_CONV3X3; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// np.pad(mode="reflect") index for any i; n >= 1
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  const int period = 2 * (n - 1);
-  i %= period;
-  if (i < 0) i += period;
-  return i < n ? i : period - i;
-}
-__device__ __forceinline__ uint8_t round_u8(double v) {
-  const double r = fmin(fmax(floor(v + 0.5), 0.0), 255.0);      // (fmax returns the other operand for a NaN: 0)
-  return (uint8_t)(int)r;
-}
+using imgdev::clampi;
+using imgdev::reflect101;
+using imgdev::round_u8;
 
 // Philox4x32-10 as implemented here: ten rounds, the key bumped between rounds
 struct Philox4 { uint32_t x0, x1, x2, x3; };
@@ -319,7 +310,6 @@ __global__ __launch_bounds__(256) void photometric_neighbourhood_kernel(const Ph
   }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 

@@ -376,7 +376,6 @@ __global__ __launch_bounds__(256) void rescale_map_kernel(const RescaleArgs a, c
   }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 template <int DT>
 int launch_rescale(const RescaleArgs& a, hipStream_t s) {

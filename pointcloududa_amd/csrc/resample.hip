@@ -33,7 +33,6 @@ constexpr int kMaxRemap = 8;
 constexpr int kMaxClasses = 8;
 constexpr int kReduceBlocks = 1024;            // workgroups of sqdev_partial_kernel, at most
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline int round4(int v) { return (v + 3) & ~3; }
 
 struct Geom {

@@ -40,6 +40,7 @@
 //   [pcuda_stylize_workspace_size bytes: f9's label plane and ping-pong image] [par int32 b h w] [size uint32 b h w]
 //   [sums uint32 b h w (c + 1)]
 #include "common.h"
+#include "image_device.h"
 #include "stylize_host.h"
 
 namespace {
@@ -70,18 +71,7 @@ __device__ __forceinline__ int conn_min_size(const ConnArgs& a, int n) {
   return m <= 0 ? 0 : min(m, a.h * a.w);
 }
 
-// first word of Philox4x32-10 as photometric.hip and stylize.hip implement it
-__device__ __forceinline__ uint32_t philox_word0(uint32_t k0, uint32_t k1, uint32_t c0) {
-  uint32_t c1 = 0, c2 = 0, c3 = 0;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
+using imgdev::philox_word0;
 
 __device__ __forceinline__ int conn_parent(int* par, int x) {      // agent-scope load: sees the other blocks' hooks
   int* p = par + x;
@@ -307,7 +297,6 @@ __global__ __launch_bounds__(256) void spx_connect_write_kernel(const ConnArgs a
     }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct ConnCtx {
   ConnArgs a;

@@ -41,6 +41,7 @@
 // (or the table) BEFORE the load, an unknown opcode copies, and every in-flight load's address stays alive (PCUDA_KEEP, VMEM
 // address rule, common.h).
 #include "common.h"
+#include "image_device.h"
 #include "stylize_host.h"
 
 namespace {
@@ -69,19 +70,10 @@ struct StyleArgs {
   int word_in, word_out;     // 4-byte loads / stores of a group of four pixels are aligned (C = 3)
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// np.pad(mode="reflect") index for any i; n >= 1
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  const int period = 2 * (n - 1);
-  i %= period;
-  if (i < 0) i += period;
-  return i < n ? i : period - i;
-}
-__device__ __forceinline__ uint8_t round_u8(double v) {
-  const double r = fmin(fmax(floor(v + 0.5), 0.0), 255.0);      // (fmax returns the other operand for a NaN: 0)
-  return (uint8_t)(int)r;
-}
+using imgdev::clampi;
+using imgdev::reflect101;
+using imgdev::round_u8;
+using imgdev::philox_word0;
 // floor((2 a + b) / (2 b)), b > 0
 __device__ __forceinline__ int rdiv(int a, int b) {
   const int num = 2 * a + b, den = 2 * b;
@@ -89,19 +81,6 @@ __device__ __forceinline__ int rdiv(int a, int b) {
   return (num % den != 0 && num < 0) ? q - 1 : q;
 }
 __device__ __forceinline__ long long rdiv64(long long a, long long b) { return (2 * a + b) / (2 * b); }      // a >= 0, b > 0
-
-// first word of Philox4x32-10 as photometric.hip implements it: ten rounds, the key bumped between rounds
-__device__ __forceinline__ uint32_t philox_word0(uint32_t k0, uint32_t k1, uint32_t c0) {
-  uint32_t c1 = 0, c2 = 0, c3 = 0;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
 
 // one pixel through HUE_SATURATION; dh in 0..179, ds in -255..255
 __device__ __forceinline__ void hue_pixel(int& r, int& g, int& b, int dh, int ds) {
@@ -425,7 +404,6 @@ __global__ __launch_bounds__(kSpxThreads) void stylize_superpixels_kernel(const 
   }
 }
 
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 

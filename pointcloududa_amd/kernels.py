@@ -46,6 +46,66 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _images(what, t, dtypes=(torch.uint8,), dim=4):
+    """the head of the image wrappers: a device tensor of one of ``dtypes`` with ``dim`` dimensions -> (the contiguous
+    tensor, its shape)"""
+    layout = "[B,H,W,C] images" if dim == 4 else "[N,H,W] slices"
+    if len(dtypes) == 1:
+        _req(t, dtypes[0])
+        layout = "uint8 " + layout
+    else:
+        if t.dtype not in dtypes:
+            raise TypeError("%s: fp32 or uint8 images, got %s" % (what, t.dtype))
+        _req(t, t.dtype)
+    if t.dim() != dim:
+        raise TypeError("%s: %s" % (what, layout))
+    t = t.contiguous()
+    return t, tuple(t.shape)
+
+
+def _program(what, b, opcode, seed, **columns):
+    """a slot program's device arrays against a batch of ``b``: ``opcode`` int32 and ``seed`` int64 ``[b,S]``, every column
+    ``name=(tensor, dtype, width)`` ``[b,S,width]`` -> (S, the contiguous tensors: opcode, the columns in order, seed)"""
+    cols = list(columns.values())
+    _req(opcode, torch.int32)
+    for t, dtype, _ in cols:
+        _req(t, dtype)
+    _req(seed, torch.int64)
+    slots = opcode.shape[1] if opcode.dim() == 2 else -1
+    if tuple(opcode.shape) != (b, slots) or tuple(seed.shape) != (b, slots) or \
+            any(tuple(t.shape) != (b, slots, n) for t, _, n in cols):
+        raise ValueError("%s: the program's arrays do not match the batch of %d" % (what, b))
+    return slots, [t.contiguous() for t in [opcode] + [c[0] for c in cols] + [seed]]
+
+
+def _workspace(nbytes, device):
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _out(what, out, like, name="out"):
+    """a caller's result tensor checked before anything is launched (the entry points only see a pointer): ``None`` -> a new
+    tensor like ``like``; else a contiguous device tensor of ``like``'s dtype and shape"""
+    if out is None:
+        return torch.empty_like(like)
+    if not torch.is_tensor(out) or not out.is_cuda or out.dtype != like.dtype or out.shape != like.shape or \
+            not out.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous %s tensor of shape %s"
+                         % (what, name, str(like.dtype).replace("torch.", ""), list(like.shape)))
+    return out
+
+
+def _labels_io(what, labels, labels_out, shape):
+    """the optional int32 labels next to images of ``shape`` ``(b, h, w)`` and their result tensor -> (the contiguous labels,
+    ``labels_out``), or ``(None, None)`` without labels"""
+    if labels is None:
+        return None, None
+    _req(labels, torch.int32)
+    labels = labels.contiguous()
+    if tuple(labels.shape) != shape:
+        raise ValueError("%s: label shape %r does not match the images" % (what, tuple(labels.shape)))
+    return labels, _out(what, labels_out, labels, "labels_out")
+
+
 def _planes(t: torch.Tensor) -> Tuple[int, int, int, int, int]:
     """(n, c, hw, sn, sc) of a [N,C,...] tensor whose trailing dims form a dense plane."""
     _req(t)
@@ -949,22 +1009,12 @@ def photometric(images_u8, opcode, iarg, farg, seed, out=None):
     """A per-sample photometric program over uint8 ``[B,H,W,C]`` images (``pcuda_photometric``): ``opcode`` int32 ``[B,S]``,
     ``iarg`` int32 ``[B,S,4]``, ``farg`` float64 ``[B,S,16]``, ``seed`` int64 ``[B,S]`` (the bits of the 64-bit Philox key), all on
     the device, ``S`` = 0..8 -> a new uint8 tensor (the input is never written)."""
-    _req(images_u8, torch.uint8)
-    if images_u8.dim() != 4:
-        raise TypeError("photometric: uint8 [B,H,W,C] images")
-    images_u8 = images_u8.contiguous()
-    b, h, w, c = images_u8.shape
-    _req(opcode, torch.int32); _req(iarg, torch.int32); _req(farg, torch.float64); _req(seed, torch.int64)
-    slots = opcode.shape[1] if opcode.dim() == 2 else -1
-    if tuple(opcode.shape) != (b, slots) or tuple(iarg.shape) != (b, slots, 4) or tuple(farg.shape) != (b, slots, 16) or \
-            tuple(seed.shape) != (b, slots):
-        raise ValueError("photometric: the program's arrays do not match the batch of %d" % b)
-    if out is None:
-        out = torch.empty_like(images_u8)
+    images_u8, (b, h, w, c) = _images("photometric", images_u8)
+    slots, arrays = _program("photometric", b, opcode, seed, iarg=(iarg, torch.int32, 4), farg=(farg, torch.float64, 16))
+    out = _out("photometric", out, images_u8)
     nbytes = L.lib().pcuda_photometric_workspace_size(b, h, w, c) if slots > 1 else 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
-    check(L.lib().pcuda_photometric(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, opcode.contiguous().data_ptr(),
-                                    iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(), seed.contiguous().data_ptr(),
+    ws = _workspace(nbytes, images_u8.device)
+    check(L.lib().pcuda_photometric(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, *(t.data_ptr() for t in arrays),
                                     _ptr(ws), nbytes, _stream()), "photometric")
     return out
 
@@ -974,32 +1024,14 @@ def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=
     (``pcuda_geometric``): ``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,4]``, ``farg`` float64 ``[B,S,32]``, ``seed`` int64
     ``[B,S]`` (the bits of the 64-bit Philox key), all on the device, ``S`` = 0..8 -> ``(images, labels or None)``, new tensors
     (the inputs are never written)."""
-    _req(images_u8, torch.uint8)
-    if images_u8.dim() != 4:
-        raise TypeError("geometric: uint8 [B,H,W,C] images")
-    images_u8 = images_u8.contiguous()
-    b, h, w, c = images_u8.shape
-    _req(opcode, torch.int32); _req(iarg, torch.int32); _req(farg, torch.float64); _req(seed, torch.int64)
-    slots = opcode.shape[1] if opcode.dim() == 2 else -1
-    if tuple(opcode.shape) != (b, slots) or tuple(iarg.shape) != (b, slots, 4) or tuple(farg.shape) != (b, slots, 32) or \
-            tuple(seed.shape) != (b, slots):
-        raise ValueError("geometric: the program's arrays do not match the batch of %d" % b)
-    if labels is not None:
-        _req(labels, torch.int32)
-        labels = labels.contiguous()
-        if tuple(labels.shape) != (b, h, w):
-            raise ValueError("geometric: label shape %r does not match the images" % (tuple(labels.shape),))
-        if labels_out is None:
-            labels_out = torch.empty_like(labels)
-    else:
-        labels_out = None
-    if out is None:
-        out = torch.empty_like(images_u8)
+    images_u8, (b, h, w, c) = _images("geometric", images_u8)
+    slots, arrays = _program("geometric", b, opcode, seed, iarg=(iarg, torch.int32, 4), farg=(farg, torch.float64, 32))
+    labels, labels_out = _labels_io("geometric", labels, labels_out, (b, h, w))
+    out = _out("geometric", out, images_u8)
     nbytes = L.lib().pcuda_geometric_workspace_size(b, h, w, c, int(labels is not None)) if slots > 1 else 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    ws = _workspace(nbytes, images_u8.device)
     check(L.lib().pcuda_geometric(images_u8.data_ptr(), out.data_ptr(), _ptr(labels), _ptr(labels_out), b, h, w, c, slots,
-                                  opcode.contiguous().data_ptr(), iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(),
-                                  seed.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()), "geometric")
+                                  *(t.data_ptr() for t in arrays), _ptr(ws), nbytes, _stream()), "geometric")
     return out, labels_out
 
 
@@ -1009,25 +1041,16 @@ def stylize(images_u8, opcode, iarg, farg, table, seed, out=None, connect=False)
     Philox key), all on the device, ``S`` = 0..8 -> a new uint8 tensor (the input is never written).  ``connect=True`` goes
     through ``pcuda_stylize_connect`` (and its larger workspace): SUPERPIXELS slots with ``iarg[5] > 0`` get the connectivity
     pass; without it ``iarg[5]`` is never read."""
-    _req(images_u8, torch.uint8)
-    if images_u8.dim() != 4:
-        raise TypeError("stylize: uint8 [B,H,W,C] images")
-    images_u8 = images_u8.contiguous()
-    b, h, w, c = images_u8.shape
-    _req(opcode, torch.int32); _req(iarg, torch.int32); _req(farg, torch.float64); _req(table, torch.float64); _req(seed, torch.int64)
-    slots = opcode.shape[1] if opcode.dim() == 2 else -1
-    if tuple(opcode.shape) != (b, slots) or tuple(iarg.shape) != (b, slots, 12) or tuple(farg.shape) != (b, slots, 16) or \
-            tuple(table.shape) != (b, slots, 768) or tuple(seed.shape) != (b, slots):
-        raise ValueError("stylize: the program's arrays do not match the batch of %d" % b)
-    if out is None:
-        out = torch.empty_like(images_u8)
+    images_u8, (b, h, w, c) = _images("stylize", images_u8)
+    slots, arrays = _program("stylize", b, opcode, seed, iarg=(iarg, torch.int32, 12), farg=(farg, torch.float64, 16),
+                             table=(table, torch.float64, 768))
+    out = _out("stylize", out, images_u8)
     size_fn, run_fn = (L.lib().pcuda_stylize_connect_workspace_size, L.lib().pcuda_stylize_connect) if connect else \
         (L.lib().pcuda_stylize_workspace_size, L.lib().pcuda_stylize)
     nbytes = size_fn(b, h, w, c) if slots > 0 else 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
-    check(run_fn(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, opcode.contiguous().data_ptr(),
-                 iarg.contiguous().data_ptr(), farg.contiguous().data_ptr(), table.contiguous().data_ptr(),
-                 seed.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()), "stylize_connect" if connect else "stylize")
+    ws = _workspace(nbytes, images_u8.device)
+    check(run_fn(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, *(t.data_ptr() for t in arrays), _ptr(ws), nbytes,
+                 _stream()), "stylize_connect" if connect else "stylize")
     return out
 
 
@@ -1035,35 +1058,14 @@ def crop_pad(images_u8, labels, opcode, iarg, out=None, labels_out=None):
     """CropAndPad with numpy's pad modes over uint8 ``[B,H,W,C]`` images and optional int32 ``[B,H,W]`` labels (``pcuda_crop_pad``):
     ``opcode`` int32 ``[B]`` (0 copy, 1 crop-and-pad), ``iarg`` int32 ``[B,6]`` = (top, right, bottom, left, mode, cval), both on the
     device -> ``(images, labels or None)``, new tensors unless ``out`` / ``labels_out`` are given (the inputs are never written)."""
-    _req(images_u8, torch.uint8)
-    if images_u8.dim() != 4:
-        raise TypeError("crop_pad: uint8 [B,H,W,C] images")
-    images_u8 = images_u8.contiguous()
-    b, h, w, c = images_u8.shape
+    images_u8, (b, h, w, c) = _images("crop_pad", images_u8)
     _req(opcode, torch.int32); _req(iarg, torch.int32)
     if tuple(opcode.shape) != (b,) or tuple(iarg.shape) != (b, 6):
         raise ValueError("crop_pad: the program's arrays do not match the batch of %d" % b)
-    if labels is not None:
-        _req(labels, torch.int32)
-        labels = labels.contiguous()
-        if tuple(labels.shape) != (b, h, w):
-            raise ValueError("crop_pad: label shape %r does not match the images" % (tuple(labels.shape),))
-        if labels_out is None:
-            labels_out = torch.empty_like(labels)
-        else:
-            _req(labels_out, torch.int32)
-            if tuple(labels_out.shape) != (b, h, w) or not labels_out.is_contiguous():
-                raise ValueError("crop_pad: labels_out must be a contiguous int32 [B,H,W] tensor")
-    else:
-        labels_out = None
-    if out is None:
-        out = torch.empty_like(images_u8)
-    else:
-        _req(out, torch.uint8)
-        if out.shape != images_u8.shape or not out.is_contiguous():
-            raise ValueError("crop_pad: out must be a contiguous uint8 tensor of the images' shape")
+    labels, labels_out = _labels_io("crop_pad", labels, labels_out, (b, h, w))
+    out = _out("crop_pad", out, images_u8)
     nbytes = L.lib().pcuda_crop_pad_workspace_size(b, h, w, c)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    ws = _workspace(nbytes, images_u8.device)
     check(L.lib().pcuda_crop_pad(images_u8.data_ptr(), out.data_ptr(), _ptr(labels), _ptr(labels_out), b, h, w, c,
                                  opcode.contiguous().data_ptr(), iarg.contiguous().data_ptr(), _ptr(ws), nbytes, _stream()),
           "crop_pad")
@@ -1074,22 +1076,15 @@ def match_hist(images, tvalues, tquantiles, tlen, out=None):
     """Histogram matching of ``[B,H,W,C]`` fp32 or uint8 images against a template's tables (``pcuda_match_hist``): ``tvalues`` and
     ``tquantiles`` float64 ``[C,T]`` (per channel the template's sorted distinct values and ``cumsum(counts) / M``), ``tlen`` int32
     ``[C]`` valid entries, all on the device -> a new tensor of the images' dtype (the input is never written)."""
-    if images.dtype not in (torch.float32, torch.uint8):
-        raise TypeError("match_hist: fp32 or uint8 images, got %s" % (images.dtype,))
-    _req(images, images.dtype)
-    if images.dim() != 4:
-        raise TypeError("match_hist: [B,H,W,C] images")
-    images = images.contiguous()
-    b, h, w, c = images.shape
+    images, (b, h, w, c) = _images("match_hist", images, (torch.float32, torch.uint8))
     _req(tvalues, torch.float64); _req(tquantiles, torch.float64); _req(tlen, torch.int32)
     if tvalues.dim() != 2 or tvalues.shape[0] != c or tvalues.shape[1] < 1 or tquantiles.shape != tvalues.shape or \
             tuple(tlen.shape) != (c,):
         raise ValueError("match_hist: the tables do not match the %d channels of the images" % c)
-    if out is None:
-        out = torch.empty_like(images)
+    out = _out("match_hist", out, images)
     is_u8 = int(images.dtype == torch.uint8)
     nbytes = L.lib().pcuda_match_hist_workspace_size(b, h, w, c, is_u8)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device) if nbytes else None
+    ws = _workspace(nbytes, images.device)
     check(L.lib().pcuda_match_hist(images.data_ptr(), out.data_ptr(), is_u8, b, h, w, c, tvalues.contiguous().data_ptr(),
                                    tquantiles.contiguous().data_ptr(), tlen.contiguous().data_ptr(), int(tvalues.shape[1]),
                                    _ptr(ws), nbytes, _stream()), "match_hist")
@@ -1100,8 +1095,7 @@ def hist_bank_storage(r, rh, rw, c, is_u8, device):
     """``(bank, workspace or None, flag)`` device tensors sized for ``hist_bank_build`` of ``[r,rh,rw,c]`` references"""
     lib = L.lib()
     bank = torch.empty(lib.pcuda_hist_bank_size(r, rh, rw, c, int(is_u8)), dtype=torch.uint8, device=device)
-    nbytes = lib.pcuda_hist_bank_workspace_size(r, rh, rw, c, int(is_u8))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+    ws = _workspace(lib.pcuda_hist_bank_workspace_size(r, rh, rw, c, int(is_u8)), device)
     return bank, ws, torch.zeros(1, dtype=torch.int32, device=device)
 
 
@@ -1131,13 +1125,7 @@ def match_hist_bank(images, bank, ref_shape, ref_index, out=None):
     ``hist_bank_build`` left it for references of ``ref_shape = (R, RH, RW, C)`` and the images' dtype, ``ref_index`` int32
     ``[B]`` on the device (sample i takes reference ``ref_index[i]``, clamped into ``[0, R)``) -> a new tensor of the images'
     dtype (the input is never written)."""
-    if images.dtype not in (torch.float32, torch.uint8):
-        raise TypeError("match_hist_bank: fp32 or uint8 images, got %s" % (images.dtype,))
-    _req(images, images.dtype)
-    if images.dim() != 4:
-        raise TypeError("match_hist_bank: [B,H,W,C] images")
-    images = images.contiguous()
-    b, h, w, c = images.shape
+    images, (b, h, w, c) = _images("match_hist_bank", images, (torch.float32, torch.uint8))
     r, rh, rw, rc = (int(v) for v in ref_shape)
     is_u8 = int(images.dtype == torch.uint8)
     _req(bank, torch.uint8); _req(ref_index, torch.int32)
@@ -1147,10 +1135,9 @@ def match_hist_bank(images, bank, ref_shape, ref_index, out=None):
         raise ValueError("match_hist_bank: ref_index must be a contiguous int32 [%d] tensor" % b)
     if bank.numel() < L.lib().pcuda_hist_bank_size(r, rh, rw, c, is_u8):
         raise ValueError("match_hist_bank: the bank is smaller than %r references of the images' dtype need" % (tuple(ref_shape),))
-    if out is None:
-        out = torch.empty_like(images)
+    out = _out("match_hist_bank", out, images)
     nbytes = L.lib().pcuda_match_hist_bank_workspace_size(b, h, w, c, is_u8)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device) if nbytes else None
+    ws = _workspace(nbytes, images.device)
     check(L.lib().pcuda_match_hist_bank(images.data_ptr(), out.data_ptr(), is_u8, b, h, w, c, bank.data_ptr(), r, rh, rw,
                                         ref_index.data_ptr(), _ptr(ws), nbytes, _stream()), "match_hist_bank")
     return out
@@ -1160,11 +1147,7 @@ def clahe(images_u8, clip_limit=2.0, tiles_x=4, tiles_y=4, to_float=False, out=N
     """CLAHE of uint8 ``[N,H,W]`` slices (``pcuda_clahe``: the convention of include/pcuda_hip.h, written after OpenCV's
     ``createCLAHE(clip_limit, (tiles_x, tiles_y)).apply``) -> a new uint8 ``[N,H,W]`` tensor, or fp32 ``[N,3,H,W]`` holding
     ``u8 / 255`` in all three channels when ``to_float`` (the input is never written)."""
-    _req(images_u8, torch.uint8)
-    if images_u8.dim() != 3:
-        raise TypeError("clahe: uint8 [N,H,W] slices")
-    images_u8 = images_u8.contiguous()
-    n, h, w = images_u8.shape
+    images_u8, (n, h, w) = _images("clahe", images_u8, dim=3)
     if out is None:
         out = torch.empty((n, 3, h, w), dtype=torch.float32, device=images_u8.device) if to_float else torch.empty_like(images_u8)
     else:
@@ -1172,7 +1155,7 @@ def clahe(images_u8, clip_limit=2.0, tiles_x=4, tiles_y=4, to_float=False, out=N
         if tuple(out.shape) != ((n, 3, h, w) if to_float else (n, h, w)) or not out.is_contiguous():
             raise ValueError("clahe: out does not match the result's shape")
     nbytes = L.lib().pcuda_clahe_workspace_size(n, int(tiles_x), int(tiles_y))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=images_u8.device) if nbytes else None
+    ws = _workspace(nbytes, images_u8.device)
     check(L.lib().pcuda_clahe(images_u8.data_ptr(), out.data_ptr(), n, h, w, float(clip_limit), int(tiles_x), int(tiles_y),
                               int(bool(to_float)), _ptr(ws), nbytes, _stream()), "clahe")
     return out
@@ -1266,7 +1249,7 @@ def zoom_standardize(volume, zoomed_hw, crop=0, channels=1, out=None, stats=None
     out = _zoom_out("zoom_standardize", out, (n, oh, ow) if channels == 1 else (n, 3, oh, ow), torch.float32, volume.device)
     stats = _zoom_out("zoom_standardize", stats, (2,), torch.float64, volume.device)
     nbytes = L.lib().pcuda_zoom_standardize_workspace_size(_PRE_DTYPES[volume.dtype], n, zh, zw, crop)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=volume.device) if nbytes else None
+    ws = _workspace(nbytes, volume.device)
     check(L.lib().pcuda_zoom_standardize(volume.data_ptr(), _PRE_DTYPES[volume.dtype], n, sh, sw, zh, zw, crop, int(channels),
                                          out.data_ptr(), stats.data_ptr(), _ptr(ws), nbytes, _stream()), "zoom_standardize")
     return out, stats
@@ -1578,7 +1561,7 @@ def linear_bwd_w(dy, x, dw, db, accumulate=True):
     k = x.shape[1]
     lib = L.lib()
     nb = lib.pcuda_linear_bwd_w_workspace_size(m, k, n)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dy.device) if nb else None
+    ws = _workspace(nb, dy.device)
     check(lib.pcuda_linear_bwd_w(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), m, k, n,
                                  1 if accumulate else 0, _ptr(ws), nb, _stream()), "linear_bwd_w")
 

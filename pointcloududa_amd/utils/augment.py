@@ -35,182 +35,33 @@ recipes with it.  Histogram matching against a
 fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
 ``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
 in front of everything else.  A reference per sample, drawn from a ``HistReferenceBank`` that stays on the device (f10b):
-``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``."""
+``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``.
+
+This module is the facade: the parameters and matrices of the light pipeline live in ``utils/affine.py``, the heavy recipes
+(presets, ``sample_heavy_plan``, ``heavy_aug``, ``sample_geo_program``, ``sample_style_program``) in ``utils/heavy.py``, the frame all
+programs share in ``utils/_program.py``; every name is re-exported here."""
 from __future__ import annotations
 
-import math
-from dataclasses import dataclass, field
-from typing import Iterable, Optional, Tuple, Union
+from typing import Iterable, Optional, Union
 
 import numpy as np
 import torch
 
 from .. import kernels as K
 from .npy2point import masks_to_pointclouds
+from ._program import HEAVY_MESSAGE, as_labels, like_masks  # noqa: F401
+from .affine import (OP_AFFINE, OP_FLIPLR, OP_FLIPUD, ROTATE, SCALE, SHEAR, TRANSLATE_X, TRANSLATE_Y, _PRESETS, AugmentParams,  # noqa: F401
+                     _translate, forward_matrices, inverse_matrices, kernel_params, sample_params, upload_params)
 from .photometric import (PHOTOMETRIC_PRESET, PhotoProgram, emboss_weights, gaussian_weights, photometric_aug,  # noqa: F401
                           sample_program, sharpen_weights, upload_program)
-from .geometric import (AUG2_DEVICE_PRESET, HEAVY_DEVICE_PRESET, GeoProgram, HeavyPlan, geometric_aug, heavy_aug,  # noqa: F401
-                        sample_geo_program, sample_heavy_plan, upload_geo_program)
-from .stylize import (AUG2_CONNECTED_PRESET, AUG2_FULL_PRESET, HEAVY_CONNECTED_PRESET, HEAVY_FULL_PRESET, StyleProgram,  # noqa: F401
-                      directed_edge_weights, edge_detect_weights, sample_style_program, simplex_grid, stylize_aug, superpixel_grid,
+from .geometric import GeoProgram, geometric_aug, upload_geo_program  # noqa: F401
+from .stylize import (StyleProgram, directed_edge_weights, edge_detect_weights, simplex_grid, stylize_aug, superpixel_grid,  # noqa: F401
                       superpixel_min_size, upload_style_program)
 from .histmatch import HistReference, HistReferenceBank, match_histograms, reference_tables  # noqa: F401
-from .croppad import (AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, MODE_NAMES, CropPadProgram, crop_pad_aug,  # noqa: F401
-                      upload_crop_pad_program)
-
-OP_FLIPLR, OP_FLIPUD, OP_AFFINE = 0, 1, 2
-
-HEAVY_MESSAGE = ("The heavy pipeline (`augmentation`: Superpixels, median blur, elastic, piecewise affine, hue/saturation ...) "
-                 "is out of scope.")
-
-# (p_fliplr, p_flipud, p_affine): data_generator_mmwhs.py:89-94, data_generator_mscmrseg.py:136-142
-_PRESETS = {"mmwhs_light": (0.2, 0.2, 0.3), "mscmrseg_simple": (0.3, 0.3, 0.45)}
-# shared by both pipelines (data_generator_mmwhs.py:95-100, data_generator_mscmrseg.py:143-150)
-SCALE = (0.8, 1.2)
-TRANSLATE_X = (-0.1, 0.05)
-TRANSLATE_Y = (-0.1, 0.1)
-ROTATE = (-10.0, 10.0)
-SHEAR = (-12.0, 12.0)
-
-
-@dataclass
-class AugmentParams:
-    """Per-sample parameters (numpy arrays of length B) and the one application order of the batch: ``op_order`` lists
-    ``OP_FLIPLR``, ``OP_FLIPUD``, ``OP_AFFINE`` in the order they are applied (``random_order=True`` draws one order per
-    batch).  ``translate_*`` are fractions of the width / height, ``rotate`` and ``shear`` degrees."""
-    flip_lr: np.ndarray
-    flip_ud: np.ndarray
-    affine_on: np.ndarray
-    scale_x: np.ndarray
-    scale_y: np.ndarray
-    translate_x: np.ndarray
-    translate_y: np.ndarray
-    rotate: np.ndarray
-    shear: np.ndarray
-    order: np.ndarray
-    cval: np.ndarray
-    op_order: Tuple[int, int, int] = field(default=(OP_FLIPLR, OP_FLIPUD, OP_AFFINE))
-
-    @property
-    def batch(self) -> int:
-        return len(self.flip_lr)
-
-    @staticmethod
-    def identity(batch: int) -> "AugmentParams":
-        z, o = np.zeros(batch, dtype=np.float64), np.ones(batch, dtype=np.float64)
-        f = np.zeros(batch, dtype=bool)
-        i = np.zeros(batch, dtype=np.int64)
-        return AugmentParams(f.copy(), f.copy(), f.copy(), o.copy(), o.copy(), z.copy(), z.copy(), z.copy(), z.copy(), i.copy(),
-                             i.copy())
-
-    def is_identity(self) -> bool:
-        return not (np.any(self.flip_lr) or np.any(self.flip_ud) or np.any(self.affine_on))
-
-    def validate(self) -> None:
-        b = self.batch
-        for name in ("flip_ud", "affine_on", "scale_x", "scale_y", "translate_x", "translate_y", "rotate", "shear", "order",
-                     "cval"):
-            if len(getattr(self, name)) != b:
-                raise ValueError("AugmentParams.%s has %d entries, flip_lr has %d" % (name, len(getattr(self, name)), b))
-        if sorted(int(o) for o in self.op_order) != [OP_FLIPLR, OP_FLIPUD, OP_AFFINE]:
-            raise ValueError("AugmentParams.op_order must be a permutation of (0, 1, 2), got %r" % (tuple(self.op_order),))
-        order, cval = np.asarray(self.order), np.asarray(self.cval)
-        if np.any((order != 0) & (order != 1)):
-            raise ValueError("AugmentParams.order must be 0 or 1")
-        if np.any((cval < 0) | (cval > 255)) or np.any(cval != np.floor(cval)):
-            raise ValueError("AugmentParams.cval must be an integer in [0, 255]")
-
-
-def sample_params(batch: int, preset: str, rng: np.random.Generator) -> AugmentParams:
-    """Draw the parameters of one batch.  ``preset``: ``"mmwhs_light"`` (flips 0.2 / 0.2, affine with p = 0.3) or
-    ``"mscmrseg_simple"`` (0.3 / 0.3, p = 0.45); both: scale 0.8-1.2 per axis, translate x in (-0.1, 0.05) and y in
-    (-0.1, 0.1), rotate +/-10, shear +/-12 degrees, order from {0, 1}, cval from 0..255, one operation order per batch.
-    (imgaug's own parameter stream is not reproduced: parity unpinned.)"""
-    if preset == "heavy":
-        raise NotImplementedError(HEAVY_MESSAGE)
-    if preset not in _PRESETS:
-        raise ValueError("unknown augmentation preset %r (have: %s)" % (preset, ", ".join(sorted(_PRESETS))))
-    p_lr, p_ud, p_aff = _PRESETS[preset]
-    op_order = tuple(int(i) for i in rng.permutation(3))
-    u = lambda lo_hi: rng.uniform(lo_hi[0], lo_hi[1], batch)
-    return AugmentParams(flip_lr=rng.random(batch) < p_lr, flip_ud=rng.random(batch) < p_ud, affine_on=rng.random(batch) < p_aff,
-                         scale_x=u(SCALE), scale_y=u(SCALE), translate_x=u(TRANSLATE_X), translate_y=u(TRANSLATE_Y),
-                         rotate=u(ROTATE), shear=u(SHEAR), order=rng.integers(0, 2, batch), cval=rng.integers(0, 256, batch),
-                         op_order=op_order)
-
-
-def _translate(tx, ty):
-    return np.array([[1.0, 0.0, tx], [0.0, 1.0, ty], [0.0, 0.0, 1.0]], dtype=np.float64)
-
-
-def forward_matrices(params: AugmentParams, h: int, w: int) -> np.ndarray:
-    """float64 ``[B,3,3]``: source pixel (x, y, 1) -> output pixel, the operations multiplied in application order."""
-    params.validate()
-    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
-    out = np.empty((params.batch, 3, 3), dtype=np.float64)
-    for i in range(params.batch):
-        m = np.eye(3, dtype=np.float64)
-        for op in params.op_order:
-            if op == OP_FLIPLR and params.flip_lr[i]:
-                m = np.array([[-1.0, 0.0, w - 1.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]) @ m
-            elif op == OP_FLIPUD and params.flip_ud[i]:
-                m = np.array([[1.0, 0.0, 0.0], [0.0, -1.0, h - 1.0], [0.0, 0.0, 1.0]]) @ m
-            elif op == OP_AFFINE and params.affine_on[i]:
-                r, s = math.radians(float(params.rotate[i])), math.radians(float(params.shear[i]))
-                rot = np.array([[math.cos(r), -math.sin(r), 0.0], [math.sin(r), math.cos(r), 0.0], [0.0, 0.0, 1.0]])
-                sh = np.array([[1.0, math.tan(s), 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
-                sc = np.diag([float(params.scale_x[i]), float(params.scale_y[i]), 1.0])
-                a = _translate(cx + float(params.translate_x[i]) * w, cy + float(params.translate_y[i]) * h) @ rot @ sh @ sc \
-                    @ _translate(-cx, -cy)
-                m = a @ m
-        out[i] = m
-    return out
-
-
-def inverse_matrices(params: AugmentParams, h: int, w: int) -> np.ndarray:
-    """float64 ``[B,2,3]``: output pixel (x, y) -> source coordinate, what the kernel consumes.  A singular map (a zero
-    scale, a 90 degree shear) raises ``ValueError``."""
-    fwd = forward_matrices(params, h, w)
-    out = np.empty((params.batch, 2, 3), dtype=np.float64)
-    for i, m in enumerate(fwd):
-        det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
-        if not np.all(np.isfinite(m)) or not abs(det) > 1e-12:
-            raise ValueError("augmentation matrix of sample %d is singular (determinant %r)" % (i, det))
-        out[i] = np.linalg.inv(m)[:2]
-    return out
-
-
-def kernel_params(params: AugmentParams, h: int, w: int):
-    """(inverse matrices float64 [B,2,3], order int32 [B], cval int32 [B]) as the kernel takes them: ``order`` and ``cval``
-    only matter where an affine is applied (a flip maps integer pixels to integer pixels), so they are 0 elsewhere."""
-    inv = inverse_matrices(params, h, w)
-    on = np.asarray(params.affine_on, dtype=bool)
-    order = np.where(on, np.asarray(params.order), 0).astype(np.int32)
-    cval = np.where(on, np.asarray(params.cval), 0).astype(np.int32)
-    return inv, order, cval
-
-
-def upload_params(params: Optional[AugmentParams], batch: int, h: int, w: int, device: torch.device):
-    """Validate on the host, then move the kernel's parameter arrays through pinned, non-blocking copies (no
-    synchronisation)."""
-    if params is None:
-        params = AugmentParams.identity(batch)
-    if params.batch != batch:
-        raise ValueError("AugmentParams for %d samples, batch of %d" % (params.batch, batch))
-    inv, order, cval = kernel_params(params, h, w)
-
-    def put(a):
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        if device.type == "cuda":
-            t = t.pin_memory()
-        return t.to(device, non_blocking=True)
-    return put(inv), put(order), put(cval)
-
-
-def _labels(masks: torch.Tensor) -> torch.Tensor:
-    if masks.dim() == 4 and masks.shape[-1] == 1:
-        masks = masks[..., 0]
-    return masks.to(torch.int32)
+from .croppad import MODE_NAMES, CropPadProgram, crop_pad_aug, upload_crop_pad_program  # noqa: F401
+from .heavy import (AUG2_CONNECTED_PRESET, AUG2_DEVICE_PRESET, AUG2_FULL_PRESET, AUG2_REFPAD_PRESET, HEAVY_CONNECTED_PRESET,  # noqa: F401
+                    HEAVY_DEVICE_PRESET, HEAVY_FULL_PRESET, HEAVY_REFPAD_PRESET, HeavyPlan, _check_preset, heavy_aug,
+                    sample_geo_program, sample_heavy_plan, sample_style_program)
 
 
 def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optional[AugmentParams], num_classes: int = 5,
@@ -256,7 +107,7 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
         if rescale == "minmax" or images_hwc.dtype != torch.uint8:
             raise TypeError("augment_batch: a heavy plan takes uint8 images (rescale='div255' or None)")
         images_hwc, masks = heavy_aug(images_hwc, masks, heavy)
-    lab = _labels(masks)
+    lab = as_labels(masks)
     b, h, w, _ = images_hwc.shape
     dev = images_hwc.device
     if photometric is not None:
@@ -301,12 +152,12 @@ def light_aug(images: torch.Tensor, masks: Optional[torch.Tensor] = None, params
         raise TypeError("light_aug: uint8 [B,H,W,C] images")
     b, h, w, _ = images.shape
     inv, order, cval = upload_params(params, b, h, w, images.device)
-    lab = None if masks is None else _labels(masks)
+    lab = as_labels(masks)
     out = K.augment_assemble(images, lab, inv, order, cval, 2, 0, K.AUG_NONE, None, want_images=False, want_onehot=False,
                              want_labels=lab is not None, want_u8=True)
     if masks is None:
         return out["images_u8"]
-    return out["images_u8"], out["labels"].to(masks.dtype).reshape(masks.shape)
+    return out["images_u8"], like_masks(out["labels"], masks)
 
 
 def simple_aug(image: torch.Tensor, mask: Optional[torch.Tensor], params: Optional[AugmentParams] = None):
@@ -348,9 +199,7 @@ class AugmentedBatches:
         if preset == "heavy" or photometric_preset == "heavy" or heavy_preset == "heavy":
             raise NotImplementedError(HEAVY_MESSAGE)
         if heavy_preset is not None:
-            if heavy_preset not in (HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET, HEAVY_FULL_PRESET, AUG2_FULL_PRESET,
-                                    HEAVY_REFPAD_PRESET, AUG2_REFPAD_PRESET, HEAVY_CONNECTED_PRESET, AUG2_CONNECTED_PRESET):
-                raise ValueError("unknown heavy preset %r" % (heavy_preset,))
+            _check_preset(heavy_preset)
             if preset is not None or photometric_preset is not None:
                 raise ValueError("AugmentedBatches: a heavy preset is the whole recipe (preset and photometric_preset must be None)")
             if rescale == "minmax":

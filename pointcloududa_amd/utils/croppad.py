@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from ._program import as_labels, like_masks, upload
 
 OP_COPY, OP_CROP_AND_PAD = 0, 1
 (MODE_CONSTANT, MODE_EDGE, MODE_LINEAR_RAMP, MODE_MAXIMUM, MODE_MEAN, MODE_MEDIAN, MODE_MINIMUM, MODE_REFLECT, MODE_SYMMETRIC,
@@ -37,7 +38,6 @@ OP_COPY, OP_CROP_AND_PAD = 0, 1
 MODE_NAMES = ("CONSTANT", "EDGE", "LINEAR_RAMP", "MAXIMUM", "MEAN", "MEDIAN", "MINIMUM", "REFLECT", "SYMMETRIC", "WRAP")
 IARGS = 6
 MAX_PAD = 64
-HEAVY_REFPAD_PRESET, AUG2_REFPAD_PRESET = "heavy_refpad_device", "mscmrseg_aug2_refpad_device"
 
 
 @dataclass
@@ -93,18 +93,13 @@ class CropPadProgram:
         self.validate(h, w)
         return self.opcode, self.iarg
 
+    def apply(self, images, masks):
+        return crop_pad_aug(images, masks, self)
+
 
 def upload_crop_pad_program(program: CropPadProgram, batch: int, h: int, w: int, device: torch.device):
     """Validate on the host, then move the kernel's arrays through pinned, non-blocking copies (no synchronisation)."""
-    if program.batch != batch:
-        raise ValueError("CropPadProgram for %d samples, batch of %d" % (program.batch, batch))
-
-    def put(a):
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        if device.type == "cuda":
-            t = t.pin_memory()
-        return t.to(device, non_blocking=True)
-    return tuple(put(a) for a in program.kernel_arrays(h, w))
+    return upload(program, batch, h, w, device=device)
 
 
 def crop_pad_aug(images: torch.Tensor, masks: Optional[torch.Tensor], program: Optional[CropPadProgram] = None, out=None):
@@ -118,10 +113,5 @@ def crop_pad_aug(images: torch.Tensor, masks: Optional[torch.Tensor], program: O
         raise TypeError("crop_pad_aug: uint8 [B,H,W,C] images")
     b, h, w, _ = images.shape
     up = upload_crop_pad_program(program, b, h, w, images.device)
-    lab = None
-    if masks is not None:
-        lab = (masks[..., 0] if masks.dim() == 4 and masks.shape[-1] == 1 else masks).to(torch.int32)
-    res, lab_out = K.crop_pad(images, lab, *up, out=out)
-    if masks is None:
-        return res, None
-    return res, lab_out.to(masks.dtype).reshape(masks.shape)
+    res, lab_out = K.crop_pad(images, as_labels(masks), *up, out=out)
+    return res, like_masks(lab_out, masks)

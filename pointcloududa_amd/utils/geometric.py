@@ -42,19 +42,16 @@ keeps raising ``NotImplementedError``.  ``Superpixels``, ``SimplexNoiseAlpha(Edg
 ``"mscmrseg_aug2_full_device"`` of ``sample_heavy_plan`` interleave them with the entries of this file and f7's."""
 from __future__ import annotations
 
-from dataclasses import dataclass, field
-from typing import List, Optional, Union
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
 
 from .. import kernels as K
-from . import photometric as P
-from . import stylize as St
-from .croppad import AUG2_REFPAD_PRESET, HEAVY_REFPAD_PRESET, CropPadProgram, crop_pad_aug
-from .photometric import PhotoProgram, gaussian_weights, photometric_aug
-from .stylize import (AUG2_CONNECTED_PRESET, AUG2_FULL_PRESET, HEAVY_CONNECTED_PRESET, HEAVY_FULL_PRESET, StyleProgram,
-                      stylize_aug)
+from ._program import SlotProgram, as_labels, like_masks, upload
+from .affine import AugmentParams, inverse_matrices
+from .photometric import gaussian_weights, photometric_aug  # noqa: F401  (photometric_aug: importable from here as before)
 
 OP_NOP, OP_HOMOGRAPHY, OP_ELASTIC, OP_PIECEWISE = range(4)
 OP_NAMES = ("NOP", "HOMOGRAPHY", "ELASTIC", "PIECEWISE_AFFINE")
@@ -62,7 +59,6 @@ MODE_CONSTANT, MODE_EDGE, MODE_REFLECT, MODE_SYMMETRIC, MODE_WRAP = range(5)
 MODE_NAMES = ("CONSTANT", "EDGE", "REFLECT", "SYMMETRIC", "WRAP")
 MAX_SLOTS, IARGS, FARGS = 8, 4, 32
 MAX_ELASTIC_RADIUS = 4
-HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET = "heavy_device", "mscmrseg_aug2_device"
 
 # data_generator_mscmrseg.py:25-43, 74-76
 FLIP_LR_P, FLIP_UD_P, SOMETIMES_P = 0.5, 0.2, 0.5
@@ -111,38 +107,20 @@ def control_grid(g: int, h: int, w: int):
 
 
 @dataclass
-class GeoProgram:
+class GeoProgram(SlotProgram):
     """``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,4]``, ``farg`` float64 ``[B,S,32]``, ``seed`` uint64 ``[B,S]`` (numpy, on
     the host; the module docstring says what each opcode reads).  The ``set_*`` methods encode slot ``s`` of sample ``i``."""
     opcode: np.ndarray
     iarg: np.ndarray
     farg: np.ndarray
     seed: np.ndarray
-
-    @property
-    def batch(self) -> int:
-        return self.opcode.shape[0]
-
-    @property
-    def slots(self) -> int:
-        return self.opcode.shape[1]
-
-    @staticmethod
-    def identity(batch: int, slots: int = 1) -> "GeoProgram":
-        return GeoProgram(np.zeros((batch, slots), dtype=np.int32), np.zeros((batch, slots, IARGS), dtype=np.int32),
-                          np.zeros((batch, slots, FARGS), dtype=np.float64), np.zeros((batch, slots), dtype=np.uint64))
-
-    def is_identity(self) -> bool:
-        return not np.any(self.opcode != OP_NOP)
+    COLUMNS = (("iarg", np.int32, IARGS), ("farg", np.float64, FARGS))
 
     def _clear(self, i, s, op, order=0, mode=MODE_CONSTANT, cval=0):
         self.opcode[i, s] = op
         self.iarg[i, s] = (int(order), int(mode), int(cval), 0)
         self.farg[i, s] = 0.0
         self.seed[i, s] = 0
-
-    def set_nop(self, i, s):
-        self._clear(i, s, OP_NOP)
 
     def set_homography(self, i, s, matrix, order=1, mode=MODE_CONSTANT, cval=0):
         """``matrix``: the INVERSE 3x3 map, output pixel -> source coordinate"""
@@ -157,10 +135,9 @@ class GeoProgram:
 
     def set_affine(self, i, s, h, w, scale_x=1.0, scale_y=1.0, translate_x=0.0, translate_y=0.0, rotate=0.0, shear=0.0, order=1,
                    mode=MODE_CONSTANT, cval=0):
-        """f6's matrix convention (``utils/augment.py``: ``A = T(c + t) . R . Sh . S . T(-c)`` about the image centre,
+        """f6's matrix convention (``utils/affine.py``: ``A = T(c + t) . R . Sh . S . T(-c)`` about the image centre,
         ``translate_*`` fractions of the width / height, ``rotate`` / ``shear`` degrees), its inverse as a homography, plus
         the border mode"""
-        from .augment import AugmentParams, inverse_matrices
         p = AugmentParams.identity(1)
         p.affine_on[:] = True
         p.scale_x[:], p.scale_y[:], p.translate_x[:], p.translate_y[:] = scale_x, scale_y, translate_x, translate_y
@@ -207,22 +184,10 @@ class GeoProgram:
         radius above 4, a negative alpha or weights that are not normalised, G outside 2..4, a homography with
         ``|det| <= 1e-12`` or -- when ``h`` and ``w`` are given -- a denominator that is not positive at the four output
         corners; ``h`` or ``w`` below 2."""
-        op, ia, fa, sd = self.opcode, self.iarg, self.farg, self.seed
-        if getattr(op, "ndim", 0) != 2 or op.dtype != np.int32:
-            raise ValueError("GeoProgram.opcode must be int32 [B,S]")
-        b, s = op.shape
-        if s > MAX_SLOTS:
-            raise ValueError("GeoProgram: %d slots, at most %d" % (s, MAX_SLOTS))
-        for name, a, shape, dt in (("iarg", ia, (b, s, IARGS), np.int32), ("farg", fa, (b, s, FARGS), np.float64),
-                                   ("seed", sd, (b, s), np.uint64)):
-            if getattr(a, "shape", None) != shape or a.dtype != dt:
-                raise ValueError("GeoProgram.%s must be %s %r" % (name, np.dtype(dt).name, list(shape)))
-        if np.any((op < 0) | (op > OP_PIECEWISE)):
-            raise ValueError("GeoProgram.opcode: unknown opcode")
+        self._check_arrays(OP_PIECEWISE)
+        op, ia, fa = self.opcode, self.iarg, self.farg
         if (h is not None and h < 2) or (w is not None and w < 2):
             raise ValueError("GeoProgram: H and W must be at least 2")
-        if not np.all(np.isfinite(fa)):
-            raise ValueError("GeoProgram.farg must be finite")
         live = op != OP_NOP
         if np.any((ia[live][:, 0] != 0) & (ia[live][:, 0] != 1)):
             raise ValueError("GeoProgram: order must be 0 or 1")
@@ -258,24 +223,13 @@ class GeoProgram:
         self.validate(h, w)
         return self.opcode, self.iarg, self.farg, self.seed.view(np.int64)
 
+    def apply(self, images, masks):
+        return geometric_aug(images, masks, self)
+
 
 def upload_geo_program(program: GeoProgram, batch: int, h: int, w: int, device: torch.device):
     """Validate on the host, then move the kernel's arrays through pinned, non-blocking copies (no synchronisation)."""
-    if program.batch != batch:
-        raise ValueError("GeoProgram for %d samples, batch of %d" % (program.batch, batch))
-
-    def put(a):
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        if device.type == "cuda":
-            t = t.pin_memory()
-        return t.to(device, non_blocking=True)
-    return tuple(put(a) for a in program.kernel_arrays(h, w))
-
-
-def _labels(masks: torch.Tensor) -> torch.Tensor:
-    if masks.dim() == 4 and masks.shape[-1] == 1:
-        masks = masks[..., 0]
-    return masks.to(torch.int32)
+    return upload(program, batch, h, w, device=device)
 
 
 def geometric_aug(images: torch.Tensor, masks: Optional[torch.Tensor], program: Optional[GeoProgram] = None):
@@ -288,79 +242,11 @@ def geometric_aug(images: torch.Tensor, masks: Optional[torch.Tensor], program: 
         raise TypeError("geometric_aug: uint8 [B,H,W,C] images")
     b, h, w, _ = images.shape
     up = upload_geo_program(program, b, h, w, images.device)
-    lab = None if masks is None else _labels(masks)
-    out, lab_out = K.geometric(images, lab, *up)
-    if masks is None:
-        return out, None
-    return out, lab_out.to(masks.dtype).reshape(masks.shape)
+    out, lab_out = K.geometric(images, as_labels(masks), *up)
+    return out, like_masks(lab_out, masks)
 
 
 # ------------------------------------------------------------------------------------------------ sampling
-_PHOTO_BLOCK = tuple(("p", e) for e in range(9))
-# the reference's list order: Superpixels, blur, sharpen, emboss, SimplexNoiseAlpha, noise, dropout, invert, add, hue, ...
-_FULL_BLOCK = ((("s", St.ENTRY_SUPERPIXELS),) + _PHOTO_BLOCK[:3] + (("s", St.ENTRY_NOISE_ALPHA),) + _PHOTO_BLOCK[3:7] +
-               (("s", St.ENTRY_HUE),) + _PHOTO_BLOCK[7:])
-_PRESETS = {
-    # data_generator_mscmrseg.py:23-82 minus Superpixels, SimplexNoiseAlpha, AddToHueAndSaturation
-    HEAVY_DEVICE_PRESET: dict(
-        outer=(("g", ENTRY_FLIPLR), ("g", ENTRY_FLIPUD), ("g", ENTRY_CROP_AND_PAD), ("g", ENTRY_AFFINE), "block"),
-        block=_PHOTO_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
-    # data_generator_mscmrseg.py:89-130 minus the same three
-    AUG2_DEVICE_PRESET: dict(outer=(("g", ENTRY_CROP_AND_PAD), "block"), block=_PHOTO_BLOCK),
-    # data_generator_mscmrseg.py:23-82, all fifteen SomeOf entries (f9)
-    HEAVY_FULL_PRESET: dict(
-        outer=(("g", ENTRY_FLIPLR), ("g", ENTRY_FLIPUD), ("g", ENTRY_CROP_AND_PAD), ("g", ENTRY_AFFINE), "block"),
-        block=_FULL_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
-    # data_generator_mscmrseg.py:89-130, all twelve
-    AUG2_FULL_PRESET: dict(outer=(("g", ENTRY_CROP_AND_PAD), "block"), block=_FULL_BLOCK),
-    # the two full recipes with CropAndPad over all ten modes of numpy.pad, a CropPadProgram stage of its own (f14)
-    HEAVY_REFPAD_PRESET: dict(
-        outer=(("g", ENTRY_FLIPLR), ("g", ENTRY_FLIPUD), ("c", ENTRY_CROP_AND_PAD), ("g", ENTRY_AFFINE), "block"),
-        block=_FULL_BLOCK + (("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE))),
-    AUG2_REFPAD_PRESET: dict(outer=(("c", ENTRY_CROP_AND_PAD), "block"), block=_FULL_BLOCK),
-}
-# the two _refpad_ recipes, draw for draw, with connected superpixels: min_size = superpixel_min_size(..) on every Superpixels
-# slot (f9b)
-_PRESETS[HEAVY_CONNECTED_PRESET] = dict(_PRESETS[HEAVY_REFPAD_PRESET], connected=True)
-_PRESETS[AUG2_CONNECTED_PRESET] = dict(_PRESETS[AUG2_REFPAD_PRESET], connected=True)
-_SOMETIMES = {("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE), ("s", St.ENTRY_SUPERPIXELS)}
-_OUTER_P = {ENTRY_FLIPLR: FLIP_LR_P, ENTRY_FLIPUD: FLIP_UD_P, ENTRY_CROP_AND_PAD: SOMETIMES_P, ENTRY_AFFINE: SOMETIMES_P}
-
-
-def _check_preset(preset):
-    if preset == "heavy":
-        from .augment import HEAVY_MESSAGE
-        raise NotImplementedError(HEAVY_MESSAGE)
-    if preset not in _PRESETS:
-        raise ValueError("unknown heavy preset %r (have: %s)" % (preset, ", ".join(sorted(_PRESETS))))
-    return _PRESETS[preset]
-
-
-def _select(b, spec, rng):
-    """-> (entries in application order, on bool [B, len(entries)]): one outer and one inner order per batch
-    (``random_order=True`` as f6 and f7 draw it); ``SomeOf((0, 5))`` picks a uniform count of distinct block entries per
-    sample, and the three warps inside the block (and, in the full presets, Superpixels) sit behind ``sometimes(0.5)``"""
-    outer, block = spec["outer"], spec["block"]
-    outer_order, inner_order = rng.permutation(len(outer)), rng.permutation(len(block))
-    count = rng.integers(SOMEOF_COUNT[0], SOMEOF_COUNT[1] + 1, b)
-    rank = np.argsort(np.argsort(rng.random((b, len(block))), axis=1), axis=1)
-    chosen = rank < count[:, None]
-    for k, entry in enumerate(block):
-        if entry in _SOMETIMES:
-            chosen[:, k] &= rng.random(b) < SOMETIMES_P
-    outer_on = {k: rng.random(b) < _OUTER_P[e[1]] for k, e in enumerate(outer) if e != "block"}
-    entries, on = [], []
-    for k in outer_order:
-        if outer[k] == "block":
-            for q in inner_order:
-                entries.append(block[q])
-                on.append(chosen[:, q])
-        else:
-            entries.append(outer[k])
-            on.append(outer_on[k])
-    return entries, np.stack(on, axis=1)
-
-
 def _draw_geo(b, rng, h, w):
     u = lambda lo_hi, *shape: rng.uniform(lo_hi[0], lo_hi[1], (b,) + shape)
     g = PIECEWISE_GRID
@@ -393,174 +279,3 @@ def _encode_geo(prog, i, s, entry, d, h, w):
         prog.set_piecewise(i, s, h, w, d["pw_dx"][i], d["pw_dy"][i])
     else:
         prog.set_perspective(i, s, h, w, d["jitter"][i])
-
-
-def _draw_photo(b, rng):
-    """the parameters of f7's nine entries, drawn as ``photometric.sample_program`` draws them"""
-    u = lambda lo_hi, *shape: rng.uniform(lo_hi[0], lo_hi[1], (b,) + shape)
-    return dict(
-        blur_kind=rng.integers(0, 3, b), sigma=u(P.SIGMA), avg_k=rng.integers(P.AVERAGE_K[0], P.AVERAGE_K[1] + 1, b),
-        med_k=2 * rng.integers(P.MEDIAN_K[0] // 2, P.MEDIAN_K[1] // 2 + 1, b) + 1,
-        sh_a=u(P.SHARPEN_ALPHA), sh_l=u(P.SHARPEN_LIGHTNESS), em_a=u(P.EMBOSS_ALPHA), em_s=u(P.EMBOSS_STRENGTH),
-        no_s=u(P.NOISE_SCALE), no_pc=rng.random(b) < P.NOISE_PER_CHANNEL,
-        dr_kind=rng.integers(0, 2, b), dr_p=u(P.DROPOUT_P), dr_pc=rng.random(b) < P.DROPOUT_PER_CHANNEL,
-        co_p=u(P.COARSE_P), co_s=u(P.COARSE_SIZE), co_pc=rng.random(b) < P.COARSE_PER_CHANNEL,
-        inv=rng.random((b, P.IARGS)) < P.INVERT_P,
-        add_pc=rng.random(b) < P.ADD_PER_CHANNEL, add_v=rng.integers(P.ADD[0], P.ADD[1] + 1, (b, P.IARGS)),
-        mul_pc=rng.random(b) < P.MULTIPLY_PER_CHANNEL, mul_v=u(P.MULTIPLY, P.IARGS), gray=u(P.GRAY_ALPHA),
-        seed=rng.integers(0, 2 ** 64, (b, 9), dtype=np.uint64))
-
-
-def _encode_photo(prog, i, s, entry, d):
-    sd = d["seed"][i, entry]
-    if entry == P.ENTRY_BLUR:
-        if d["blur_kind"][i] == 0:
-            prog.set_gaussian_blur(i, s, d["sigma"][i])
-        elif d["blur_kind"][i] == 1:
-            prog.set_average_blur(i, s, d["avg_k"][i])
-        else:
-            prog.set_median_blur(i, s, d["med_k"][i])
-    elif entry == P.ENTRY_SHARPEN:
-        prog.set_conv3x3(i, s, P.sharpen_weights(d["sh_a"][i], d["sh_l"][i]))
-    elif entry == P.ENTRY_EMBOSS:
-        prog.set_conv3x3(i, s, P.emboss_weights(d["em_a"][i], d["em_s"][i]))
-    elif entry == P.ENTRY_NOISE:
-        prog.set_gaussian_noise(i, s, d["no_s"][i], d["no_pc"][i], sd)
-    elif entry == P.ENTRY_DROPOUT:
-        if d["dr_kind"][i] == 0:
-            prog.set_dropout(i, s, d["dr_p"][i], d["dr_pc"][i], sd)
-        else:
-            prog.set_coarse_dropout(i, s, d["co_p"][i], d["co_s"][i], d["co_pc"][i], sd)
-    elif entry == P.ENTRY_INVERT:
-        prog.set_invert(i, s, d["inv"][i])
-    elif entry == P.ENTRY_ADD:
-        prog.set_add(i, s, d["add_v"][i] if d["add_pc"][i] else d["add_v"][i, 0])
-    elif entry == P.ENTRY_MULTIPLY:
-        prog.set_multiply(i, s, d["mul_v"][i] if d["mul_pc"][i] else d["mul_v"][i, 0])
-    else:
-        prog.set_grayscale(i, s, d["gray"][i])
-
-
-def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> GeoProgram:
-    """Draw the GEOMETRIC entries of one batch of a preset for ``h x w`` images, as one program (the photometric entries
-    of the recipe are skipped: ``sample_heavy_plan`` interleaves both).
-
-    ``"heavy_device"`` (``data_generator_mscmrseg.py:23-82``), 7 slots: Fliplr p = 0.5, Flipud p = 0.2, ``sometimes``
-    CropAndPad (percent -0.05..0.1 per side independently, a border mode of the five, cval 0..255), ``sometimes`` Affine
-    (scale 0.8-1.2 per axis, translate +/-0.2, rotate +/-45, shear +/-16 degrees, order {0, 1}, cval 0..255, a border mode of the
-    five) and, out of the ``SomeOf((0, 5))`` block of twelve built entries, ``sometimes`` ElasticTransformation (alpha
-    0.5-3.5, sigma 0.25), PiecewiseAffine (G = 4, jitter N(0, scale size), scale 0.01-0.05) and PerspectiveTransform (jitter
-    N(0, scale), scale 0.01-0.1, clipped to 0.45), in one random order per batch.  ``"mscmrseg_aug2_device"``
-    (``:89-130``), 1 slot: ``sometimes`` CropAndPad.  On ``"heavy_refpad_device"`` the six entries without CropAndPad (which is
-    a ``CropPadProgram`` there, f14); ``"mscmrseg_aug2_refpad_device"`` holds no geometric entry (0 slots).  imgaug's own
-    parameter stream is not reproduced (parity unpinned)."""
-    spec = _check_preset(preset)
-    entries, on = _select(batch, spec, rng)
-    d = _draw_geo(batch, rng, h, w)
-    geo = [k for k, e in enumerate(entries) if e[0] == "g"]
-    prog = GeoProgram.identity(batch, len(geo))
-    for i in range(batch):
-        s = 0
-        for k in geo:
-            if on[i, k]:
-                _encode_geo(prog, i, s, entries[k][1], d, h, w)
-                s += 1
-    return prog
-
-
-@dataclass
-class HeavyPlan:
-    """The ordered stages of one batch: ``PhotoProgram``, ``GeoProgram``, (f9) ``StyleProgram`` and (f14) ``CropPadProgram``
-    stages, no two neighbours of one kind; every stage covers the whole batch (a sample without an active entry in a stage
-    holds NOPs there)."""
-    batch: int
-    stages: List[Union[PhotoProgram, GeoProgram, StyleProgram, CropPadProgram]] = field(default_factory=list)
-
-    def is_identity(self) -> bool:
-        return all(st.is_identity() for st in self.stages)
-
-
-def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> HeavyPlan:
-    """Draw the whole recipe of one batch: photometric and geometric entries interleaved by ``random_order=True`` (one outer
-    and one inner order per batch).  Consecutive photometric entries form one ``PhotoProgram``, consecutive geometric entries
-    one ``GeoProgram``; a stage has as many slots as its busiest sample uses, a stage nobody uses is dropped.
-
-    ``"heavy_device"``: ``augmentation`` minus Superpixels, SimplexNoiseAlpha and AddToHueAndSaturation -- the outer order is
-    over {Fliplr, Flipud, CropAndPad, Affine, SomeOf block}; ``SomeOf`` draws 0..5 of the twelve built entries (f7's nine and
-    the three warps, each warp behind ``sometimes(0.5)``).  ``"mscmrseg_aug2_device"``: ``augmentation2`` minus the same
-    three -- ``sometimes(CropAndPad)`` and f7's nine-entry block, in random order.
-
-    ``"heavy_full_device"`` and ``"mscmrseg_aug2_full_device"`` (f9): the same two recipes with all fifteen / twelve ``SomeOf``
-    entries -- ``sometimes`` Superpixels, SimplexNoiseAlpha and AddToHueAndSaturation (``utils/stylize.py``) sit in the block
-    at the reference's list positions, and consecutive stylize entries form one ``StyleProgram``.
-
-    ``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` (f14): the two full recipes with CropAndPad as a
-    ``CropPadProgram`` stage of its own (``utils/croppad.py``), its mode uniform over the ten of ``numpy.pad``.  Everything the
-    ``_full_`` twin draws is drawn in the same order, then one ``rng.integers(0, 10, batch)`` for the mode; the sides and cval
-    are ``_draw_geo``'s ``crop`` / ``crop_cval`` (its ``crop_mode`` draw is consumed and unused).
-
-    ``"heavy_connected_device"`` and ``"mscmrseg_aug2_connected_device"`` (f9b): the ``_refpad_`` presets, draw for draw, with
-    ``min_size = superpixel_min_size(gy, gx, h, w)`` in ``iarg[5]`` of every Superpixels slot (connected segments,
-    ``csrc/spx_connect.hip``); every other array of the plan equals the ``_refpad_`` plan of the same generator state."""
-    spec = _check_preset(preset)
-    entries, on = _select(batch, spec, rng)
-    dg, dp = _draw_geo(batch, rng, h, w), _draw_photo(batch, rng)
-    ds = St.draw_style(batch, rng) if any(e[0] == "s" for e in entries) else None
-    pad_mode = rng.integers(0, 10, batch) if any(e[0] == "c" for e in entries) else None
-    used = [k for k in range(len(entries)) if on[:, k].any()]      # (an entry nobody drew does not split a stage)
-    entries, on = [entries[k] for k in used], on[:, used]
-    plan = HeavyPlan(batch)
-    k = 0
-    while k < len(entries):
-        kind = entries[k][0]
-        e = k
-        while e < len(entries) and entries[e][0] == kind:
-            e += 1
-        used = int(on[:, k:e].sum(1).max()) if batch else 0
-        if used:
-            if kind == "c":
-                prog = CropPadProgram.identity(batch)
-            else:
-                prog = {"p": PhotoProgram, "g": GeoProgram, "s": StyleProgram}[kind].identity(batch, used)
-            for i in range(batch):
-                s = 0
-                for q in range(k, e):
-                    if on[i, q]:
-                        if kind == "p":
-                            _encode_photo(prog, i, s, entries[q][1], dp)
-                        elif kind == "s":
-                            St.encode_style(prog, i, s, entries[q][1], ds, h, w, connected=bool(spec.get("connected")))
-                        elif kind == "c":
-                            t, r, bt, l = dg["crop"][i]
-                            prog.set_crop_and_pad(i, crop_pad_pixels(t, h), crop_pad_pixels(r, w), crop_pad_pixels(bt, h),
-                                                  crop_pad_pixels(l, w), int(pad_mode[i]), int(dg["crop_cval"][i]))
-                        else:
-                            _encode_geo(prog, i, s, entries[q][1], dg, h, w)
-                        s += 1
-            plan.stages.append(prog)
-        k = e
-    return plan
-
-
-def heavy_aug(images: torch.Tensor, masks: Optional[torch.Tensor], plan: Optional[HeavyPlan] = None):
-    """Run a plan: uint8 ``[B,H,W,C]`` images and integer masks (or ``None``) on the device -> ``(images, masks)``.  ``plan``
-    is required: draw it with ``sample_heavy_plan(B, "heavy_device", rng, H, W)``."""
-    if plan is None:
-        raise TypeError("heavy_aug: plan is required (sample_heavy_plan(batch, preset, rng, h, w)); there is no silent identity")
-    if images.dtype != torch.uint8 or images.dim() != 4:
-        raise TypeError("heavy_aug: uint8 [B,H,W,C] images")
-    if plan.batch != images.shape[0]:
-        raise ValueError("HeavyPlan for %d samples, batch of %d" % (plan.batch, images.shape[0]))
-    for stage in plan.stages:
-        if isinstance(stage, PhotoProgram):
-            images = photometric_aug(images, stage)
-        elif isinstance(stage, StyleProgram):
-            images = stylize_aug(images, stage)
-        elif isinstance(stage, GeoProgram):
-            images, masks = geometric_aug(images, masks, stage)
-        elif isinstance(stage, CropPadProgram):
-            images, masks = crop_pad_aug(images, masks, stage)
-        else:
-            raise TypeError("heavy_aug: a stage is a PhotoProgram, a GeoProgram, a StyleProgram or a CropPadProgram, got %s"
-                            % type(stage).__name__)
-    return images, masks

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from ._program import to_device
 
 
 def reference_tables(reference_hwc: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -67,17 +68,11 @@ class HistReference:
 
     def __init__(self, reference_hwc: np.ndarray, device):
         ref = np.asarray(reference_hwc)
-        values, quantiles, lengths = reference_tables(ref)
+        tables = reference_tables(ref)
         self.dtype = ref.dtype
         self.channels = int(ref.shape[2])
         self.device = torch.device(device)
-
-        def put(a):
-            t = torch.from_numpy(np.ascontiguousarray(a))
-            if self.device.type == "cuda":
-                t = t.pin_memory()
-            return t.to(self.device, non_blocking=True)
-        self.values, self.quantiles, self.lengths = put(values), put(quantiles), put(lengths)
+        self.values, self.quantiles, self.lengths = to_device(tables, self.device)
 
 
 class HistReferenceBank:
@@ -169,9 +164,7 @@ class HistReferenceBank:
                 self._index_cache[batch] = (torch.arange(batch, dtype=torch.int32, device=self.device) if self.size == batch
                                             else torch.zeros(batch, dtype=torch.int32, device=self.device))
             return self._index_cache[batch]
-        host = validate_index(index, batch, self.size)
-        t = torch.from_numpy(host)
-        return (t.pin_memory() if self.device.type == "cuda" else t).to(self.device, non_blocking=True)
+        return to_device((validate_index(index, batch, self.size),), self.device)[0]
 
 
 def validate_index(index, batch: int, size: int) -> np.ndarray:

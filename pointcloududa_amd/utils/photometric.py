@@ -35,7 +35,8 @@ restatement).
 NOT in this program type: ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
 ``AddToHueAndSaturation`` (the other three ``SomeOf`` entries) live in ``utils/stylize.py`` (f9); ``"heavy"`` keeps raising (imgaug's
 parameter stream is not reproduced).  ``CropAndPad`` and the elastic / piecewise / perspective warps of the heavy ``augmentation`` pipeline move the mask:
-they live in ``utils/geometric.py`` (f8), whose ``sample_heavy_plan`` interleaves them with the operators of this file."""
+they live in ``utils/geometric.py`` (f8); ``sample_heavy_plan`` (``utils/heavy.py``) interleaves them with the operators of this
+file, whose nine entries it draws and encodes through ``draw_photo`` / ``encode_photo`` here, as ``sample_program`` does."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -45,6 +46,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from ._program import HEAVY_MESSAGE, SlotProgram, upload
 
 (OP_NOP, OP_GAUSSIAN_BLUR, OP_AVERAGE_BLUR, OP_MEDIAN_BLUR, OP_CONV3X3, OP_GAUSSIAN_NOISE, OP_DROPOUT, OP_COARSE_DROPOUT,
  OP_INVERT, OP_ADD, OP_MULTIPLY, OP_GRAYSCALE) = range(12)
@@ -109,38 +111,15 @@ def coarse_grid(size_percent: float, h: int, w: int):
 
 
 @dataclass
-class PhotoProgram:
+class PhotoProgram(SlotProgram):
     """``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,4]``, ``farg`` float64 ``[B,S,16]``, ``seed`` uint64 ``[B,S]`` (numpy,
     on the host; the module docstring says what each opcode reads).  The ``set_*`` methods encode one slot."""
     opcode: np.ndarray
     iarg: np.ndarray
     farg: np.ndarray
     seed: np.ndarray
-
-    @property
-    def batch(self) -> int:
-        return self.opcode.shape[0]
-
-    @property
-    def slots(self) -> int:
-        return self.opcode.shape[1]
-
-    @staticmethod
-    def identity(batch: int, slots: int = PRESET_SLOTS) -> "PhotoProgram":
-        return PhotoProgram(np.zeros((batch, slots), dtype=np.int32), np.zeros((batch, slots, IARGS), dtype=np.int32),
-                            np.zeros((batch, slots, FARGS), dtype=np.float64), np.zeros((batch, slots), dtype=np.uint64))
-
-    def is_identity(self) -> bool:
-        return not np.any(self.opcode != OP_NOP)
-
-    def _clear(self, i, s, op):
-        self.opcode[i, s] = op
-        self.iarg[i, s] = 0
-        self.farg[i, s] = 0.0
-        self.seed[i, s] = 0
-
-    def set_nop(self, i, s):
-        self._clear(i, s, OP_NOP)
+    COLUMNS = (("iarg", np.int32, IARGS), ("farg", np.float64, FARGS))
+    SLOTS = PRESET_SLOTS
 
     def set_gaussian_blur(self, i, s, sigma):
         wts = gaussian_weights(sigma)
@@ -206,22 +185,10 @@ class PhotoProgram:
         2..7, an even k or one outside 3..11, non-finite weights, a scale outside [0, 255], p or size_percent outside
         [0, 1], an invert mask outside 0..15, an addend outside [-255, 255], a factor outside [0, 255], alpha outside
         [0, 1], and -- when ``channels`` is given -- more than 4 channels or a grayscale slot on C other than 1 or 3."""
-        op, ia, fa, sd = self.opcode, self.iarg, self.farg, self.seed
-        if getattr(op, "ndim", 0) != 2 or op.dtype != np.int32:
-            raise ValueError("PhotoProgram.opcode must be int32 [B,S]")
-        b, s = op.shape
-        if s > MAX_SLOTS:
-            raise ValueError("PhotoProgram: %d slots, at most %d" % (s, MAX_SLOTS))
-        for name, a, shape, dt in (("iarg", ia, (b, s, IARGS), np.int32), ("farg", fa, (b, s, FARGS), np.float64),
-                                   ("seed", sd, (b, s), np.uint64)):
-            if getattr(a, "shape", None) != shape or a.dtype != dt:
-                raise ValueError("PhotoProgram.%s must be %s %r" % (name, np.dtype(dt).name, list(shape)))
-        if np.any((op < 0) | (op > OP_GRAYSCALE)):
-            raise ValueError("PhotoProgram.opcode: unknown opcode")
+        self._check_arrays(OP_GRAYSCALE)
+        op, ia, fa = self.opcode, self.iarg, self.farg
         if channels is not None and not 1 <= channels <= 4:
             raise ValueError("PhotoProgram: 1..4 channels, got %d" % channels)
-        if not np.all(np.isfinite(fa)):
-            raise ValueError("PhotoProgram.farg must be finite")
 
         def sel(code):
             m = op == code
@@ -282,6 +249,55 @@ class PhotoProgram:
                     ia[i, s, 2:4] = coarse_grid(self.farg[i, s, 1], h, w)
         return self.opcode, ia, self.farg, self.seed.view(np.int64)
 
+    def apply(self, images, masks):
+        return photometric_aug(images, self), masks
+
+
+def draw_photo(b: int, rng: np.random.Generator, seed_shape):
+    """the parameters of the nine entries for every sample of a batch, and ``seed_shape`` seeds drawn last"""
+    u = lambda lo_hi, *shape: rng.uniform(lo_hi[0], lo_hi[1], (b,) + shape)
+    return dict(
+        blur_kind=rng.integers(0, 3, b), sigma=u(SIGMA), avg_k=rng.integers(AVERAGE_K[0], AVERAGE_K[1] + 1, b),
+        med_k=2 * rng.integers(MEDIAN_K[0] // 2, MEDIAN_K[1] // 2 + 1, b) + 1,
+        sh_a=u(SHARPEN_ALPHA), sh_l=u(SHARPEN_LIGHTNESS), em_a=u(EMBOSS_ALPHA), em_s=u(EMBOSS_STRENGTH),
+        no_s=u(NOISE_SCALE), no_pc=rng.random(b) < NOISE_PER_CHANNEL,
+        dr_kind=rng.integers(0, 2, b), dr_p=u(DROPOUT_P), dr_pc=rng.random(b) < DROPOUT_PER_CHANNEL,
+        co_p=u(COARSE_P), co_s=u(COARSE_SIZE), co_pc=rng.random(b) < COARSE_PER_CHANNEL,
+        inv=rng.random((b, IARGS)) < INVERT_P,
+        add_pc=rng.random(b) < ADD_PER_CHANNEL, add_v=rng.integers(ADD[0], ADD[1] + 1, (b, IARGS)),
+        mul_pc=rng.random(b) < MULTIPLY_PER_CHANNEL, mul_v=u(MULTIPLY, IARGS), gray=u(GRAY_ALPHA),
+        seed=rng.integers(0, 2 ** 64, seed_shape, dtype=np.uint64))
+
+
+def encode_photo(prog: PhotoProgram, i: int, s: int, entry: int, d, seed) -> None:
+    """entry ``entry`` of sample ``i`` into slot ``s`` from ``draw_photo``'s ``d``; ``seed`` keys the entry if it is a random one"""
+    if entry == ENTRY_BLUR:
+        if d["blur_kind"][i] == 0:
+            prog.set_gaussian_blur(i, s, d["sigma"][i])
+        elif d["blur_kind"][i] == 1:
+            prog.set_average_blur(i, s, d["avg_k"][i])
+        else:
+            prog.set_median_blur(i, s, d["med_k"][i])
+    elif entry == ENTRY_SHARPEN:
+        prog.set_conv3x3(i, s, sharpen_weights(d["sh_a"][i], d["sh_l"][i]))
+    elif entry == ENTRY_EMBOSS:
+        prog.set_conv3x3(i, s, emboss_weights(d["em_a"][i], d["em_s"][i]))
+    elif entry == ENTRY_NOISE:
+        prog.set_gaussian_noise(i, s, d["no_s"][i], d["no_pc"][i], seed)
+    elif entry == ENTRY_DROPOUT:
+        if d["dr_kind"][i] == 0:
+            prog.set_dropout(i, s, d["dr_p"][i], d["dr_pc"][i], seed)
+        else:
+            prog.set_coarse_dropout(i, s, d["co_p"][i], d["co_s"][i], d["co_pc"][i], seed)
+    elif entry == ENTRY_INVERT:
+        prog.set_invert(i, s, d["inv"][i])
+    elif entry == ENTRY_ADD:
+        prog.set_add(i, s, d["add_v"][i] if d["add_pc"][i] else d["add_v"][i, 0])
+    elif entry == ENTRY_MULTIPLY:
+        prog.set_multiply(i, s, d["mul_v"][i] if d["mul_pc"][i] else d["mul_v"][i, 0])
+    else:
+        prog.set_grayscale(i, s, d["gray"][i])
+
 
 def sample_program(batch: int, preset: str, rng: np.random.Generator) -> PhotoProgram:
     """Draw the program of one batch.  ``preset``: ``"mscmrseg_aug2_photometric"``, the ``SomeOf((0, 5), ..,
@@ -297,76 +313,29 @@ def sample_program(batch: int, preset: str, rng: np.random.Generator) -> PhotoPr
     twelve); so is the ``CropAndPad`` in front of it.  imgaug's own parameter stream is not reproduced
     (parity unpinned)."""
     if preset == "heavy":
-        from .augment import HEAVY_MESSAGE
         raise NotImplementedError(HEAVY_MESSAGE)
     if preset != PHOTOMETRIC_PRESET:
         raise ValueError("unknown photometric preset %r (have: %s)" % (preset, PHOTOMETRIC_PRESET))
     b = batch
-    u = lambda lo_hi, *shape: rng.uniform(lo_hi[0], lo_hi[1], (b,) + shape)
     order = rng.permutation(9)
     count = rng.integers(0, 6, b)
     rank = np.argsort(np.argsort(rng.random((b, 9)), axis=1), axis=1)
     chosen = rank < count[:, None]                                    # [B,9]: `count` distinct entries per sample
-    blur_kind, sigma = rng.integers(0, 3, b), u(SIGMA)
-    avg_k = rng.integers(AVERAGE_K[0], AVERAGE_K[1] + 1, b)
-    med_k = 2 * rng.integers(MEDIAN_K[0] // 2, MEDIAN_K[1] // 2 + 1, b) + 1
-    sh_a, sh_l, em_a, em_s = u(SHARPEN_ALPHA), u(SHARPEN_LIGHTNESS), u(EMBOSS_ALPHA), u(EMBOSS_STRENGTH)
-    no_s, no_pc = u(NOISE_SCALE), rng.random(b) < NOISE_PER_CHANNEL
-    dr_kind, dr_p, dr_pc = rng.integers(0, 2, b), u(DROPOUT_P), rng.random(b) < DROPOUT_PER_CHANNEL
-    co_p, co_s, co_pc = u(COARSE_P), u(COARSE_SIZE), rng.random(b) < COARSE_PER_CHANNEL
-    inv = rng.random((b, IARGS)) < INVERT_P
-    add_pc, add_v = rng.random(b) < ADD_PER_CHANNEL, rng.integers(ADD[0], ADD[1] + 1, (b, IARGS))
-    mul_pc, mul_v = rng.random(b) < MULTIPLY_PER_CHANNEL, u(MULTIPLY, IARGS)
-    gray = u(GRAY_ALPHA)
-    seeds = rng.integers(0, 2 ** 64, (b, PRESET_SLOTS), dtype=np.uint64)
+    d = draw_photo(b, rng, (b, PRESET_SLOTS))
     prog = PhotoProgram.identity(b, PRESET_SLOTS)
-    for i in range(b):
+    order, seeds = order.tolist(), d["seed"]                          # (plain ints: the entry is compared up to eight times)
+    for i, row in enumerate(chosen[:, order].tolist()):
         s = 0
-        for entry in order:
-            if not chosen[i, entry]:
-                continue
-            sd = seeds[i, s]
-            if entry == ENTRY_BLUR:
-                if blur_kind[i] == 0:
-                    prog.set_gaussian_blur(i, s, sigma[i])
-                elif blur_kind[i] == 1:
-                    prog.set_average_blur(i, s, avg_k[i])
-                else:
-                    prog.set_median_blur(i, s, med_k[i])
-            elif entry == ENTRY_SHARPEN:
-                prog.set_conv3x3(i, s, sharpen_weights(sh_a[i], sh_l[i]))
-            elif entry == ENTRY_EMBOSS:
-                prog.set_conv3x3(i, s, emboss_weights(em_a[i], em_s[i]))
-            elif entry == ENTRY_NOISE:
-                prog.set_gaussian_noise(i, s, no_s[i], no_pc[i], sd)
-            elif entry == ENTRY_DROPOUT:
-                if dr_kind[i] == 0:
-                    prog.set_dropout(i, s, dr_p[i], dr_pc[i], sd)
-                else:
-                    prog.set_coarse_dropout(i, s, co_p[i], co_s[i], co_pc[i], sd)
-            elif entry == ENTRY_INVERT:
-                prog.set_invert(i, s, inv[i])
-            elif entry == ENTRY_ADD:
-                prog.set_add(i, s, add_v[i] if add_pc[i] else add_v[i, 0])
-            elif entry == ENTRY_MULTIPLY:
-                prog.set_multiply(i, s, mul_v[i] if mul_pc[i] else mul_v[i, 0])
-            else:
-                prog.set_grayscale(i, s, gray[i])
-            s += 1
+        for entry, on in zip(order, row):
+            if on:
+                encode_photo(prog, i, s, entry, d, seeds[i, s])
+                s += 1
     return prog
 
 
 def upload_program(program: PhotoProgram, batch: int, h: int, w: int, channels: int, device: torch.device):
     """Validate on the host, then move the kernel's arrays through pinned, non-blocking copies (no synchronisation)."""
-    if program.batch != batch:
-        raise ValueError("PhotoProgram for %d samples, batch of %d" % (program.batch, batch))
-
-    def put(a):
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        if device.type == "cuda":
-            t = t.pin_memory()
-        return t.to(device, non_blocking=True)
-    return tuple(put(a) for a in program.kernel_arrays(h, w, channels))
+    return upload(program, batch, h, w, channels, device=device)
 
 
 def photometric_aug(images: torch.Tensor, program: Optional[PhotoProgram] = None) -> torch.Tensor:

@@ -68,6 +68,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from ._program import SlotProgram, upload
 
 OP_NOP, OP_HUE_SATURATION, OP_NOISE_ALPHA_CONV3X3, OP_SUPERPIXELS = range(4)
 OP_NAMES = ("NOP", "HUE_SATURATION", "NOISE_ALPHA_CONV3X3", "SUPERPIXELS")
@@ -78,8 +79,6 @@ UPSCALE_NEAREST, UPSCALE_BILINEAR = 0, 1
 AGG_MIN, AGG_MEAN, AGG_MAX = 0, 1, 2
 MAX_SEGMENTS, MAX_UPDATES = 256, 10
 MAX_CONNECT_PIXELS = 1 << 24      # connected slots: the segment sums are 32-bit
-HEAVY_FULL_PRESET, AUG2_FULL_PRESET = "heavy_full_device", "mscmrseg_aug2_full_device"
-HEAVY_CONNECTED_PRESET, AUG2_CONNECTED_PRESET = "heavy_connected_device", "mscmrseg_aug2_connected_device"
 
 # data_generator_mscmrseg.py:46, 57-60, 69
 (ENTRY_SUPERPIXELS, ENTRY_NOISE_ALPHA, ENTRY_HUE) = range(3)
@@ -226,7 +225,7 @@ def superpixel_min_size(gy: int, gx: int, h: int, w: int) -> int:
 
 
 @dataclass
-class StyleProgram:
+class StyleProgram(SlotProgram):
     """``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed``
     uint64 ``[B,S]`` (numpy, on the host; the module docstring says what each opcode reads).  The ``set_*`` methods encode slot
     ``s`` of sample ``i``."""
@@ -235,33 +234,7 @@ class StyleProgram:
     farg: np.ndarray
     table: np.ndarray
     seed: np.ndarray
-
-    @property
-    def batch(self) -> int:
-        return self.opcode.shape[0]
-
-    @property
-    def slots(self) -> int:
-        return self.opcode.shape[1]
-
-    @staticmethod
-    def identity(batch: int, slots: int = 1) -> "StyleProgram":
-        return StyleProgram(np.zeros((batch, slots), dtype=np.int32), np.zeros((batch, slots, IARGS), dtype=np.int32),
-                            np.zeros((batch, slots, FARGS), dtype=np.float64), np.zeros((batch, slots, TABLE), dtype=np.float64),
-                            np.zeros((batch, slots), dtype=np.uint64))
-
-    def is_identity(self) -> bool:
-        return not np.any(self.opcode != OP_NOP)
-
-    def _clear(self, i, s, op):
-        self.opcode[i, s] = op
-        self.iarg[i, s] = 0
-        self.farg[i, s] = 0.0
-        self.table[i, s] = 0.0
-        self.seed[i, s] = 0
-
-    def set_nop(self, i, s):
-        self._clear(i, s, OP_NOP)
+    COLUMNS = (("iarg", np.int32, IARGS), ("farg", np.float64, FARGS), ("table", np.float64, TABLE))
 
     def set_hue_saturation(self, i, s, dh, ds):
         self._clear(i, s, OP_HUE_SATURATION)
@@ -300,24 +273,10 @@ class StyleProgram:
         flag that is not 0 / 1, table values outside [0, 1], a threshold beyond +/-1000; gy or gx below 1 or above H / W,
         ``gy gx > 256``, updates outside 0..10, M2 outside 0..2^20, p_replace outside [0, 1], min_size outside 0..H W, or
         min_size > 0 on more than 2^24 pixels."""
-        op, ia, fa, tb, sd = self.opcode, self.iarg, self.farg, self.table, self.seed
-        if getattr(op, "ndim", 0) != 2 or op.dtype != np.int32:
-            raise ValueError("StyleProgram.opcode must be int32 [B,S]")
-        b, s = op.shape
-        if s > MAX_SLOTS:
-            raise ValueError("StyleProgram: %d slots, at most %d" % (s, MAX_SLOTS))
-        for name, a, shape, dt in (("iarg", ia, (b, s, IARGS), np.int32), ("farg", fa, (b, s, FARGS), np.float64),
-                                   ("table", tb, (b, s, TABLE), np.float64), ("seed", sd, (b, s), np.uint64)):
-            if getattr(a, "shape", None) != shape or a.dtype != dt:
-                raise ValueError("StyleProgram.%s must be %s %r" % (name, np.dtype(dt).name, list(shape)))
-        if np.any((op < 0) | (op > OP_SUPERPIXELS)):
-            raise ValueError("StyleProgram.opcode: unknown opcode")
+        self._check_arrays(OP_SUPERPIXELS)
+        op, ia, fa, tb = self.opcode, self.iarg, self.farg, self.table
         if channels is not None and not 1 <= channels <= 4:
             raise ValueError("StyleProgram: 1..4 channels, got %d" % channels)
-        if not np.all(np.isfinite(fa)):
-            raise ValueError("StyleProgram.farg must be finite")
-        if not np.all(np.isfinite(tb)):
-            raise ValueError("StyleProgram.table must be finite")
         i = ia[op == OP_HUE_SATURATION]
         if len(i):
             if channels is not None and channels != 3:
@@ -374,6 +333,9 @@ class StyleProgram:
             ia[i, s, 4] = np.array(threshold(self.farg[i, s, 0]), dtype=np.uint32).view(np.int32)      # (the bits)
         return self.opcode, ia, self.farg, self.table, self.seed.view(np.int64)
 
+    def apply(self, images, masks):
+        return stylize_aug(images, self), masks
+
 
 # ------------------------------------------------------------------------------------------------ sampling
 def draw_style(b: int, rng: np.random.Generator):
@@ -407,43 +369,9 @@ def encode_style(prog: StyleProgram, i: int, s: int, entry: int, d, h: int, w: i
         prog.set_hue_saturation(i, s, int(math.floor(v * 180.0 / 255.0 + 0.5)), v)
 
 
-def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> StyleProgram:
-    """Draw the three STYLE entries of one batch of a preset (``"heavy_full_device"`` or ``"mscmrseg_aug2_full_device"``) for
-    ``h x w`` images as one program of three slots, in the batch's order (the other entries of the recipe are skipped:
-    ``sample_heavy_plan`` interleaves all kinds): ``sometimes(0.5)`` Superpixels (p_replace U(0, 1), n_segments 20..200 ->
-    ``superpixel_grid``, 5 updates, compactness 10), SimplexNoiseAlpha (alpha U(0.5, 1), OneOf EdgeDetect | DirectedEdgeDetect
-    with direction U(0, 1); 1..3 grids of 2..16 cells per side, nearest | bilinear, min | mean | max, sigmoid with a threshold
-    from N(0, 5)) and AddToHueAndSaturation (v integer in -20..20: ds = v, dh = floor(v 180 / 255 + 0.5)), each only for the
-    samples whose ``SomeOf((0, 5))`` drew it.  The ``_connected_`` presets draw what their ``_refpad_`` twins draw and give every
-    Superpixels slot ``min_size = superpixel_min_size(gy, gx, h, w)``."""
-    from . import geometric as Geo
-    spec = Geo._check_preset(preset)
-    entries, on = Geo._select(batch, spec, rng)
-    d = draw_style(batch, rng)
-    sty = [k for k, e in enumerate(entries) if e[0] == "s"]
-    if not sty:
-        raise ValueError("preset %r holds no stylize entry (have: %s, %s)" % (preset, HEAVY_FULL_PRESET, AUG2_FULL_PRESET))
-    prog = StyleProgram.identity(batch, len(sty))
-    for i in range(batch):
-        s = 0
-        for k in sty:
-            if on[i, k]:
-                encode_style(prog, i, s, entries[k][1], d, h, w, connected=bool(spec.get("connected")))
-                s += 1
-    return prog
-
-
 def upload_style_program(program: StyleProgram, batch: int, h: int, w: int, channels: int, device: torch.device):
     """Validate on the host, then move the kernel's arrays through pinned, non-blocking copies (no synchronisation)."""
-    if program.batch != batch:
-        raise ValueError("StyleProgram for %d samples, batch of %d" % (program.batch, batch))
-
-    def put(a):
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        if device.type == "cuda":
-            t = t.pin_memory()
-        return t.to(device, non_blocking=True)
-    return tuple(put(a) for a in program.kernel_arrays(h, w, channels))
+    return upload(program, batch, h, w, channels, device=device)
 
 
 def stylize_aug(images: torch.Tensor, program: Optional[StyleProgram] = None) -> torch.Tensor:

@@ -34,7 +34,7 @@ from pointcloududa_amd import _lib  # noqa: E402
 from pointcloududa_amd import kernels as KK  # noqa: E402
 from pointcloududa_amd.utils import geometric as P  # noqa: E402
 from pointcloududa_amd.utils import photometric as F7  # noqa: E402
-from pointcloududa_amd.utils.augment import augment_batch, heavy_aug  # noqa: E402
+from pointcloududa_amd.utils.augment import augment_batch, heavy_aug, sample_heavy_plan  # noqa: E402
 
 B, H, W, C, K = 32, 256, 256, 3, 5
 PRESET = "heavy_device"
@@ -99,7 +99,7 @@ def main():
         a_ms[name] = timed(prog)
         a_nolab[name] = timed(prog, labels=False)
 
-    plan = P.sample_heavy_plan(B, PRESET, np.random.default_rng(2027), H, W)
+    plan = sample_heavy_plan(B, PRESET, np.random.default_rng(2027), H, W)
     geo = [st for st in plan.stages if isinstance(st, P.GeoProgram)]
     ups = [(isinstance(st, P.GeoProgram), P.upload_geo_program(st, B, H, W, dev) if isinstance(st, P.GeoProgram)
             else F7.upload_program(st, B, H, W, C, dev)) for st in plan.stages]
@@ -122,7 +122,7 @@ def main():
         "extra_pass_nop_with_labels": a_ms["nop"],
     }
     rng = np.random.default_rng(5)
-    d_ms = {"sample_heavy_plan": host_ms(lambda: P.sample_heavy_plan(B, PRESET, rng, H, W), 50)}
+    d_ms = {"sample_heavy_plan": host_ms(lambda: sample_heavy_plan(B, PRESET, rng, H, W), 50)}
     torch.cuda.synchronize()
 
     def restate(backend):

@@ -342,7 +342,7 @@ def plan_digest(plan):
 def digests():
     """the four presets that existed before f14, seeds 0..19: to be recorded on a commit whose draws are to be pinned"""
     sys.path.insert(0, ROOT)
-    from pointcloududa_amd.utils.geometric import sample_heavy_plan
+    from pointcloududa_amd.utils.heavy import sample_heavy_plan
     return {p: [plan_digest(sample_heavy_plan(DIGEST_BATCH, p, np.random.default_rng(s), DIGEST_H, DIGEST_W))
                 for s in range(DIGEST_SEEDS)] for p in DIGEST_PRESETS}
 

@@ -247,6 +247,7 @@ def test_refpad_presets_draw_all_ten_modes_within_the_documented_ranges(preset):
 def test_refpad_presets_consume_the_generator_as_documented(preset):
     """everything the _full_ twin draws, in the same order, then one integers(0, 10, batch); sides and cval are _draw_geo's"""
     from pointcloududa_amd.utils import geometric as Geo
+    from pointcloududa_amd.utils import heavy as Hv
     from pointcloududa_amd.utils import stylize as St
     from pointcloududa_amd.utils.augment import sample_heavy_plan
     full = {"heavy_refpad_device": "heavy_full_device", "mscmrseg_aug2_refpad_device": "mscmrseg_aug2_full_device"}[preset]
@@ -254,16 +255,16 @@ def test_refpad_presets_consume_the_generator_as_documented(preset):
     for seed in range(10):
         rng, twin, rng_full = (np.random.default_rng(seed) for _ in range(3))
         plan = sample_heavy_plan(b, preset, rng, h, w)
-        spec = Geo._PRESETS[preset]
-        assert [e if e == "block" else e[1] for e in spec["outer"]] == [e if e == "block" else e[1] for e in Geo._PRESETS[full]["outer"]]
-        assert spec["block"] == Geo._PRESETS[full]["block"]
+        spec = Hv._PRESETS[preset]
+        assert [e if e == "block" else e[1] for e in spec["outer"]] == [e if e == "block" else e[1] for e in Hv._PRESETS[full]["outer"]]
+        assert spec["block"] == Hv._PRESETS[full]["block"]
         twin.permutation(len(spec["outer"])); twin.permutation(len(spec["block"]))
         twin.integers(0, 6, b); twin.random((b, len(spec["block"])))
         for e in spec["block"]:
-            if e in Geo._SOMETIMES:
+            if e in Hv._SOMETIMES:
                 twin.random(b)
         coins = [twin.random(b) for e in spec["outer"] if e != "block"]
-        dg = Geo._draw_geo(b, twin, h, w); Geo._draw_photo(b, twin); St.draw_style(b, twin)
+        dg = Geo._draw_geo(b, twin, h, w); Hv._draw_photo(b, twin); St.draw_style(b, twin)
         mode = twin.integers(0, 10, b)
         nxt = twin.integers(0, 2 ** 62)
         assert rng.integers(0, 2 ** 62) == nxt, (preset, seed)

@@ -239,6 +239,7 @@ def test_encoders_hold_their_identities():
 def test_programs_are_validated_on_the_host():
     import torch
     from pointcloududa_amd.utils import geometric as P
+    from pointcloududa_amd.utils import heavy as Hv
     h, w = 40, 30
 
     def one(setter, *args, **kw):
@@ -287,11 +288,11 @@ def test_programs_are_validated_on_the_host():
     with pytest.raises(TypeError, match="uint8"):
         P.geometric_aug(torch.zeros(1, 4, 4, 3), None, P.GeoProgram.identity(1))
     with pytest.raises(TypeError, match="plan is required"):
-        P.heavy_aug(torch.zeros(1, 4, 4, 3, dtype=torch.uint8), None)
+        Hv.heavy_aug(torch.zeros(1, 4, 4, 3, dtype=torch.uint8), None)
     with pytest.raises(ValueError, match="batch"):
         P.upload_geo_program(P.GeoProgram.identity(2), 3, 8, 8, torch.device("cpu"))
     with pytest.raises(ValueError, match="batch"):
-        P.heavy_aug(torch.zeros(1, 4, 4, 3, dtype=torch.uint8), None, P.HeavyPlan(2))
+        Hv.heavy_aug(torch.zeros(1, 4, 4, 3, dtype=torch.uint8), None, Hv.HeavyPlan(2))
 
 
 # ---------------------------------------------------------------------------------------------- the samplers
@@ -309,12 +310,13 @@ def _homography_kind(f, h, w):
 
 def test_sample_geo_program_stays_in_range_over_1000_draws():
     from pointcloududa_amd.utils import geometric as P
+    from pointcloududa_amd.utils import heavy as Hv
     h, w = 256, 224
     rng = np.random.default_rng(5)
     seen, orders = {}, set()
     crop_modes, aff_modes, aff_orders = set(), set(), set()
     for _ in range(1000):
-        prog = P.sample_geo_program(4, "heavy_device", rng, h, w)
+        prog = Hv.sample_geo_program(4, "heavy_device", rng, h, w)
         prog.validate(h, w)
         assert prog.opcode.shape == (4, 7) and prog.farg.shape == (4, 7, 32) and prog.seed.dtype == np.uint64
         for i in range(4):
@@ -377,7 +379,7 @@ def test_sample_geo_program_stays_in_range_over_1000_draws():
     # the aug2 preset: one slot, sometimes(CropAndPad)
     cnt = 0
     for _ in range(200):
-        prog = P.sample_geo_program(8, "mscmrseg_aug2_device", rng, h, w)
+        prog = Hv.sample_geo_program(8, "mscmrseg_aug2_device", rng, h, w)
         prog.validate(h, w)
         assert prog.opcode.shape == (8, 1) and set(np.unique(prog.opcode)) <= {0, 1}
         cnt += int(prog.opcode.sum())
@@ -388,13 +390,14 @@ def test_sample_geo_program_stays_in_range_over_1000_draws():
 
 def test_sample_heavy_plan_stays_in_range_over_1000_draws():
     from pointcloududa_amd.utils import geometric as P
+    from pointcloududa_amd.utils import heavy as Hv
     from pointcloududa_amd.utils import photometric as F7
     h, w = 128, 160
     rng = np.random.default_rng(6)
     geo_ops, photo_ops, nstages, block_counts = set(), set(), set(), []
     for it in range(1000):
         preset = ("heavy_device", "mscmrseg_aug2_device")[it % 4 == 3]
-        plan = P.sample_heavy_plan(4, preset, rng, h, w)
+        plan = Hv.sample_heavy_plan(4, preset, rng, h, w)
         assert plan.batch == 4
         nstages.add(len(plan.stages))
         photo_slots = np.zeros(4, dtype=int)
@@ -423,19 +426,19 @@ def test_sample_heavy_plan_stays_in_range_over_1000_draws():
             assert len(plan.stages) <= 2
     assert geo_ops == {0, 1, 2, 3} and photo_ops == set(range(12))
     assert max(nstages) >= 5 and min(nstages) <= 1 and max(block_counts) == 5
-    a = P.sample_heavy_plan(9, "heavy_device", np.random.default_rng(11), h, w)
-    b = P.sample_heavy_plan(9, "heavy_device", np.random.default_rng(11), h, w)
+    a = Hv.sample_heavy_plan(9, "heavy_device", np.random.default_rng(11), h, w)
+    b = Hv.sample_heavy_plan(9, "heavy_device", np.random.default_rng(11), h, w)
     assert len(a.stages) == len(b.stages)
     for x, y in zip(a.stages, b.stages):
         for k in ("opcode", "iarg", "farg", "seed"):
             assert np.array_equal(getattr(x, k), getattr(y, k)), k
-    assert P.HeavyPlan(3).is_identity() and not a.is_identity()
+    assert Hv.HeavyPlan(3).is_identity() and not a.is_identity()
 
 
 def test_heavy_still_raises_and_presets_are_checked():
     from pointcloududa_amd.utils import augment as A
     rng = np.random.default_rng(0)
-    assert A.sample_geo_program.__module__.endswith("utils.geometric") and A.HEAVY_DEVICE_PRESET == "heavy_device"
+    assert A.sample_geo_program.__module__.endswith("utils.heavy") and A.HEAVY_DEVICE_PRESET == "heavy_device"
     for fn in (lambda: A.sample_geo_program(4, "heavy", rng, 64, 64), lambda: A.sample_heavy_plan(4, "heavy", rng, 64, 64),
                lambda: A.sample_params(4, "heavy", rng), lambda: A.sample_program(4, "heavy", rng)):
         with pytest.raises(NotImplementedError, match="heavy pipeline .* is out of scope"):

@@ -166,8 +166,8 @@ def test_a_connected_plan_is_the_refpad_plan_plus_min_size(preset, twin):
                 assert ia[5] == S.superpixel_min_size(ia[0], ia[1], 64, 48) >= 1
             assert sa.needs_connect() == bool(spx.any()) and not sb.needs_connect()
             seen += int(spx.sum())
-        pa = S.sample_style_program(6, preset, np.random.default_rng(seed), 64, 48)
-        pb = S.sample_style_program(6, twin, np.random.default_rng(seed), 64, 48)
+        pa = A.sample_style_program(6, preset, np.random.default_rng(seed), 64, 48)
+        pb = A.sample_style_program(6, twin, np.random.default_rng(seed), 64, 48)
         assert np.array_equal(pa.opcode, pb.opcode) and np.array_equal(pa.iarg[..., :5], pb.iarg[..., :5])
         assert pa.needs_connect() == bool((pa.opcode == S.OP_SUPERPIXELS).any())
     assert seen > 0

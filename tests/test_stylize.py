@@ -367,6 +367,7 @@ def test_old_presets_draw_what_they_drew_and_hold_no_style_program():
     """"heavy_device", "mscmrseg_aug2_device" and "mscmrseg_aug2_photometric" consume the generator exactly as before (their
     draws are followed by the same next value as a replay of the documented sequence) and never hold a StyleProgram"""
     from pointcloududa_amd.utils import geometric as Geo
+    from pointcloududa_amd.utils import heavy as Hv
     from pointcloududa_amd.utils.augment import StyleProgram, sample_heavy_plan
     for preset in ("heavy_device", "mscmrseg_aug2_device"):
         for seed in range(20):
@@ -374,7 +375,7 @@ def test_old_presets_draw_what_they_drew_and_hold_no_style_program():
             plan = sample_heavy_plan(16, preset, rng, 64, 48)
             assert not any(isinstance(st, StyleProgram) for st in plan.stages)
             twin = np.random.default_rng(seed)
-            spec = Geo._PRESETS[preset]
+            spec = Hv._PRESETS[preset]
             assert all(e == "block" or e[0] in "pg" for e in spec["outer"] + spec["block"])
             # the documented sequence: two orders, the count, the ranks, one sometimes per warp of the block, the outer
             # coins, then the geometric and the photometric parameters -- and nothing after them
@@ -386,7 +387,7 @@ def test_old_presets_draw_what_they_drew_and_hold_no_style_program():
             for e in spec["outer"]:
                 if e != "block":
                     twin.random(16)
-            Geo._draw_geo(16, twin, 64, 48); Geo._draw_photo(16, twin)
+            Geo._draw_geo(16, twin, 64, 48); Hv._draw_photo(16, twin)
             assert rng.integers(0, 2 ** 62) == twin.integers(0, 2 ** 62), (preset, seed)
 
 
