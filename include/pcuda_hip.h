@@ -471,6 +471,17 @@ size_t pcuda_geometric_workspace_size(int b, int h, int w, int c, int with_label
 int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w, int c,
                     int slots, const int* opcode, const int* iarg, const double* farg, const unsigned long long* seed,
                     void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* pcuda_geometric with a third sampling order (f8b): the same arguments, rules and workspace, but iarg[0] == 3 is the Keys
+ * cubic convolution with A = -0.75 over the 4 x 4 neighbours floor(s) - 1 .. floor(s) + 2 (0 stays nearest, anything else
+ * bilinear).  For t = s - floor(s), u = t + 1, r = 1 - t, in float64, every operation rounded on its own:
+ *   wm = ((A u - 5 A) u + 8 A) u - 4 A;  w0 = ((A + 2) t - (A + 3)) t t + 1;  w1 = ((A + 2) r - (A + 3)) r r + 1;
+ *   w2 = ((1 - wm) - w0) - w1
+ * The border mode folds each of the eight neighbour indices (constant: cval per tap); a row is
+ * ((p[-1] wxm + p[0] wx0) + p[1] wx1) + p[2] wx2, the four rows are summed likewise with the y weights, floor(v + 0.5)
+ * clipped to [0, 255].  A kernel instance of its own: pcuda_geometric keeps its registers and samples order 3 bilinearly. */
+int pcuda_geometric_cubic(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w, int c,
+                          int slots, const int* opcode, const int* iarg, const double* farg, const unsigned long long* seed,
+                          void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* device-side stylize augmentation: the three entries of the reference's SomeOf lists that pcuda_photometric and
  * pcuda_geometric do not hold (data_generator_mscmrseg.py:46, 57-60, 69) on uint8 images [b][h][w][c], c = 1..4, as a per-sample
  * program of `slots` (0..8) slots in device memory: opcode [b][slots], iarg [b][slots][12], farg [b][slots][16] (float64),
@@ -486,7 +497,9 @@ int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* labels_in, int* 
  *                                    (p,V,t), (p,q,V), (t,p,V), (V,p,q)
  *   PCUDA_STYLE_NOISE_ALPHA_CONV3X3  iarg[0] = n 1..3 grids, iarg[1] = upscale (0 nearest: cell ((y h') / h, (x w') / w);
  *                                    1 bilinear: sy = (y + 0.5) h' / h - 0.5 clamped to [0, h' - 1], rows g00 (1 - fx) + g01 fx,
- *                                    then top (1 - fy) + bot fy), iarg[2] = aggregation (0 min, 1 mean in grid order, 2 max),
+ *                                    then top (1 - fy) + bot fy; 3 cubic: the same sy, sx unclamped, the weights and the
+ *                                    summation order of pcuda_geometric_cubic, every tap index clamped into the grid, the
+ *                                    value clipped to [0, 1]; 2 is no upscale), iarg[2] = aggregation (0 min, 1 mean in grid order, 2 max),
  *                                    iarg[3] = sigmoid on: m = 1 / (1 + exp(-(20 (m - 0.5) - farg[9]))), iarg[4 + 2 k],
  *                                    iarg[5 + 2 k] = h', w' of grid k (2..16); farg[0..8] = 3x3 correlation as
  *                                    PCUDA_PHOTO_CONV3X3, e = its rounded result; out = floor((1 - m) x + m e + 0.5) clipped;

@@ -129,6 +129,7 @@ _PROTOS = {
     "pcuda_photometric": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_geometric_workspace_size": (sz, [i32, i32, i32, i32, i32]),
     "pcuda_geometric": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "pcuda_geometric_cubic": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_stylize_workspace_size": (sz, [i32, i32, i32, i32]),
     "pcuda_stylize": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_stylize_connect_workspace_size": (sz, [i32, i32, i32, i32]),

@@ -10,6 +10,9 @@
 //     with -ffp-contract=off), then one sample; the value is uint8 again between two slots
 //   * order 0 takes the texel at floor(s + 0.5); order 1 is bilinear over (floor(s), floor(s) + 1) in f6's order
 //     (v = 0; v += ((p * wy) * wx) for the neighbours row-major), floor(v + 0.5) clipped to [0, 255]
+//   * order 3 (pcuda_geometric_cubic only; pcuda_geometric samples it as order 1): Keys cubic convolution, A = -0.75, over
+//     floor(s) - 1 .. floor(s) + 2 per axis with imgdev::cubic_weights of s - floor(s); a row is summed left to right
+//     (((p0 wx0 + p1 wx1) + p2 wx2) + p3 wx3), then the rows top to bottom likewise, floor(v + 0.5) clipped to [0, 255]
 //   * border mode per neighbour INDEX, folded in integers: 0 constant (cval), 1 edge, 2 reflect without repeating the edge
 //     (period 2 (n - 1)), 3 symmetric (period 2 n), 4 wrap (period n); anything else behaves as 0
 //   * labels take order 0 and constant 0 at the same coordinate whatever the image's order, mode and cval are
@@ -136,6 +139,46 @@ __device__ __forceinline__ void sample_store(const GeoArgs& a, int n, int xg, in
       labv[j] = lin ? l : 0;
       PCUDA_KEEP(pl);
     }
+    if constexpr (ORD == 3) {
+      // Keys cubic over the 4 x 4 neighbours (floor(s) - 1 .. floor(s) + 2 per axis): the border mode folds each of the
+      // eight indices, a row is summed left to right, then the four rows top to bottom
+      const double xf = floor(cx), yf = floor(cy);
+      double wx[4], wy[4];
+      imgdev::cubic_weights(cx - xf, wx);
+      imgdev::cubic_weights(cy - yf, wy);
+      const int xa = (int)xf - 1, ya = (int)yf - 1;
+      int fx[4], fy[4];
+      bool ix[4], iy[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        fx[q] = fold(xa + q, w, mode, ix[q]) * c;
+        fy[q] = fold(ya + q, h, mode, iy[q]) * w * c;
+        ix[q] = ix[q] && !bad;
+      }
+#pragma unroll
+      for (int ch = 0; ch < kMaxC; ++ch) {
+        if (ch >= c) break;
+        double rows[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint8_t* pc[4];
+          double p[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            pc[q] = src + (fy[k] + fx[q] + ch);
+            const uint8_t t = *pc[q];
+            p[q] = (ix[q] && iy[k]) ? (double)t : (double)cv;
+          }
+          rows[k] = ((p[0] * wx[0] + p[1] * wx[1]) + p[2] * wx[2]) + p[3] * wx[3];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) PCUDA_KEEP(pc[q]);      // (VMEM address rule, common.h)
+        }
+        const double v = ((rows[0] * wy[0] + rows[1] * wy[1]) + rows[2] * wy[2]) + rows[3] * wy[3];
+        const int e = j * c + ch;
+        words[e >> 2] |= round_u8_word(v) << (8 * (e & 3));
+      }
+      continue;
+    }
     const uint8_t* pt[NB];
     bool tin[NB];
     double wx1 = 0.0, wy1 = 0.0;
@@ -210,6 +253,9 @@ __device__ __forceinline__ void sample_store(const GeoArgs& a, int n, int xg, in
   }
 }
 
+// CUBIC: order 3 samples cubically (the instance behind pcuda_geometric_cubic); without it order 3 samples as order 1 and
+// the kernel is the one pcuda_geometric has always launched, register for register
+template <bool CUBIC>
 __global__ __launch_bounds__(256) void geometric_kernel(const GeoArgs a) {
   __shared__ double s_f[kFArgs];
   __shared__ uint32_t s_seed[2];
@@ -319,7 +365,8 @@ __global__ __launch_bounds__(256) void geometric_kernel(const GeoArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) { sx[j] = (double)(xg + j); sy[j] = Y; }
   }
-  if (order != 0) sample_store<1>(a, n, xg, y, sx, sy, mode, cv);
+  if (CUBIC && order == 3) sample_store<3>(a, n, xg, y, sx, sy, mode, cv);
+  else if (order != 0) sample_store<1>(a, n, xg, y, sx, sy, mode, cv);
   else sample_store<0>(a, n, xg, y, sx, sy, mode, cv);
 }
 
@@ -332,9 +379,9 @@ extern "C" size_t pcuda_geometric_workspace_size(int b, int h, int w, int c, int
   return round16(px * c) + (with_labels ? round16(px * sizeof(int)) : 0);
 }
 
-extern "C" int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w,
-                               int c, int slots, const int* opcode, const int* iarg, const double* farg,
-                               const unsigned long long* seed, void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
+static int geometric_run(bool cubic, const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w,
+                         int c, int slots, const int* opcode, const int* iarg, const double* farg,
+                         const unsigned long long* seed, void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
   if (!in || !out) PCUDA_FAIL(PCUDA_E_BADARG, "geometric: null pointer");
   if (in == out || (labels_in && labels_in == labels_out))
     PCUDA_FAIL(PCUDA_E_BADARG, "geometric: in == out (the input is never written)");
@@ -367,9 +414,30 @@ extern "C" int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* label
     a.in = cur; a.out = dst; a.lab_in = cur_lab; a.lab_out = dst_lab; a.slot = slots > 0 ? i : -1;
     a.vec_out = ((uintptr_t)dst & 3) == 0 && (((long long)w * c) & 3) == 0;
     a.vec_lab = ((uintptr_t)dst_lab & 15) == 0 && (w & 3) == 0;
-    hipLaunchKernelGGL(geometric_kernel, grid, dim3(256), 0, (hipStream_t)s, a);
-    PCUDA_CHECK_LAUNCH("geometric_kernel");
+    if (cubic) {
+      hipLaunchKernelGGL(geometric_kernel<true>, grid, dim3(256), 0, (hipStream_t)s, a);
+      PCUDA_CHECK_LAUNCH("geometric_kernel<cubic>");
+    } else {
+      hipLaunchKernelGGL(geometric_kernel<false>, grid, dim3(256), 0, (hipStream_t)s, a);
+      PCUDA_CHECK_LAUNCH("geometric_kernel");
+    }
     cur = dst; cur_lab = dst_lab;
   }
   return PCUDA_OK;
+}
+
+extern "C" int pcuda_geometric(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w,
+                               int c, int slots, const int* opcode, const int* iarg, const double* farg,
+                               const unsigned long long* seed, void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
+  return geometric_run(false, in, out, labels_in, labels_out, b, h, w, c, slots, opcode, iarg, farg, seed, workspace,
+                       workspace_bytes, s);
+}
+
+// the same arguments and workspace; order 3 is cubic here (order 0 nearest, anything else bilinear)
+extern "C" int pcuda_geometric_cubic(const uint8_t* in, uint8_t* out, const int* labels_in, int* labels_out, int b, int h, int w,
+                                     int c, int slots, const int* opcode, const int* iarg, const double* farg,
+                                     const unsigned long long* seed, void* workspace, size_t workspace_bytes,
+                                     pcuda_stream_t s) {
+  return geometric_run(true, in, out, labels_in, labels_out, b, h, w, c, slots, opcode, iarg, farg, seed, workspace,
+                       workspace_bytes, s);
 }

@@ -21,6 +21,19 @@ __device__ __forceinline__ uint8_t round_u8(double v) {
   return (uint8_t)(int)r;
 }
 
+// Keys cubic convolution, A = -0.75 (the constant OpenCV documents for INTER_CUBIC), for the fraction t in [0, 1) of a
+// source coordinate: the weights of the taps i0 - 1, i0, i0 + 1, i0 + 2.  Float64, every operation rounded on
+// its own (-ffp-contract=off), in exactly this order; t = 0 gives (0, 1, 0, 0) exactly
+constexpr double kCubicA = -0.75;
+__device__ __forceinline__ void cubic_weights(double t, double (&wt)[4]) {
+  const double u = t + 1.0;
+  wt[0] = ((kCubicA * u - 5.0 * kCubicA) * u + 8.0 * kCubicA) * u - 4.0 * kCubicA;
+  wt[1] = ((kCubicA + 2.0) * t - (kCubicA + 3.0)) * t * t + 1.0;
+  const double r = 1.0 - t;
+  wt[2] = ((kCubicA + 2.0) * r - (kCubicA + 3.0)) * r * r + 1.0;
+  wt[3] = ((1.0 - wt[0]) - wt[1]) - wt[2];
+}
+
 // first word of Philox4x32-10 as photometric.hip implements it: ten rounds, the key bumped between rounds
 __device__ __forceinline__ uint32_t philox_word0(uint32_t k0, uint32_t k1, uint32_t c0) {
   uint32_t c1 = 0, c2 = 0, c3 = 0;

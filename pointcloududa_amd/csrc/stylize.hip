@@ -15,7 +15,10 @@
 //   * NOISE_ALPHA_CONV3X3 (float64 in the written order; the library is built with -ffp-contract=off): n = 1..3 coarse grids
 //     h' x w' (2..16 each) of values in [0, 1] come from the host (table); each is upscaled to H x W -- nearest: cell
 //     ((y h') / H, (x w') / W); bilinear: sy = (y + 0.5) h' / H - 0.5 clamped to [0, h' - 1], y0 = floor(sy), y1 = min(y0 + 1,
-//     h' - 1), fy = sy - y0, top = g00 (1 - fx) + g01 fx, bot likewise, top (1 - fy) + bot fy --, aggregated (min | mean in
+//     h' - 1), fy = sy - y0, top = g00 (1 - fx) + g01 fx, bot likewise, top (1 - fy) + bot fy; cubic (iarg[1] = 3, f8b): the
+//     same sy, sx UNCLAMPED, Keys weights (A = -0.75, imgdev::cubic_weights) of sy - floor(sy) over the taps floor(sy) - 1 ..
+//     floor(sy) + 2, each tap index clamped to [0, h' - 1], rows summed left to right, then the rows, the value clipped to
+//     [0, 1] --, aggregated (min | mean in
 //     iteration order | max), optionally m = 1 / (1 + exp(-(20 (m - 0.5) - t))); e = to_u8(3x3 correlation, f7's CONV3X3:
 //     t = 0, nine taps row-major, reflect-101); out = to_u8((1 - m) x + m e), to_u8 = floor(v + 0.5) clipped
 //   * SUPERPIXELS (integers only): a gy x gx grid SLIC.  Centre k = j gx + i starts at (((2j+1) H) / (2 gy), ((2i+1) W) / (2 gx))
@@ -47,6 +50,7 @@
 namespace {
 
 enum { OP_NOP = 0, OP_HUE_SATURATION = 1, OP_NOISE_ALPHA = 2, OP_SUPERPIXELS = 3 };
+enum { UPSCALE_NEAREST = 0, UPSCALE_BILINEAR = 1, UPSCALE_CUBIC = 3 };      // (2 is not an upscale: the host rejects it)
 
 constexpr int kMaxSlots = 8, kIArgs = 12, kFArgs = 16;
 constexpr int kGrid = 256;                 // values of one coarse grid (16 x 16)
@@ -191,10 +195,28 @@ __global__ __launch_bounds__(256) void stylize_pointwise_kernel(const StyleArgs 
 // ------------------------------------------------------------------------------------------
 // NOISE_ALPHA_CONV3X3: one pixel per lane
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double upscaled(const double* g, int h2, int w2, int y, int x, int h, int w, bool bilinear) {
-  if (!bilinear) return g[(int)(((long long)y * h2) / h) * w2 + (int)(((long long)x * w2) / w)];
+__device__ __forceinline__ double upscaled(const double* g, int h2, int w2, int y, int x, int h, int w, int up) {
+  if (up != UPSCALE_BILINEAR && up != UPSCALE_CUBIC) return g[(int)(((long long)y * h2) / h) * w2 + (int)(((long long)x * w2) / w)];
   double sy = ((double)y + 0.5) * (double)h2 / (double)h - 0.5;
   double sx = ((double)x + 0.5) * (double)w2 / (double)w - 0.5;
+  if (up == UPSCALE_CUBIC) {      // the coordinate stays unclamped, each of the eight tap indices is clamped into the grid
+    const double yf = floor(sy), xf = floor(sx);
+    double wy[4], wx[4];
+    imgdev::cubic_weights(sy - yf, wy);
+    imgdev::cubic_weights(sx - xf, wx);
+    const int ya = (int)yf - 1, xa = (int)xf - 1;
+    int xi[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xi[q] = clampi(xa + q, 0, w2 - 1);
+    double rows[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double* r = g + clampi(ya + k, 0, h2 - 1) * w2;
+      rows[k] = ((r[xi[0]] * wx[0] + r[xi[1]] * wx[1]) + r[xi[2]] * wx[2]) + r[xi[3]] * wx[3];
+    }
+    const double v = ((rows[0] * wy[0] + rows[1] * wy[1]) + rows[2] * wy[2]) + rows[3] * wy[3];
+    return fmin(fmax(v, 0.0), 1.0);      // an alpha: the cubic overshoots
+  }
   sy = fmin(fmax(sy, 0.0), (double)(h2 - 1));
   sx = fmin(fmax(sx, 0.0), (double)(w2 - 1));
   const int y0 = clampi((int)floor(sy), 0, h2 - 1), x0 = clampi((int)floor(sx), 0, w2 - 1);
@@ -215,7 +237,7 @@ __global__ __launch_bounds__(256) void stylize_noise_alpha_kernel(const StyleArg
   const int c = a.c, w = a.w, h = a.h;
   const int* ia = a.iarg + at * kIArgs;
   const int niter = clampi(ia[0], 1, 3);
-  const bool bilinear = ia[1] == 1;
+  const int up = ia[1];
   const int aggregation = ia[2];
   const bool sigmoid = ia[3] != 0;
   int h2[3], w2[3];
@@ -237,9 +259,9 @@ __global__ __launch_bounds__(256) void stylize_noise_alpha_kernel(const StyleArg
   if (pix >= h * w) return;
   const int y = pix / w, x = pix - y * w;
 
-  double m = upscaled(s_tab, h2[0], w2[0], y, x, h, w, bilinear);
+  double m = upscaled(s_tab, h2[0], w2[0], y, x, h, w, up);
   for (int k = 1; k < niter; ++k) {
-    const double v = upscaled(s_tab + k * kGrid, h2[k], w2[k], y, x, h, w, bilinear);
+    const double v = upscaled(s_tab + k * kGrid, h2[k], w2[k], y, x, h, w, up);
     if (aggregation == 0) m = fmin(m, v);
     else if (aggregation == 2) m = fmax(m, v);
     else m = m + v;

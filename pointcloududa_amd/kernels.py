@@ -1019,19 +1019,21 @@ def photometric(images_u8, opcode, iarg, farg, seed, out=None):
     return out
 
 
-def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=None):
+def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=None, cubic=False):
     """A per-sample geometric program over uint8 ``[B,H,W,C]`` images and optional int32 ``[B,H,W]`` labels
     (``pcuda_geometric``): ``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,4]``, ``farg`` float64 ``[B,S,32]``, ``seed`` int64
     ``[B,S]`` (the bits of the 64-bit Philox key), all on the device, ``S`` = 0..8 -> ``(images, labels or None)``, new tensors
-    (the inputs are never written)."""
+    (the inputs are never written).  ``cubic=True`` goes through ``pcuda_geometric_cubic`` (the same arguments and workspace):
+    order 3 samples cubically there; without it order 3 samples as order 1."""
     images_u8, (b, h, w, c) = _images("geometric", images_u8)
     slots, arrays = _program("geometric", b, opcode, seed, iarg=(iarg, torch.int32, 4), farg=(farg, torch.float64, 32))
     labels, labels_out = _labels_io("geometric", labels, labels_out, (b, h, w))
     out = _out("geometric", out, images_u8)
     nbytes = L.lib().pcuda_geometric_workspace_size(b, h, w, c, int(labels is not None)) if slots > 1 else 0
     ws = _workspace(nbytes, images_u8.device)
-    check(L.lib().pcuda_geometric(images_u8.data_ptr(), out.data_ptr(), _ptr(labels), _ptr(labels_out), b, h, w, c, slots,
-                                  *(t.data_ptr() for t in arrays), _ptr(ws), nbytes, _stream()), "geometric")
+    run_fn = L.lib().pcuda_geometric_cubic if cubic else L.lib().pcuda_geometric
+    check(run_fn(images_u8.data_ptr(), out.data_ptr(), _ptr(labels), _ptr(labels_out), b, h, w, c, slots,
+                 *(t.data_ptr() for t in arrays), _ptr(ws), nbytes, _stream()), "geometric_cubic" if cubic else "geometric")
     return out, labels_out
 
 

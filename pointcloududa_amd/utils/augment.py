@@ -60,7 +60,7 @@ from .stylize import (StyleProgram, directed_edge_weights, edge_detect_weights, 
 from .histmatch import HistReference, HistReferenceBank, match_histograms, reference_tables  # noqa: F401
 from .croppad import MODE_NAMES, CropPadProgram, crop_pad_aug, upload_crop_pad_program  # noqa: F401
 from .heavy import (AUG2_CONNECTED_PRESET, AUG2_DEVICE_PRESET, AUG2_FULL_PRESET, AUG2_REFPAD_PRESET, HEAVY_CONNECTED_PRESET,  # noqa: F401
-                    HEAVY_DEVICE_PRESET, HEAVY_FULL_PRESET, HEAVY_REFPAD_PRESET, HeavyPlan, _check_preset, heavy_aug,
+                    HEAVY_DEVICE_PRESET, HEAVY_FULL_PRESET, HEAVY_REFPAD_PRESET, HeavyPlan, _check_interp, _check_preset, heavy_aug,
                     sample_geo_program, sample_heavy_plan, sample_style_program)
 
 
@@ -182,7 +182,9 @@ class AugmentedBatches:
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
     uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"``, their ``_full_``,
     ``_refpad_`` or ``_connected_`` twins) ``preset`` must
-    be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters.  With
+    be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters;
+    ``heavy_interp="cubic"`` (f8b) draws it with ``sample_heavy_plan(.., interp="cubic")`` -- order-3 elastic warps and a share of
+    cubic noise upscales, one more ``rng.random(B)`` per batch --, ``"linear"`` (the default) as before.  With
     ``match_hist_reference`` (an ``[H,W,C]`` numpy image) its tables are built and uploaded once (``match_hist``) and every batch
     is histogram-matched against it first.  With ``match_hist_bank`` (a ``HistReferenceBank``) every sample is matched to a
     reference drawn from the bank: ``rng.integers(R, size=B)`` is the FIRST draw of a batch (``last_match_index``), made only
@@ -191,7 +193,9 @@ class AugmentedBatches:
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
                  photometric_preset: Optional[str] = None, heavy_preset: Optional[str] = None,
-                 match_hist_reference: Optional[np.ndarray] = None, match_hist_bank: Optional[HistReferenceBank] = None):
+                 match_hist_reference: Optional[np.ndarray] = None, match_hist_bank: Optional[HistReferenceBank] = None,
+                 heavy_interp: str = "linear"):
+        _check_interp(heavy_interp)
         if match_hist_reference is not None and match_hist_bank is not None:
             raise ValueError("AugmentedBatches: match_hist_reference (one image for every sample) or match_hist_bank, not both")
         if match_hist_bank is not None and not isinstance(match_hist_bank, HistReferenceBank):
@@ -214,7 +218,7 @@ class AugmentedBatches:
         self.batches = DeviceBatches(iterator, device, depth)
         self.preset, self.rng = preset, rng
         self.num_classes, self.crop_size, self.rescale, self.resample_verts = num_classes, crop_size, rescale, resample_verts
-        self.photometric_preset, self.heavy_preset = photometric_preset, heavy_preset
+        self.photometric_preset, self.heavy_preset, self.heavy_interp = photometric_preset, heavy_preset, heavy_interp
         self.match_hist = None if match_hist_reference is None else HistReference(match_hist_reference, device)
         self.match_hist_bank = match_hist_bank
         if match_hist_bank is not None:
@@ -236,7 +240,8 @@ class AugmentedBatches:
             index = self.last_match_index = self.rng.integers(self.match_hist_bank.size, size=images.shape[0])
         if self.heavy_preset is not None:
             self.last_params = AugmentParams.identity(images.shape[0])
-            self.last_plan = sample_heavy_plan(images.shape[0], self.heavy_preset, self.rng, images.shape[1], images.shape[2])
+            self.last_plan = sample_heavy_plan(images.shape[0], self.heavy_preset, self.rng, images.shape[1], images.shape[2],
+                                               interp=self.heavy_interp)
             return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
                                  resample_verts=self.resample_verts, verts=verts, heavy=self.last_plan,
                                  match_hist=self.match_hist, match_hist_index=index)

@@ -6,11 +6,18 @@ PROGRAM that one HIP entry point (``csrc/geometric.hip``) runs over uint8 ``[B,H
 move the mask, and with it the point cloud the sampler draws.
 
 A program has ``S`` slots per sample (``S <= 8``); slot ``s`` of sample ``i`` is ``opcode[i, s]`` with ``iarg[i, s, :4]`` (int32:
-interpolation order 0 / 1, border mode, cval 0..255, one opcode argument), ``farg[i, s, :32]`` (float64) and ``seed[i, s]``
+interpolation order 0 / 1 / 3, border mode, cval 0..255, one opcode argument), ``farg[i, s, :32]`` (float64) and ``seed[i, s]``
 (uint64).  Every slot is one resampling: a source coordinate ``(sx, sy)`` per output pixel ``(x, y)`` in float64, then
 
 * order 0: the texel at ``floor(s + 0.5)``; order 1: bilinear over ``floor(s)`` and ``floor(s) + 1`` per axis, summed in f6's
   order, ``floor(v + 0.5)`` clipped to [0, 255]; the value is uint8 again between two slots
+* order 3 (f8b): the Keys cubic convolution with ``A = -0.75`` (the constant OpenCV documents for ``INTER_CUBIC``) over the 4 x 4
+  neighbours ``floor(s) - 1 .. floor(s) + 2``.  With ``t = s - floor(s)``, ``u = t + 1``, ``r = 1 - t``, float64, every operation
+  rounded on its own: ``wm = ((A u - 5 A) u + 8 A) u - 4 A``, ``w0 = ((A + 2) t - (A + 3)) t t + 1``, ``w1 = ((A + 2) r - (A + 3)) r r
+  + 1``, ``w2 = ((1 - wm) - w0) - w1``; a row is ``((p[-1] wxm + p[0] wx0) + p[1] wx1) + p[2] wx2``, the four rows are summed
+  likewise with the y weights, ``floor(v + 0.5)`` clipped to [0, 255] (the clip is live: cubic overshoots).  An integer
+  coordinate returns the texel's bits.  A program that holds an order-3 slot runs through ``pcuda_geometric_cubic``, a kernel
+  instance of its own (``GeoProgram.uses_cubic()``, a host-side look); every other program runs where it always ran
 * border mode per neighbour index: ``MODE_CONSTANT`` (``cval``; scipy ``grid-constant``), ``MODE_EDGE`` (``nearest``),
   ``MODE_REFLECT`` (no edge repeat; ``mirror``), ``MODE_SYMMETRIC`` (``reflect``), ``MODE_WRAP`` (``grid-wrap``)
 * masks take order 0 and constant 0 at the same coordinate, whatever the image's order, mode and cval are (f6's rule)
@@ -36,7 +43,10 @@ plain-numpy restatement).  One divergence from the reference's recipe is left: i
 ``CropAndPad`` with all ten modes of ``numpy.pad`` (``pad_mode=ia.ALL``: the five above plus ``linear_ramp``, ``maximum``,
 ``mean``, ``median``, ``minimum``) lives in ``utils/croppad.py`` (f14) as a program of its own: the presets
 ``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` of ``sample_heavy_plan`` draw it, while ``set_crop_and_pad`` here
-and the four older presets keep the five modes above.  NOT built: interpolation orders above 1; the string ``"heavy"``
+and the four older presets keep the five modes above.  Order 3 is pinned by ``tests/golden/geometric_cubic.npz``
+(``scripts/make_geometric_cubic_golden.py``: the numpy restatement and one in exact rational arithmetic); it is NOT scipy's
+``order=3`` (no spline prefilter) and not cv2's 1/32-pixel fixed-point tables, and the samplers draw it only with
+``interp="cubic"`` (every elastic slot; imgaug's elastic default).  NOT built: order 2, 4 and 5; the string ``"heavy"``
 keeps raising ``NotImplementedError``.  ``Superpixels``, ``SimplexNoiseAlpha(EdgeDetect | DirectedEdgeDetect)`` and
 ``AddToHueAndSaturation`` live in ``utils/stylize.py`` (f9): the presets ``"heavy_full_device"`` and
 ``"mscmrseg_aug2_full_device"`` of ``sample_heavy_plan`` interleave them with the entries of this file and f7's."""
@@ -59,6 +69,7 @@ MODE_CONSTANT, MODE_EDGE, MODE_REFLECT, MODE_SYMMETRIC, MODE_WRAP = range(5)
 MODE_NAMES = ("CONSTANT", "EDGE", "REFLECT", "SYMMETRIC", "WRAP")
 MAX_SLOTS, IARGS, FARGS = 8, 4, 32
 MAX_ELASTIC_RADIUS = 4
+ORDERS = (0, 1, 3)                     # nearest, bilinear, Keys cubic (f8b)
 
 # data_generator_mscmrseg.py:25-43, 74-76
 FLIP_LR_P, FLIP_UD_P, SOMETIMES_P = 0.5, 0.2, 0.5
@@ -178,9 +189,13 @@ class GeoProgram(SlotProgram):
         self.farg[i, s, :g * g] = (gx[None, :] + dx).reshape(-1)
         self.farg[i, s, 16:16 + g * g] = (gy[:, None] + dy).reshape(-1)
 
+    def uses_cubic(self) -> bool:
+        """any live slot of order 3 (a host-side look at the program: it picks the entry point)"""
+        return bool(np.any((self.opcode != OP_NOP) & (self.iarg[..., 0] == 3)))
+
     def validate(self, h: Optional[int] = None, w: Optional[int] = None) -> None:
         """Raises ``ValueError`` for a program the kernel is not defined on: shapes and dtypes, more than 8 slots, unknown
-        opcodes, non-finite arguments, an order outside {0, 1}, a mode outside 0..4, a cval outside 0..255, an elastic
+        opcodes, non-finite arguments, an order outside {0, 1, 3}, a mode outside 0..4, a cval outside 0..255, an elastic
         radius above 4, a negative alpha or weights that are not normalised, G outside 2..4, a homography with
         ``|det| <= 1e-12`` or -- when ``h`` and ``w`` are given -- a denominator that is not positive at the four output
         corners; ``h`` or ``w`` below 2."""
@@ -189,8 +204,8 @@ class GeoProgram(SlotProgram):
         if (h is not None and h < 2) or (w is not None and w < 2):
             raise ValueError("GeoProgram: H and W must be at least 2")
         live = op != OP_NOP
-        if np.any((ia[live][:, 0] != 0) & (ia[live][:, 0] != 1)):
-            raise ValueError("GeoProgram: order must be 0 or 1")
+        if not np.all(np.isin(ia[live][:, 0], ORDERS)):
+            raise ValueError("GeoProgram: order must be 0, 1 or 3 (nearest, bilinear, cubic)")
         if np.any((ia[live][:, 1] < 0) | (ia[live][:, 1] > MODE_WRAP)):
             raise ValueError("GeoProgram: mode must be in 0..4")
         if np.any((ia[live][:, 2] < 0) | (ia[live][:, 2] > 255)):
@@ -242,7 +257,7 @@ def geometric_aug(images: torch.Tensor, masks: Optional[torch.Tensor], program: 
         raise TypeError("geometric_aug: uint8 [B,H,W,C] images")
     b, h, w, _ = images.shape
     up = upload_geo_program(program, b, h, w, images.device)
-    out, lab_out = K.geometric(images, as_labels(masks), *up)
+    out, lab_out = K.geometric(images, as_labels(masks), *up, cubic=program.uses_cubic())
     return out, like_masks(lab_out, masks)
 
 
@@ -261,7 +276,7 @@ def _draw_geo(b, rng, h, w):
         jitter=np.clip(rng.standard_normal((b, 4, 2)) * ps_scale[:, None, None], -PERSPECTIVE_MAX_JITTER, PERSPECTIVE_MAX_JITTER))
 
 
-def _encode_geo(prog, i, s, entry, d, h, w):
+def _encode_geo(prog, i, s, entry, d, h, w, elastic_order=1):
     if entry == ENTRY_FLIPLR:
         prog.set_flip_lr(i, s, w)
     elif entry == ENTRY_FLIPUD:
@@ -274,7 +289,7 @@ def _encode_geo(prog, i, s, entry, d, h, w):
         prog.set_affine(i, s, h, w, d["scale"][i, 0], d["scale"][i, 1], d["translate"][i, 0], d["translate"][i, 1],
                         d["rotate"][i], d["shear"][i], int(d["order"][i]), int(d["mode"][i]), int(d["cval"][i]))
     elif entry == ENTRY_ELASTIC:
-        prog.set_elastic(i, s, d["alpha"][i], ELASTIC_SIGMA, d["seed"][i])
+        prog.set_elastic(i, s, d["alpha"][i], ELASTIC_SIGMA, d["seed"][i], order=elastic_order)
     elif entry == ENTRY_PIECEWISE:
         prog.set_piecewise(i, s, h, w, d["pw_dx"][i], d["pw_dy"][i])
     else:

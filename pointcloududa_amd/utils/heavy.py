@@ -1,7 +1,13 @@
 """The recipes of the heavy pipelines on the device: which entries of the four operator
 families (``photometric``, ``geometric``, ``stylize``, ``croppad``) a preset holds, how one batch selects and orders them
 (``_select``), the plan that interleaves them (``sample_heavy_plan``, ``HeavyPlan``, ``heavy_aug``) and the geometric / stylize
-entries of a preset alone (``sample_geo_program``, ``sample_style_program``).  The operator modules know nothing of presets."""
+entries of a preset alone (``sample_geo_program``, ``sample_style_program``).  The operator modules know nothing of presets.
+
+``interp`` (f8b), a keyword of the three samplers: ``"linear"`` (the default) draws what has always been drawn.  ``"cubic"``
+encodes every ElasticTransformation slot with order 3 (imgaug's default for it; no extra draw) and, AFTER every other draw
+of the call, draws one more ``rng.random(B)``: the SimplexNoiseAlpha slot of sample ``i`` takes ``UPSCALE_CUBIC`` where that value
+is below ``stylize.NOISE_CUBIC_P`` (0.35, this build's choice: recalled as imgaug's default weight, not checkable here).  Every
+other array equals the linear draw of the same generator state.  No preset is added."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -89,12 +95,27 @@ def _select(b, spec, rng):
     return entries, np.stack(on, axis=1)
 
 
+INTERPS = ("linear", "cubic")
+
+
+def _check_interp(interp):
+    if interp not in INTERPS:
+        raise ValueError("unknown interp %r (have: %s)" % (interp, ", ".join(INTERPS)))
+    return interp == "cubic"
+
+
+def _cubic_upscale(prog, cubic_draw):
+    """the noise-alpha slots of the samples whose draw fell below NOISE_CUBIC_P upscale cubically"""
+    pick = (prog.opcode == St.OP_NOISE_ALPHA_CONV3X3) & (cubic_draw < St.NOISE_CUBIC_P)[:, None]
+    prog.iarg[..., 1][pick] = St.UPSCALE_CUBIC
+
+
 def _draw_photo(b, rng):
     """f7's nine entries with one seed per ENTRY (``sample_program`` draws one per slot)"""
     return draw_photo(b, rng, (b, 9))
 
 
-def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> GeoProgram:
+def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int, interp: str = "linear") -> GeoProgram:
     """Draw the GEOMETRIC entries of one batch of a preset for ``h x w`` images, as one program (the photometric entries
     of the recipe are skipped: ``sample_heavy_plan`` interleaves both).
 
@@ -106,21 +127,25 @@ def sample_geo_program(batch: int, preset: str, rng: np.random.Generator, h: int
     N(0, scale), scale 0.01-0.1, clipped to 0.45), in one random order per batch.  ``"mscmrseg_aug2_device"``
     (``:89-130``), 1 slot: ``sometimes`` CropAndPad.  On ``"heavy_refpad_device"`` the six entries without CropAndPad (which is
     a ``CropPadProgram`` there, f14); ``"mscmrseg_aug2_refpad_device"`` holds no geometric entry (0 slots).  imgaug's own
-    parameter stream is not reproduced (parity unpinned)."""
+    parameter stream is not reproduced (parity unpinned).  ``interp="cubic"``: every elastic slot has order 3, and one
+    ``rng.random(batch)`` is consumed after every other draw (unused here: the three samplers consume alike)."""
+    cubic = _check_interp(interp)
     entries, on = _select(batch, _check_preset(preset), rng)
     d = _draw_geo(batch, rng, h, w)
+    if cubic:
+        rng.random(batch)
     geo = [k for k, e in enumerate(entries) if e[0] == "g"]
     prog = GeoProgram.identity(batch, len(geo))
     for i in range(batch):
         s = 0
         for k in geo:
             if on[i, k]:
-                _encode_geo(prog, i, s, entries[k][1], d, h, w)
+                _encode_geo(prog, i, s, entries[k][1], d, h, w, elastic_order=3 if cubic else 1)
                 s += 1
     return prog
 
 
-def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> StyleProgram:
+def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: int, w: int, interp: str = "linear") -> StyleProgram:
     """Draw the three STYLE entries of one batch of a preset (``"heavy_full_device"`` or ``"mscmrseg_aug2_full_device"``) for
     ``h x w`` images as one program of three slots, in the batch's order (the other entries of the recipe are skipped:
     ``sample_heavy_plan`` interleaves all kinds): ``sometimes(0.5)`` Superpixels (p_replace U(0, 1), n_segments 20..200 ->
@@ -128,10 +153,13 @@ def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: i
     with direction U(0, 1); 1..3 grids of 2..16 cells per side, nearest | bilinear, min | mean | max, sigmoid with a threshold
     from N(0, 5)) and AddToHueAndSaturation (v integer in -20..20: ds = v, dh = floor(v 180 / 255 + 0.5)), each only for the
     samples whose ``SomeOf((0, 5))`` drew it.  The ``_connected_`` presets draw what their ``_refpad_`` twins draw and give every
-    Superpixels slot ``min_size = superpixel_min_size(gy, gx, h, w)``."""
+    Superpixels slot ``min_size = superpixel_min_size(gy, gx, h, w)``.  ``interp="cubic"``: one more ``rng.random(batch)`` after
+    every other draw; the SimplexNoiseAlpha slot of sample ``i`` upscales cubically where it is below ``NOISE_CUBIC_P``."""
+    cubic = _check_interp(interp)
     spec = _check_preset(preset)
     entries, on = _select(batch, spec, rng)
     d = St.draw_style(batch, rng)
+    cubic_draw = rng.random(batch) if cubic else None
     sty = [k for k, e in enumerate(entries) if e[0] == "s"]
     if not sty:
         raise ValueError("preset %r holds no stylize entry (have: %s, %s)" % (preset, HEAVY_FULL_PRESET, AUG2_FULL_PRESET))
@@ -142,6 +170,8 @@ def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: i
             if on[i, k]:
                 St.encode_style(prog, i, s, entries[k][1], d, h, w, connected=bool(spec.get("connected")))
                 s += 1
+    if cubic:
+        _cubic_upscale(prog, cubic_draw)
     return prog
 
 
@@ -157,7 +187,7 @@ class HeavyPlan:
         return all(st.is_identity() for st in self.stages)
 
 
-def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int, w: int) -> HeavyPlan:
+def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int, w: int, interp: str = "linear") -> HeavyPlan:
     """Draw the whole recipe of one batch: photometric and geometric entries interleaved by ``random_order=True`` (one outer
     and one inner order per batch).  Consecutive photometric entries form one ``PhotoProgram``, consecutive geometric entries
     one ``GeoProgram``; a stage has as many slots as its busiest sample uses, a stage nobody uses is dropped.
@@ -178,12 +208,18 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
 
     ``"heavy_connected_device"`` and ``"mscmrseg_aug2_connected_device"`` (f9b): the ``_refpad_`` presets, draw for draw, with
     ``min_size = superpixel_min_size(gy, gx, h, w)`` in ``iarg[5]`` of every Superpixels slot (connected segments,
-    ``csrc/spx_connect.hip``); every other array of the plan equals the ``_refpad_`` plan of the same generator state."""
+    ``csrc/spx_connect.hip``); every other array of the plan equals the ``_refpad_`` plan of the same generator state.
+
+    ``interp="cubic"`` (f8b, any preset): every elastic slot has order 3 and, after every other draw of the call, one
+    ``rng.random(batch)`` decides per sample whether its SimplexNoiseAlpha slot upscales cubically (below ``NOISE_CUBIC_P``);
+    every other array of the plan equals the ``"linear"`` plan of the same generator state."""
+    cubic = _check_interp(interp)
     spec = _check_preset(preset)
     entries, on = _select(batch, spec, rng)
     dg, dp = _draw_geo(batch, rng, h, w), _draw_photo(batch, rng)
     ds = St.draw_style(batch, rng) if any(e[0] == "s" for e in entries) else None
     pad_mode = rng.integers(0, 10, batch) if any(e[0] == "c" for e in entries) else None
+    cubic_draw = rng.random(batch) if cubic else None
     used = [k for k in range(len(entries)) if on[:, k].any()]      # (an entry nobody drew does not split a stage)
     entries, on = [entries[k] for k in used], on[:, used]
     plan = HeavyPlan(batch)
@@ -210,8 +246,10 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
                             prog.set_crop_and_pad(i, crop_pad_pixels(t, h), crop_pad_pixels(r, w), crop_pad_pixels(bt, h),
                                                   crop_pad_pixels(l, w), int(pad_mode[i]), int(dg["crop_cval"][i]))
                         else:
-                            _encode_geo(prog, i, s, entry, dg, h, w)
+                            _encode_geo(prog, i, s, entry, dg, h, w, elastic_order=3 if cubic else 1)
                         s += 1
+            if cubic and kind == "s":
+                _cubic_upscale(prog, cubic_draw)
             plan.stages.append(prog)
         k = e
     return plan

@@ -16,14 +16,17 @@ A program has ``S`` slots per sample (``S <= 8``); slot ``s`` of sample ``i`` is
                             (H + dh) mod 180``, ``S' = clip(S + ds, 0, 255)``; back through ``p = rdiv(V (255 - S'), 255)``,
                             ``q = rdiv(V (7650 - S' F), 7650)``, ``t = rdiv(V (7650 - S' (30 - F)), 7650)``, ``F = H' % 30``, by
                             sector ``H' // 30``: (V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q)
-``OP_NOISE_ALPHA_CONV3X3``  ``iarg[0]`` = n (1..3 grids), ``iarg[1]`` = upscale (``UPSCALE_NEAREST`` | ``UPSCALE_BILINEAR``),
+``OP_NOISE_ALPHA_CONV3X3``  ``iarg[0]`` = n (1..3 grids), ``iarg[1]`` = upscale (``UPSCALE_NEAREST`` | ``UPSCALE_BILINEAR`` | ``UPSCALE_CUBIC``),
                             ``iarg[2]`` = aggregation (``AGG_MIN`` | ``AGG_MEAN`` | ``AGG_MAX``), ``iarg[3]`` = sigmoid on,
                             ``iarg[4 + 2 k : 6 + 2 k]`` = (h', w') of grid k (2..16 each), ``table[256 k + y w' + x]`` = its values
                             in [0, 1] (``simplex_grid``, evaluated HERE in float64, as f7 evaluates the Gaussian's weights),
                             ``farg[0..8]`` = 3x3 correlation weights (``edge_detect_weights``, ``directed_edge_weights``),
                             ``farg[9]`` = the sigmoid's threshold t.  Each grid is upscaled to H x W (nearest: cell
                             ``((y h') // H, (x w') // W)``; bilinear: source ``(y + 0.5) h' / H - 0.5`` clamped to
-                            ``[0, h' - 1]``), the n masks are aggregated (the mean sums in grid order), optionally
+                            ``[0, h' - 1]``; cubic (``UPSCALE_CUBIC = 3``, f8b): the same source coordinate UNCLAMPED, the
+                            Keys weights (A = -0.75) and summation order of ``utils/geometric.py``'s order 3 over the taps
+                            ``floor(s) - 1 .. floor(s) + 2``, each tap index clamped into the grid, the upscaled value
+                            clipped to [0, 1]), the n masks are aggregated (the mean sums in grid order), optionally
                             ``m = 1 / (1 + exp(-(20 (m - 0.5) - t)))``; ``e = to_u8(f7's CONV3X3)`` (reflect-101 border),
                             ``out = to_u8((1 - m) x + m e)``; float64 in this order, one m for all channels
 ``OP_SUPERPIXELS``          ``iarg[0:2]`` = (gy, gx), ``gy gx <= 256``; ``iarg[2]`` = updates (0..10), ``iarg[3]`` = M2 =
@@ -55,7 +58,8 @@ unpinned, the convention is this build's own and is pinned by ``tests/golden/sty
 a vectorised numpy restatement and an independent one -- plain Python integers for hue and superpixels, scipy for
 noise-alpha).  Divergences from imgaug: hue / saturation follow the integer formulas above (cv2's uint8 HSV tables differ by
 a grey level in places) and one value moves both (``per_channel`` is not built); the simplex noise is this file's (gradient
-from Philox, grids of at most 16 x 16, nearest and bilinear upscale only -- no cubic); the superpixels are a grid SLIC without
+from Philox, grids of at most 16 x 16; the cubic upscale is the Keys kernel in float64, not cv2's fixed-point tables, and the
+samplers draw it only with ``interp="cubic"``, for a share of ``NOISE_CUBIC_P`` of the slots); the superpixels are a grid SLIC without
 imgaug's downscale to 128 pixels, and without a connectivity pass unless ``min_size`` asks for one (above).  The string ``"heavy"`` keeps raising (imgaug's parameter
 stream is not reproduced)."""
 from __future__ import annotations
@@ -75,7 +79,7 @@ OP_NAMES = ("NOP", "HUE_SATURATION", "NOISE_ALPHA_CONV3X3", "SUPERPIXELS")
 MAX_SLOTS, IARGS, FARGS = 8, 12, 16
 GRID_VALUES, MAX_GRIDS = 256, 3
 TABLE = MAX_GRIDS * GRID_VALUES
-UPSCALE_NEAREST, UPSCALE_BILINEAR = 0, 1
+UPSCALE_NEAREST, UPSCALE_BILINEAR, UPSCALE_CUBIC = 0, 1, 3      # (2 is no upscale and keeps raising)
 AGG_MIN, AGG_MEAN, AGG_MAX = 0, 1, 2
 MAX_SEGMENTS, MAX_UPDATES = 256, 10
 MAX_CONNECT_PIXELS = 1 << 24      # connected slots: the segment sums are 32-bit
@@ -90,6 +94,9 @@ HUE_VALUE = (-20, 20)
 # this build's own (imgaug's defaults where it has one): 1..3 grids of 2..16 cells per side, nearest or bilinear with equal
 # probability, min / mean / max with equal probability, the sigmoid always on with a threshold drawn from N(0, 5)
 NOISE_ITERATIONS, NOISE_SIZE, NOISE_SIGMOID_P, NOISE_THRESH_SIGMA = (1, 3), (2, 16), 1.0, 5.0
+# interp="cubic" (f8b): the share of noise-alpha slots whose upscale becomes cubic.  This build's choice: recalled as the
+# weight imgaug's default upscale_method gives "cubic", which cannot be checked here (imgaug is not installed)
+NOISE_CUBIC_P = 0.35
 
 _M32 = np.uint64(0xFFFFFFFF)
 _F2, _G2 = 0.5 * (math.sqrt(3.0) - 1.0), (3.0 - math.sqrt(3.0)) / 6.0
@@ -290,8 +297,8 @@ class StyleProgram(SlotProgram):
         if len(i):
             if np.any((i[:, 0] < 1) | (i[:, 0] > MAX_GRIDS)):
                 raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 grid count (iarg[0]) must be in 1..3")
-            if np.any((i[:, 1] != UPSCALE_NEAREST) & (i[:, 1] != UPSCALE_BILINEAR)):
-                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 upscale (iarg[1]) must be 0 (nearest) or 1 (bilinear)")
+            if not np.all(np.isin(i[:, 1], (UPSCALE_NEAREST, UPSCALE_BILINEAR, UPSCALE_CUBIC))):
+                raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 upscale (iarg[1]) must be 0 (nearest), 1 (bilinear) or 3 (cubic)")
             if np.any((i[:, 2] < AGG_MIN) | (i[:, 2] > AGG_MAX)):
                 raise ValueError("StyleProgram: NOISE_ALPHA_CONV3X3 aggregation (iarg[2]) must be 0 (min), 1 (mean) or 2 (max)")
             if np.any((i[:, 3] != 0) & (i[:, 3] != 1)):

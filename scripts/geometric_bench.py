@@ -13,7 +13,15 @@ B = 32, 256x256x3 uint8 images (6.3 MB) with int32 labels (8.4 MB):
 
 (a), (b) are timed with the host running ahead of the device (a spin kernel goes first).
 
-    python scripts/geometric_bench.py [--iters 100] [--out profiles/geometric_bench.json]"""
+    python scripts/geometric_bench.py [--iters 100] [--out profiles/geometric_bench.json]
+
+``--cubic`` (f8b) measures something else and nothing of the above: per opcode, with labels, the order-1 row through
+``pcuda_geometric`` (the kernel instance that serves orders 0 and 1), the same order-1 program through ``pcuda_geometric_cubic``
+(what the second instance costs a program without order 3, which ``geometric_aug`` never sends there) and the order-3 row, ``--runs``
+times over; the result goes under the key ``"geometric"`` of ``--out`` (other keys of an existing file are kept:
+``stylize_bench.py --cubic`` writes its own into the same file).
+
+    python scripts/geometric_bench.py --cubic [--runs 5] [--out profiles/geometric_cubic_bench.json]"""
 import argparse
 import json
 import os
@@ -55,14 +63,75 @@ def host_ms(fn, reps):
     return 1e3 * (time.perf_counter() - t0) / reps
 
 
+def order_rows():
+    """name -> order-1 program of one opcode, every sample the same encoder (the rows of --cubic)"""
+    rng = np.random.default_rng(7)
+    jit = rng.normal(0, 0.1, (4, 2)).clip(-0.45, 0.45)
+    dx, dy = rng.normal(0, 0.05 * W, (4, 4)), rng.normal(0, 0.05 * H, (4, 4))
+    aff = dict(scale_x=0.8, scale_y=1.2, translate_x=0.2, translate_y=-0.2, rotate=45.0, shear=16.0)
+    return {
+        "affine_constant": one_op("set_affine", H, W, order=1, mode=0, cval=7, **aff),
+        "affine_reflect": one_op("set_affine", H, W, order=1, mode=2, **aff),
+        "affine_wrap": one_op("set_affine", H, W, order=1, mode=4, **aff),
+        "crop_and_pad": one_op("set_crop_and_pad", H, W, 26, -13, 25, -12, 3, 0),
+        "perspective": one_op("set_perspective", H, W, jit),
+        "elastic_r1": one_op("set_elastic", 3.5, 0.25, 1234567),
+        "elastic_r4": one_op("set_elastic", 20.0, 1.0, 1234567),
+        "piecewise_g4": one_op("set_piecewise", H, W, dx, dy),
+    }
+
+
+def merge_out(path, key, value):
+    """write ``value`` under ``key`` of the JSON file ``path``, keeping its other keys"""
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    doc[key] = value
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
+def cubic_main(args, dev):
+    x = np.concatenate([PG.make_images("grey3", 16, H, W, C, 71), PG.make_images("smooth", 8, H, W, C, 72),
+                        PG.make_images("random", 8, H, W, C, 73)])
+    lab = np.argmax(synth_batch(B, 1, K, H, seed=3)[1], axis=1).astype(np.int32)
+    tx, tl32 = torch.from_numpy(x).to(dev), torch.from_numpy(lab).to(dev)
+    out, out_lab = torch.empty_like(tx), torch.empty_like(tl32)
+    rows = {}
+    for name, prog in order_rows().items():
+        up1 = P.upload_geo_program(prog, B, H, W, dev)
+        prog.iarg[..., 0] = 3
+        up3 = P.upload_geo_program(prog, B, H, W, dev)
+        rows[name + "_order1"] = (up1, False)
+        rows[name + "_order1_cubic_entry"] = (up1, True)
+        rows[name + "_order3"] = (up3, True)
+    runs = []
+    for _ in range(args.runs):
+        runs.append({name: round(device_ms(lambda: KK.geometric(tx, tl32, *up, out=out, labels_out=out_lab, cubic=cubic), args.iters), 4)
+                     for name, (up, cubic) in rows.items()})
+    r = {"shape": [B, H, W, C], "iters": args.iters, "build": _lib.csrc_hash(), "with_labels": True, "runs_ms": runs,
+         "median_ms": {k: round(float(np.median([q[k] for q in runs])), 4) for k in runs[0]},
+         "min_max_ms": {k: [min(q[k] for q in runs), max(q[k] for q in runs)] for k in runs[0]},
+         "clock_ghz_under_load": round(KK.clock_ghz_under_load(dev), 3)}
+    print(json.dumps(r), flush=True)
+    if args.out:
+        merge_out(args.out, "geometric", r)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None, help="also write the result to this JSON file")
+    ap.add_argument("--cubic", action="store_true", help="order-1 against order-3 rows per opcode (f8b) and nothing else")
+    ap.add_argument("--runs", type=int, default=5, help="--cubic: how often every row is measured")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("geometric_bench: needs a HIP device")
     dev = torch.device("cuda", 0)
+    if args.cubic:
+        return cubic_main(args, dev)
     x = np.concatenate([PG.make_images("grey3", 16, H, W, C, 71), PG.make_images("smooth", 8, H, W, C, 72),
                         PG.make_images("random", 8, H, W, C, 73)])
     lab = np.argmax(synth_batch(B, 1, K, H, seed=3)[1], axis=1).astype(np.int64)

@@ -14,7 +14,13 @@
 
 (a) and (b) are timed with the host running ahead of the device (a spin kernel goes first).
 
-    python scripts/stylize_bench.py [--iters 100] [--out profiles/stylize_bench.json]"""
+    python scripts/stylize_bench.py [--iters 100] [--out profiles/stylize_bench.json]
+
+``--cubic`` (f8b) measures the noise-alpha slot alone -- one 2x2 grid and three 16x16 grids (mean, sigmoid), each with the
+bilinear and with the cubic upscale -- ``--runs`` times over and writes it under the key ``"stylize"`` of ``--out`` (other keys of
+an existing file are kept: ``geometric_bench.py --cubic`` writes its own into the same file).
+
+    python scripts/stylize_bench.py --cubic [--runs 5] [--out profiles/geometric_cubic_bench.json]"""
 import argparse
 import json
 import os
@@ -56,14 +62,42 @@ def host_ms(fn, reps):
     return 1e3 * (time.perf_counter() - t0) / reps
 
 
+def cubic_main(args, dev):
+    from geometric_bench import merge_out
+    x = np.concatenate([G.make_images("grey3", 16, H, W, C, 71), G.make_images("smooth", 8, H, W, C, 72),
+                        G.make_images("random", 8, H, W, C, 73)])
+    tx = torch.from_numpy(x).to(dev)
+    out = torch.empty_like(tx)
+    small = [S.simplex_grid(2, 2, 5)]
+    large = [S.simplex_grid(16, 16, 5 + k) for k in range(3)]
+    rows = {}
+    for up_name, up_mode in (("bilinear", S.UPSCALE_BILINEAR), ("cubic", S.UPSCALE_CUBIC)):
+        rows["noise_alpha_1x2x2_%s" % up_name] = one_op("set_noise_alpha", S.edge_detect_weights(0.8), small, up_mode, S.AGG_MIN, False, 0.0)
+        rows["noise_alpha_3x16x16_%s_sigmoid" % up_name] = one_op("set_noise_alpha", S.directed_edge_weights(0.8, 0.3), large, up_mode,
+                                                                  S.AGG_MEAN, True, 1.0)
+    ups = {name: S.upload_style_program(prog, B, H, W, C, dev) for name, prog in rows.items()}
+    runs = [{name: round(device_ms(lambda: KK.stylize(tx, *up, out=out), args.iters), 4) for name, up in ups.items()}
+            for _ in range(args.runs)]
+    r = {"shape": [B, H, W, C], "iters": args.iters, "build": _lib.csrc_hash(), "runs_ms": runs,
+         "median_ms": {k: round(float(np.median([q[k] for q in runs])), 4) for k in runs[0]},
+         "min_max_ms": {k: [min(q[k] for q in runs), max(q[k] for q in runs)] for k in runs[0]}}
+    print(json.dumps(r), flush=True)
+    if args.out:
+        merge_out(args.out, "stylize", r)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default=None, help="also write the result to this JSON file")
+    ap.add_argument("--cubic", action="store_true", help="the noise-alpha slot, bilinear against cubic (f8b), and nothing else")
+    ap.add_argument("--runs", type=int, default=5, help="--cubic: how often every row is measured")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stylize_bench: needs a HIP device")
     dev = torch.device("cuda", 0)
+    if args.cubic:
+        return cubic_main(args, dev)
     x = np.concatenate([G.make_images("grey3", 16, H, W, C, 71), G.make_images("smooth", 8, H, W, C, 72),
                         G.make_images("random", 8, H, W, C, 73)])
     lab = np.argmax(synth_batch(B, 1, K, H, seed=3)[1], axis=1).astype(np.int64)
