@@ -44,8 +44,9 @@ struct TapSet {
   }
 };
 
+// (zero-initialised: src travels whole into kernel arguments and the device-resident job table, conv_igemm.hip fill_pack)
 static inline TapSet fwd_taps(const pcuda_conv_geom* g) {
-  TapSet t; t.n = 0;
+  TapSet t = {};
   for (int ky = 0; ky < g->k; ++ky)
     for (int kx = 0; kx < g->k; ++kx) {
       t.dy[t.n] = (signed char)(ky * g->dil - g->pad);
@@ -61,7 +62,7 @@ static inline int posmod(int a, int m) { return ((a % m) + m) % m; }
 
 // taps of the dgrad parity class (ry, rx): dX[s*m + ry] = sum_ky dY[m + (ry + pad - ky*dil)/s] w[ky]
 static inline TapSet dgrad_taps(const pcuda_conv_geom* g, int ry, int rx) {
-  TapSet t; t.n = 0;
+  TapSet t = {};
   const int s = g->stride;
   for (int ky = 0; ky < g->k; ++ky) {
     const int vy = ry + g->pad - ky * g->dil;
@@ -183,6 +184,68 @@ bool rs_layer_ok(const pcuda_conv_geom* g, int rows, int red, int prec);
 bool rs_map_ok(int n, int h, int w);
 int rs_tiles(int n, int h, int w);
 int rs_try_launch(const IgemmParams& p, int prec, const TapSet& taps, hipStream_t s, int* rc);
+
+// ------------------------------------------------------------------------------------------
+// What lies where in a layer's packed weight buffers: THE place that knows (sizes, packers and launches all walk this).
+// Forward buffer: the ordinary image, then the anti-phase image behind it.  Data-gradient buffer: the two paired row-class
+// images, or one image per stride-parity class (ry-major) followed by the anti-phase image -- which only a stride-1 layer
+// has, behind its single class.  A class without taps has no image.  Depends on the LAYER only (kernel, stride, padding,
+// dilation, channels, precision): a packed buffer is valid for whatever map the layer later runs on.
+// ------------------------------------------------------------------------------------------
+static inline size_t packed_elems(int rows, int red, int ntaps, int prec) {   // bf16 elements of one ordinary / pair image
+  const int co_tile = 32 * ig_co_blks(rows);
+  const int n_co_tiles = cdiv(rows, co_tile), nchunks = cdiv(red, 32);
+  return (size_t)n_co_tiles * nchunks * ntaps * co_tile * (ig_rec_bytes(prec == PCUDA_PREC_BF16X3) / 2);
+}
+
+enum { SIDE_FWD = 0, SIDE_DGRAD = 1 };
+enum { IMG_ORDINARY = 0, IMG_PAIR = 1, IMG_AP = 2 };
+struct PackedImage {
+  int kind;
+  int rows, red;            // rows and reduction channels of the launch that reads it (pair: 2 x cin rows)
+  long long s_row, s_red;   // element strides of a row / a reduction index in the fp32 weights [cout][cin][k][k]
+  int ry, rx;               // data gradient: the parity class (pair: the row class)
+  size_t off, bytes;        // inside the side's buffer
+  TapSet taps;              // (anti-phase image: the taps of the ordinary image in front of it)
+};
+struct PackedLayout {
+  int n;
+  size_t bytes;                          // of the whole buffer
+  PackedImage img[IG_MAX_TAPS + 1];      // every class with an image owns a tap, + the anti-phase image
+  const PackedImage* ap() const { return n > 0 && img[n - 1].kind == IMG_AP ? &img[n - 1] : nullptr; }
+  const PackedImage* cls(int ry, int rx) const {       // the image of a parity class, or NULL (no taps)
+    for (int i = 0; i < n; ++i)
+      if (img[i].kind != IMG_AP && img[i].ry == ry && img[i].rx == rx) return &img[i];
+    return nullptr;
+  }
+};
+static inline void packed_layout(const pcuda_conv_geom* g, int prec, int side, PackedLayout* L) {
+  const int kk = g->k * g->k;
+  const bool fwd = side == SIDE_FWD;
+  const int rows = fwd ? g->cout : g->cin, red = fwd ? g->cin : g->cout;
+  const long long s_row = fwd ? (long long)g->cin * kk : kk, s_red = fwd ? kk : (long long)g->cin * kk;
+  L->n = 0; L->bytes = 0;
+  auto add = [&](int kind, int r, const TapSet& t, int ry, int rx) {
+    PackedImage& im = L->img[L->n++];
+    im.kind = kind; im.rows = r; im.red = red; im.s_row = s_row; im.s_red = s_red; im.ry = ry; im.rx = rx; im.taps = t;
+    im.off = L->bytes;
+    im.bytes = kind == IMG_AP ? ap_layer_packed_bytes(r, red) : packed_elems(r, red, t.n, prec) * 2;
+    L->bytes += im.bytes;
+  };
+  if (fwd) {
+    add(IMG_ORDINARY, rows, fwd_taps(g), 0, 0);
+  } else if (dgrad_pair_ok(g)) {          // (no anti-phase image: stride 2)
+    for (int ry = 0; ry < 2; ++ry) add(IMG_PAIR, 2 * rows, dgrad_pair_taps(g, ry), ry, 0);
+    return;
+  } else {
+    for (int ry = 0; ry < g->stride; ++ry)
+      for (int rx = 0; rx < g->stride; ++rx) {
+        const TapSet t = dgrad_taps(g, ry, rx);
+        if (t.n) add(IMG_ORDINARY, rows, t, ry, rx);
+      }
+  }
+  if (ap_layer_ok(g, rows, red, prec)) add(IMG_AP, rows, L->img[0].taps, 0, 0);
+}
 
 // direct (vector-ALU) kernels of the degenerate layers (conv_direct.hip); each returns 1 when it took the launch
 int direct_fwd_tiles(const pcuda_conv_geom* g);

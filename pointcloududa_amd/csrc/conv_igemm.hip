@@ -19,31 +19,7 @@
 // ------------------------------------------------------------------------------------------
 // weight repack: fp32 [rows][red][taps] (any strides) -> bf16 [co_tile][chunk][tap][CO_TILE][40]
 // ------------------------------------------------------------------------------------------
-__global__ void pack_kernel(const PackParams p) {
-  const long long total = (long long)p.n_co_tiles * p.nchunks * p.ntaps * p.co_tile * p.rec;
-  for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long long)gridDim.x * blockDim.x) {
-    // record = 40 bf16 (bf16 mode: 32 values + 8 pad) or 72 (bf16x3: 32 hi | 32 lo | 8 pad)
-    int col = (int)(idx % p.rec);
-    long long rest = idx / p.rec;
-    int row = (int)(rest % p.co_tile); rest /= p.co_tile;
-    int t = (int)(rest % p.ntaps); rest /= p.ntaps;
-    int ch = (int)(rest % p.nchunks);
-    int cot = (int)(rest / p.nchunks);
-    const bool is_lo = p.rec > IG_REC && col >= 32;
-    const int cc = is_lo ? col - 32 : col;
-    int r = cot * p.co_tile + row, c = ch * 32 + cc;
-    float v = 0.f;
-    if (cc < 32 && r < p.rows && c < p.red)
-      v = p.w[(p.pair ? r >> 1 : r) * p.s_row + c * p.s_red + p.tap_src[p.pair ? (r & 1) * p.ntaps + t : t]];
-    __bf16 hi = (__bf16)v;
-    if (is_lo) hi = (__bf16)(v - (float)hi);
-    p.out[idx] = __builtin_bit_cast(uint16_t, hi);
-  }
-}
-
-
-// several repacks of one weight tensor in one launch (forward layout + every dgrad parity class): blockIdx.y = job
+// one or several repacks of one weight tensor in one launch (forward layout + every dgrad parity class): blockIdx.y = job
 #define PACK_MAX_JOBS 5
 struct PackJobs {
   int n;
@@ -214,37 +190,47 @@ int ig_plan_mode() {
   return mode;
 }
 
-size_t packed_elems(int rows, int red, int ntaps, int prec) {   // bf16 elements of one packed layout (both planes)
-  const int co_tile = 32 * ig_co_blks(rows);
-  const int n_co_tiles = cdiv(rows, co_tile), nchunks = cdiv(red, 32);
-  return (size_t)n_co_tiles * nchunks * ntaps * co_tile * (ig_rec_bytes(prec == PCUDA_PREC_BF16X3) / 2);
-}
-
-// pair: rows = 2 x the source rows, (source row, column class) interleaved; taps.src holds both classes' sources
-size_t fill_pack(PackParams& p, const float* w, uint16_t* out, int prec, int rows, int red, long long s_row,
-                 long long s_red, const TapSet& taps, bool pair = false) {
-  p.w = w; p.out = out;
-  p.rows = rows; p.red = red; p.s_row = s_row; p.s_red = s_red;
-  p.ntaps = taps.n;
-  p.pair = pair ? 1 : 0;
-  memcpy(p.tap_src, taps.src, sizeof(p.tap_src));
-  p.co_tile = 32 * ig_co_blks(rows);
-  p.n_co_tiles = cdiv(rows, p.co_tile);
-  p.nchunks = cdiv(red, 32);
-  const size_t plane = packed_elems(rows, red, taps.n, prec);
+// the repack job of one image (conv_host.h: packed_layout) of the buffer `buf`; false: an anti-phase image of taps that are not 3x3
+// (pair: rows = 2 x the source rows, (source row, column class) interleaved; taps.src holds both classes' sources)
+bool fill_pack(PackParams& p, const float* w, void* buf, int prec, const PackedImage& im) {
+  unsigned char* out = (unsigned char*)buf + im.off;
+  if (im.kind == IMG_AP) return ap_fill_pack(p, w, out, im.rows, im.red, im.s_row, im.s_red, im.taps);
+  p.w = w; p.out = (uint16_t*)out;
+  p.rows = im.rows; p.red = im.red; p.s_row = im.s_row; p.s_red = im.s_red;
+  p.ntaps = im.taps.n;
+  p.pair = im.kind == IMG_PAIR ? 1 : 0;
+  memcpy(p.tap_src, im.taps.src, sizeof(p.tap_src));
+  p.co_tile = 32 * ig_co_blks(im.rows);
+  p.n_co_tiles = cdiv(im.rows, p.co_tile);
+  p.nchunks = cdiv(im.red, 32);
   p.rec = ig_rec_bytes(prec == PCUDA_PREC_BF16X3) / 2;
-  return plane;
+  return true;
 }
 
-int launch_pack(const float* w, uint16_t* out, int prec, int rows, int red, long long s_row, long long s_red,
-                const TapSet& taps, hipStream_t s, bool pair = false) {
-  if (taps.n == 0) return PCUDA_OK;
-  PackParams p;
-  const size_t plane = fill_pack(p, w, out, prec, rows, red, s_row, s_red, taps, pair);
-  const int blocks = (int)((plane + 255) / 256 > 4096 ? 4096 : (plane + 255) / 256);
-  hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, s, p);
-  PCUDA_CHECK_LAUNCH("pack_kernel");
+int launch_pack_jobs(const PackJobs& jobs, size_t max_elems, int max_blocks, hipStream_t s) {
+  const int blocks = (int)std::min<size_t>((max_elems + 255) / 256, max_blocks);
+  hipLaunchKernelGGL(pack_multi_kernel, dim3(blocks, jobs.n), dim3(256), 0, s, jobs);
+  PCUDA_CHECK_LAUNCH("pack_multi_kernel");
   return PCUDA_OK;
+}
+
+// one image in a launch of its own
+int launch_pack(const float* w, void* buf, int prec, const PackedImage& im, hipStream_t s) {
+  if (im.kind == IMG_AP)
+    return ap_launch_pack(w, (unsigned char*)buf + im.off, im.rows, im.red, im.s_row, im.s_red, im.taps, s);
+  PackJobs jobs = {};
+  jobs.n = 1;
+  fill_pack(jobs.p[0], w, buf, prec, im);
+  return launch_pack_jobs(jobs, im.bytes / 2, 4096, s);
+}
+
+// every image of one side of a layer, one launch each (pcuda_conv2d_pack_fwd / _dgrad)
+int pack_side(const pcuda_conv_geom* g, int prec, int side, const float* w, void* packed, hipStream_t s) {
+  PackedLayout L;
+  packed_layout(g, prec, side, &L);
+  int rc = PCUDA_OK;
+  for (int i = 0; i < L.n && rc == PCUDA_OK; ++i) rc = launch_pack(w, packed, prec, L.img[i], s);
+  return rc;
 }
 
 // pick taps-per-group and LDS size; returns <0 when nothing fits.  fat: one workgroup per CU (160 KiB),
@@ -367,8 +353,36 @@ int plan_igemm(int rows, int red, int n, int lh, int lw, int in_h, int in_w, int
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// THE route of a layer on given maps: which kernel family its geometry selects and how many tiles that family writes --
+// what a caller sizes its BatchNorm partial sums by (pcuda_conv2d_fwd_tiles / _dgrad_tiles) and what launch_igemm holds a
+// launch with partial sums to.  Layer properties (ap_layer_ok, rs_layer_ok) AND map properties (ap_map_ok, rs_map_ok: they
+// depend on n and read their knobs per call).  Data gradient: stride-1 layers only (one launch); others have no one count.
+// plan = false: the tiles of ROUTE_IGEMM are not worked out (-1: whatever the plan of the launch has)
+// ------------------------------------------------------------------------------------------
+enum { ROUTE_DIRECT, ROUTE_AP, ROUTE_RS, ROUTE_IGEMM };
+struct ConvRoute {
+  int family, tiles;
+};
+ConvRoute conv_route(const pcuda_conv_geom* g, int prec, int side, bool plan = true) {
+  const bool fwd = side == SIDE_FWD;
+  if (!fwd && g->stride != 1) return {ROUTE_IGEMM, 0};
+  const int rows = fwd ? g->cout : g->cin, red = fwd ? g->cin : g->cout;
+  if (const int d = fwd ? direct_fwd_tiles(g) : direct_dgrad_tiles(g)) return {ROUTE_DIRECT, d};
+  if (ap_layer_ok(g, rows, red, prec) && ap_map_ok(g->n, g->in_h, g->in_w, rows)) return {ROUTE_AP, ap_tiles(g->n, g->in_h, g->in_w)};
+  if (rs_layer_ok(g, rows, red, prec) && rs_map_ok(g->n, g->in_h, g->in_w)) return {ROUTE_RS, rs_tiles(g->n, g->in_h, g->in_w)};
+  if (!plan) return {ROUTE_IGEMM, -1};
+  IgemmPlan pl;
+  const bool x3 = prec == PCUDA_PREC_BF16X3;
+  const int rc = fwd ? plan_igemm(rows, red, g->n, g->out_h, g->out_w, g->in_h, g->in_w, g->stride, fwd_taps(g), x3, &pl)
+                     : plan_igemm(rows, red, g->n, g->in_h, g->in_w, g->out_h, g->out_w, 1, dgrad_taps(g, 0, 0), x3, &pl);
+  return {ROUTE_IGEMM, rc < 0 ? 0 : g->n * pl.tiles_x * pl.tiles_y};
+}
+
 // ap_image: the layer's anti-phase image (behind its ordinary packed layout), or NULL
-int launch_igemm(IgemmParams& p, int prec, const TapSet& taps, hipStream_t s, const unsigned char* ap_image = nullptr) {
+// expect: the route of a launch with partial sums (p.stats): the tiles its caller sized them by
+int launch_igemm(IgemmParams& p, int prec, const TapSet& taps, hipStream_t s, const unsigned char* ap_image = nullptr,
+                 const ConvRoute* expect = nullptr) {
   {
     int rc;
     if (ap_image && prec == PCUDA_PREC_BF16X3 && ap_try_launch(p, taps, ap_image, s, &rc)) return rc;
@@ -381,16 +395,12 @@ int launch_igemm(IgemmParams& p, int prec, const TapSet& taps, hipStream_t s, co
   if (plan_igemm(p.cout, p.cin, p.n, p.lh, p.lw, p.in_h, p.in_w, p.in_step, taps, x3, &pl, true) < 0)
     PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "igemm: no tile of this convolution fits LDS (in_step %d, tap span %d)",
                p.in_step, taps.dy_max - taps.dy_min);
-  // (a launch the anti-phase kernel was expected to take -- the caller sized its partial sums by THAT kernel's tiles -- but did
-  //  not, e.g. misaligned tensors: only if this plan writes the same tiles)
-  if (ap_image && p.stats && ap_map_ok(p.n, p.in_h, p.in_w, p.cout) && p.in_step == 1 && !p.fold &&
-      (long long)pl.tiles_x * pl.tiles_y * p.n != ap_tiles(p.n, p.in_h, p.in_w))
-    PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv: tensors the anti-phase kernel cannot address on a map whose ordinary plan has other tiles");
-  // (the same for the row-streaming kernel of the 32 -> 32 layers: its tiles are its work items)
-  if (p.stats && p.cin == 32 && p.cout == 32 && prec == PCUDA_PREC_BF16X3 && taps.n == 9 && p.in_step == 1 && !p.in_shift && !p.fold &&
-      !p.pair && taps.dy_max - taps.dy_min == 2 && rs_map_ok(p.n, p.in_h, p.in_w) && p.lh == p.in_h && p.lw == p.in_w &&
-      (long long)pl.tiles_x * pl.tiles_y * p.n != rs_tiles(p.n, p.in_h, p.in_w))
-    PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv: tensors the row-streaming kernel cannot address on a map whose ordinary plan has other tiles");
+  // (a launch the anti-phase or the row-streaming kernel was expected to take -- the caller sized its partial sums by THAT
+  //  kernel's tiles -- but did not, e.g. misaligned tensors: only if this plan writes the same tiles.  The 2x2 fold's 32 x 8
+  //  plan has the anti-phase kernel's tiles.)
+  if (p.stats && expect && expect->tiles >= 0 && (long long)pl.tiles_x * pl.tiles_y * p.n != expect->tiles)
+    PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv: tensors the %s kernel cannot address on a map whose ordinary plan has other tiles",
+               expect->family == ROUTE_AP ? "anti-phase" : "row-streaming");
   p.n_co_tiles = cdiv(p.cout, co_tile);
   p.nchunks = cdiv(p.cin, 32);
   p.tw = pl.tw; p.th = pl.th; p.tmagic = 65536 / pl.tw + 1; p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y;
@@ -470,65 +480,29 @@ int launch_igemm(IgemmParams& p, int prec, const TapSet& taps, hipStream_t s, co
 
 // ------------------------------------------------------------------------------------------
 // (the anti-phase image of a layer that has one sits BEHIND its ordinary layout: every launch can still take the ordinary kernels)
-extern "C" size_t pcuda_conv2d_packed_fwd_bytes(const pcuda_conv_geom* g, int prec) {
+// (sizes, packers and the batched repack's job list below all walk packed_layout, conv_host.h)
+static size_t packed_bytes(const pcuda_conv_geom* g, int prec, int side) {
   if (!geom_ok(g)) return 0;
-  return packed_elems(g->cout, g->cin, g->k * g->k, prec) * 2 + (ap_layer_ok(g, g->cout, g->cin, prec) ? ap_layer_packed_bytes(g->cout, g->cin) : 0);
+  PackedLayout L;
+  packed_layout(g, prec, side, &L);
+  return L.bytes;
 }
-
-extern "C" size_t pcuda_conv2d_packed_dgrad_bytes(const pcuda_conv_geom* g, int prec) {
-  if (!geom_ok(g)) return 0;
-  size_t tot = 0;
-  if (dgrad_pair_ok(g)) {
-    for (int ry = 0; ry < 2; ++ry) tot += packed_elems(2 * g->cin, g->cout, dgrad_taps(g, ry, 0).n, prec) * 2;
-    return tot;
-  }
-  for (int ry = 0; ry < g->stride; ++ry)
-    for (int rx = 0; rx < g->stride; ++rx) {
-      TapSet t = dgrad_taps(g, ry, rx);
-      tot += packed_elems(g->cin, g->cout, t.n, prec) * 2;
-    }
-  if (ap_layer_ok(g, g->cin, g->cout, prec)) tot += ap_layer_packed_bytes(g->cin, g->cout);
-  return tot;
-}
+extern "C" size_t pcuda_conv2d_packed_fwd_bytes(const pcuda_conv_geom* g, int prec) { return packed_bytes(g, prec, SIDE_FWD); }
+extern "C" size_t pcuda_conv2d_packed_dgrad_bytes(const pcuda_conv_geom* g, int prec) { return packed_bytes(g, prec, SIDE_DGRAD); }
 
 extern "C" int pcuda_conv2d_pack_fwd(const pcuda_conv_geom* g, int prec, const float* w, void* packed,
                                      pcuda_stream_t s) {
   if (!geom_ok(g) || !w || !packed) PCUDA_FAIL(PCUDA_E_BADARG, "pack_fwd: bad geometry or null pointer");
-  const int kk = g->k * g->k;
-  TapSet t = fwd_taps(g);
-  int rc = launch_pack(w, (uint16_t*)packed, prec, g->cout, g->cin, (long long)g->cin * kk, kk, t, (hipStream_t)s);
-  if (rc == PCUDA_OK && ap_layer_ok(g, g->cout, g->cin, prec))
-    rc = ap_launch_pack(w, (unsigned char*)packed + packed_elems(g->cout, g->cin, kk, prec) * 2, g->cout, g->cin,
-                        (long long)g->cin * kk, kk, t, (hipStream_t)s);
-  return rc;
+  return pack_side(g, prec, SIDE_FWD, w, packed, (hipStream_t)s);
 }
 
 extern "C" int pcuda_conv2d_pack_dgrad(const pcuda_conv_geom* g, int prec, const float* w, void* packed,
                                        pcuda_stream_t s) {
   if (!geom_ok(g) || !w || !packed) PCUDA_FAIL(PCUDA_E_BADARG, "pack_dgrad: bad geometry or null pointer");
-  const int kk = g->k * g->k;
-  uint16_t* out = (uint16_t*)packed;
-  if (dgrad_pair_ok(g)) {
-    for (int ry = 0; ry < 2; ++ry) {
-      TapSet t = dgrad_pair_taps(g, ry);
-      int rc = launch_pack(w, out, prec, 2 * g->cin, g->cout, kk, (long long)g->cin * kk, t, (hipStream_t)s, true);
-      if (rc) return rc;
-      out += packed_elems(2 * g->cin, g->cout, t.n, prec);
-    }
-    return PCUDA_OK;
-  }
-  for (int ry = 0; ry < g->stride; ++ry)
-    for (int rx = 0; rx < g->stride; ++rx) {
-      TapSet t = dgrad_taps(g, ry, rx);
-      int rc = launch_pack(w, out, prec, g->cin, g->cout, kk, (long long)g->cin * kk, t, (hipStream_t)s);
-      if (rc) return rc;
-      out += packed_elems(g->cin, g->cout, t.n, prec);
-    }
-  if (ap_layer_ok(g, g->cin, g->cout, prec))
-    return ap_launch_pack(w, (unsigned char*)out, g->cin, g->cout, kk, (long long)g->cin * kk, dgrad_taps(g, 0, 0), (hipStream_t)s);
-  return PCUDA_OK;
+  return pack_side(g, prec, SIDE_DGRAD, w, packed, (hipStream_t)s);
 }
 
+// the ordinary and pair images of both sides in ONE launch, the anti-phase images behind it
 extern "C" int pcuda_conv2d_pack_all(const pcuda_conv_geom* g, int prec, const float* w, void* packed_fwd,
                                      void* packed_dgrad, pcuda_stream_t s) {
   if (!geom_ok(g) || !w || !packed_fwd) PCUDA_FAIL(PCUDA_E_BADARG, "pack_all: bad geometry or null pointer");
@@ -537,57 +511,49 @@ extern "C" int pcuda_conv2d_pack_all(const pcuda_conv_geom* g, int prec, const f
     if (rc == PCUDA_OK && packed_dgrad) rc = pcuda_conv2d_pack_dgrad(g, prec, w, packed_dgrad, s);
     return rc;
   }
-  const int kk = g->k * g->k;
-  PackJobs jobs;
-  jobs.n = 0;
-  size_t maxplane = fill_pack(jobs.p[jobs.n++], w, (uint16_t*)packed_fwd, prec, g->cout, g->cin, (long long)g->cin * kk,
-                              kk, fwd_taps(g));
-  if (packed_dgrad && dgrad_pair_ok(g)) {
-    uint16_t* out = (uint16_t*)packed_dgrad;
-    for (int ry = 0; ry < 2; ++ry) {
-      const size_t plane = fill_pack(jobs.p[jobs.n++], w, out, prec, 2 * g->cin, g->cout, kk, (long long)g->cin * kk,
-                                     dgrad_pair_taps(g, ry), true);
-      if (plane > maxplane) maxplane = plane;
-      out += plane;
+  void* const buf[2] = {packed_fwd, packed_dgrad};
+  PackedLayout L[2];
+  PackJobs jobs = {};
+  size_t max_elems = 0;
+  for (int side = 0; side < 2 && buf[side]; ++side) {
+    packed_layout(g, prec, side, &L[side]);
+    for (int i = 0; i < L[side].n; ++i) {
+      const PackedImage& im = L[side].img[i];
+      if (im.kind == IMG_AP) continue;
+      fill_pack(jobs.p[jobs.n++], w, buf[side], prec, im);
+      max_elems = std::max(max_elems, im.bytes / 2);
     }
-  } else if (packed_dgrad) {
-    uint16_t* out = (uint16_t*)packed_dgrad;
-    for (int ry = 0; ry < g->stride; ++ry)
-      for (int rx = 0; rx < g->stride; ++rx) {
-        TapSet t = dgrad_taps(g, ry, rx);
-        if (t.n == 0) continue;
-        const size_t plane = fill_pack(jobs.p[jobs.n++], w, out, prec, g->cin, g->cout, kk, (long long)g->cin * kk, t);
-        if (plane > maxplane) maxplane = plane;
-        out += plane;
-      }
   }
-  const int blocks = (int)((maxplane + 255) / 256 > 2048 ? 2048 : (maxplane + 255) / 256);
-  hipLaunchKernelGGL(pack_multi_kernel, dim3(blocks, jobs.n), dim3(256), 0, (hipStream_t)s, jobs);
-  PCUDA_CHECK_LAUNCH("pack_multi_kernel");
-  if (ap_layer_ok(g, g->cout, g->cin, prec)) {
-    int rc = ap_launch_pack(w, (unsigned char*)packed_fwd + packed_elems(g->cout, g->cin, kk, prec) * 2, g->cout, g->cin,
-                            (long long)g->cin * kk, kk, fwd_taps(g), (hipStream_t)s);
-    if (rc) return rc;
-  }
-  if (packed_dgrad && ap_layer_ok(g, g->cin, g->cout, prec)) {   // (stride 1: one class in front of the image)
-    TapSet t = dgrad_taps(g, 0, 0);
-    int rc = ap_launch_pack(w, (unsigned char*)packed_dgrad + packed_elems(g->cin, g->cout, t.n, prec) * 2, g->cin, g->cout, kk,
-                            (long long)g->cin * kk, t, (hipStream_t)s);
-    if (rc) return rc;
-  }
-  return PCUDA_OK;
+  int rc = launch_pack_jobs(jobs, max_elems, 2048, (hipStream_t)s);
+  for (int side = 0; side < 2 && buf[side] && rc == PCUDA_OK; ++side)
+    if (const PackedImage* im = L[side].ap()) rc = launch_pack(w, buf[side], prec, *im, (hipStream_t)s);
+  return rc;
 }
 
 extern "C" int pcuda_conv2d_fwd_tiles(const pcuda_conv_geom* g, int prec) {
-  if (!geom_ok(g)) return 0;
-  if (const int d = direct_fwd_tiles(g)) return d;
-  if (ap_layer_ok(g, g->cout, g->cin, prec) && ap_map_ok(g->n, g->in_h, g->in_w, g->cout)) return ap_tiles(g->n, g->in_h, g->in_w);
-  if (rs_layer_ok(g, g->cout, g->cin, prec) && rs_map_ok(g->n, g->in_h, g->in_w)) return rs_tiles(g->n, g->in_h, g->in_w);
-  TapSet t = fwd_taps(g);
-  IgemmPlan pl;
-  if (plan_igemm(g->cout, g->cin, g->n, g->out_h, g->out_w, g->in_h, g->in_w, g->stride, t, prec == PCUDA_PREC_BF16X3, &pl) < 0)
-    return 0;
-  return g->n * pl.tiles_x * pl.tiles_y;
+  return geom_ok(g) ? conv_route(g, prec, SIDE_FWD).tiles : 0;
+}
+
+// a data-gradient launch: the image `im` of the buffer `packed` (NULL: a parity class without taps -- the launch only clears
+// its pixels and reads no weights) over lh x lw logical pixels stored at (oy * mul + oy_off, ox * mul + ox_off).  The pair,
+// mask, reduce and fold fields are the caller's.
+static IgemmParams dgrad_params(const pcuda_conv_geom* g, const pcuda_src* dy, const pcuda_dst* dx, const void* packed,
+                                const PackedImage* im, int lh, int lw, int mul, int oy_off, int ox_off, int accumulate) {
+  IgemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.x = *dy; p.cin = g->cout;
+  p.in_h = g->out_h; p.in_w = g->out_w; p.in_shift = 0; p.in_row = g->out_w;
+  p.y = *dx; p.cout = im ? im->rows : g->cin; p.out_w = g->in_w;
+  p.lh = lh; p.lw = lw;
+  p.oy_mul = p.ox_mul = mul; p.oy_off = oy_off; p.ox_off = ox_off;
+  p.in_step = 1;
+  p.wpack = (const uint16_t*)((const unsigned char*)packed + (im ? im->off : 0)); p.w_lo_off = 0;   // (both planes live in one record)
+  p.bias = nullptr; p.slope = 1.f; p.accumulate = accumulate; p.stats = nullptr;
+  p.n = g->n;
+  return p;
+}
+static const unsigned char* image_ptr(const void* packed, const PackedImage* im) {
+  return im ? (const unsigned char*)packed + im->off : nullptr;
 }
 
 extern "C" int pcuda_conv2d_forward(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const void* packed_w,
@@ -604,6 +570,8 @@ extern "C" int pcuda_conv2d_forward(const pcuda_conv_geom* g, int prec, const pc
     if (direct_d5_forward(g, prec, x, packed_w, bias, slope, y, bn_partials, (hipStream_t)s, &rc)) return rc;
     if (direct_d1_forward(g, prec, x, packed_w, bias, slope, y, bn_partials, (hipStream_t)s, &rc)) return rc;
   }
+  PackedLayout L;
+  packed_layout(g, prec, SIDE_FWD, &L);
   IgemmParams p;
   memset(&p, 0, sizeof(p));
   p.x = *x; p.cin = g->cin;
@@ -612,14 +580,12 @@ extern "C" int pcuda_conv2d_forward(const pcuda_conv_geom* g, int prec, const pc
   p.lh = g->out_h; p.lw = g->out_w;
   p.oy_mul = p.ox_mul = 1; p.oy_off = p.ox_off = 0;
   p.in_step = g->stride;
-  p.wpack = (const uint16_t*)packed_w;
+  p.wpack = (const uint16_t*)image_ptr(packed_w, &L.img[0]);
   p.w_lo_off = 0;   // (both planes live in one record)
   p.bias = bias; p.slope = slope; p.accumulate = 0; p.stats = bn_partials;
   p.n = g->n;
-  TapSet t = fwd_taps(g);
-  const unsigned char* ap_image = ap_layer_ok(g, g->cout, g->cin, prec)
-                                      ? (const unsigned char*)packed_w + packed_elems(g->cout, g->cin, g->k * g->k, prec) * 2 : nullptr;
-  return launch_igemm(p, prec, t, (hipStream_t)s, ap_image);
+  const ConvRoute route = bn_partials ? conv_route(g, prec, SIDE_FWD, false) : ConvRoute{ROUTE_IGEMM, -1};
+  return launch_igemm(p, prec, L.img[0].taps, (hipStream_t)s, image_ptr(packed_w, L.ap()), &route);
 }
 
 // mask_a != NULL: the LeakyReLU backward of the layer in front rides in the epilogue (pcuda_conv2d_dgrad_lrelu)
@@ -629,61 +595,27 @@ static int dgrad_impl(const pcuda_conv_geom* g, int prec, const pcuda_src* dy, c
   if (!geom_ok(g)) PCUDA_FAIL(PCUDA_E_BADARG, "conv2d_dgrad: inconsistent geometry");
   if (!src_ok(dy, g->cout) || !dst_ok(dx, g->cin) || !packed_w_dgrad) PCUDA_FAIL(PCUDA_E_BADARG, "conv2d_dgrad: bad tensors");
   if (prec != PCUDA_PREC_BF16X3 && prec != PCUDA_PREC_BF16) PCUDA_FAIL(PCUDA_E_BADARG, "conv2d_dgrad: bad precision");
+  PackedLayout L;
+  packed_layout(g, prec, SIDE_DGRAD, &L);
   if (!mask_a) {
     int rc;
     if (direct_dgrad(g, prec, dy, packed_w_dgrad, dx, accumulate, (hipStream_t)s, &rc)) return rc;
-    if (direct_d1_dgrad(g, prec, dy, packed_w_dgrad, dx, accumulate, packed_elems(g->cin, g->cout, 4, prec), (hipStream_t)s, &rc))
-      return rc;
+    // (the d1 kernel's layers have the four-class layout: four images of one size)
+    if (direct_d1_dgrad(g, prec, dy, packed_w_dgrad, dx, accumulate, L.img[0].bytes / 2, (hipStream_t)s, &rc)) return rc;
   }
-  const uint16_t* wp = (const uint16_t*)packed_w_dgrad;
   const int st = g->stride;
-  if (dgrad_pair_ok(g)) {   // (conv_host.h: one launch per row class, rows = (channel, column class))
-    for (int ry = 0; ry < 2; ++ry) {
-      TapSet t = dgrad_pair_taps(g, ry);
-      const int lh = (g->in_h - ry + 1) / 2, lw = (g->in_w + 1) / 2;
-      if (lh > 0) {
-        IgemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.x = *dy; p.cin = g->cout;
-        p.in_h = g->out_h; p.in_w = g->out_w; p.in_shift = 0; p.in_row = g->out_w;
-        p.y = *dx; p.cout = 2 * g->cin; p.out_w = g->in_w;
-        p.lh = lh; p.lw = lw; p.pair = 1; p.lw2 = g->in_w / 2;
-        p.oy_mul = p.ox_mul = 2; p.oy_off = ry; p.ox_off = 0;
-        p.in_step = 1;
-        p.wpack = wp; p.w_lo_off = 0;
-        p.bias = nullptr; p.slope = 1.f; p.accumulate = accumulate; p.stats = nullptr;
-        p.mask_a = mask_a; p.mask_sn = mask_sn; p.mask_slope = mask_slope;
-        p.n = g->n;
-        int rc = launch_igemm(p, prec, t, (hipStream_t)s);
-        if (rc) return rc;
-      }
-      wp += packed_elems(2 * g->cin, g->cout, t.n, prec);
-    }
-    return PCUDA_OK;
-  }
+  const bool pair = L.img[0].kind == IMG_PAIR;   // (conv_host.h: one launch per row class, rows = (channel, column class))
+  const TapSet none = {};
   for (int ry = 0; ry < st; ++ry)
-    for (int rx = 0; rx < st; ++rx) {
-      TapSet t = dgrad_taps(g, ry, rx);
-      const size_t plane = packed_elems(g->cin, g->cout, t.n, prec);
+    for (int rx = 0; rx < (pair ? 1 : st); ++rx) {
+      const PackedImage* im = L.cls(ry, rx);
       const int lh = (g->in_h - ry + st - 1) / st, lw = (g->in_w - rx + st - 1) / st;
-      if (lh > 0 && lw > 0) {
-        IgemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.x = *dy; p.cin = g->cout;
-        p.in_h = g->out_h; p.in_w = g->out_w; p.in_shift = 0; p.in_row = g->out_w;
-        p.y = *dx; p.cout = g->cin; p.out_w = g->in_w;
-        p.lh = lh; p.lw = lw;
-        p.oy_mul = p.ox_mul = st; p.oy_off = ry; p.ox_off = rx;
-        p.in_step = 1;
-        p.wpack = wp; p.w_lo_off = 0;
-        p.bias = nullptr; p.slope = 1.f; p.accumulate = accumulate; p.stats = nullptr;
-        p.mask_a = mask_a; p.mask_sn = mask_sn; p.mask_slope = mask_slope;
-        p.n = g->n;
-        const unsigned char* ap_image = (!mask_a && ap_layer_ok(g, g->cin, g->cout, prec)) ? (const unsigned char*)(wp + plane) : nullptr;
-        int rc = launch_igemm(p, prec, t, (hipStream_t)s, ap_image);
-        if (rc) return rc;
-      }
-      wp += plane;
+      if (lh <= 0 || lw <= 0) continue;
+      IgemmParams p = dgrad_params(g, dy, dx, packed_w_dgrad, im, lh, lw, st, ry, rx, accumulate);
+      if (pair) { p.pair = 1; p.lw2 = g->in_w / 2; }
+      p.mask_a = mask_a; p.mask_sn = mask_sn; p.mask_slope = mask_slope;
+      int rc = launch_igemm(p, prec, im ? im->taps : none, (hipStream_t)s, mask_a ? nullptr : image_ptr(packed_w_dgrad, L.ap()));
+      if (rc) return rc;
     }
   return PCUDA_OK;
 }
@@ -705,7 +637,7 @@ extern "C" int pcuda_conv2d_dgrad_lrelu(const pcuda_conv_geom* g, int prec, cons
   if (dx->c1 < g->cin || a_sc != dx->sc1 || g->in_up)
     PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv2d_dgrad_lrelu: one NCHW destination with the activation's plane stride");
   // (a data gradient the anti-phase kernel takes has no masked store: the caller runs that kernel + pcuda_lrelu_bwd)
-  if (ap_layer_ok(g, g->cin, g->cout, prec) && ap_map_ok(g->n, g->in_h, g->in_w, g->cin))
+  if (conv_route(g, prec, SIDE_DGRAD, false).family == ROUTE_AP)
     PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv2d_dgrad_lrelu: this layer's data gradient runs on the anti-phase kernel");
   return dgrad_impl(g, prec, dy, packed_w_dgrad, dx, 0, a, a_sn, slope, s);
 }
@@ -726,14 +658,14 @@ extern "C" int pcuda_debug_read_clocks(unsigned long long* out8) {
 // PCUDA_E_UNSUPPORTED otherwise (the caller then runs pcuda_conv2d_dgrad + pcuda_bn_bwd_reduce).
 // ------------------------------------------------------------------------------------------
 extern "C" int pcuda_conv2d_dgrad_tiles(const pcuda_conv_geom* g, int prec) {
-  if (!geom_ok(g) || g->stride != 1) return 0;
-  if (const int d = direct_dgrad_tiles(g)) return d;
-  if (ap_layer_ok(g, g->cin, g->cout, prec) && ap_map_ok(g->n, g->in_h, g->in_w, g->cin)) return ap_tiles(g->n, g->in_h, g->in_w);
-  if (rs_layer_ok(g, g->cin, g->cout, prec) && rs_map_ok(g->n, g->in_h, g->in_w)) return rs_tiles(g->n, g->in_h, g->in_w);
-  TapSet t = dgrad_taps(g, 0, 0);
-  IgemmPlan pl;
-  if (plan_igemm(g->cin, g->cout, g->n, g->in_h, g->in_w, g->out_h, g->out_w, 1, t, prec == PCUDA_PREC_BF16X3, &pl) < 0) return 0;
-  return g->n * pl.tiles_x * pl.tiles_y;
+  return geom_ok(g) ? conv_route(g, prec, SIDE_DGRAD).tiles : 0;
+}
+
+// the single launch of a stride-1 layer's data gradient with partial sums (the fused reduce) in `p`
+static int launch_dgrad_stats(IgemmParams& p, const pcuda_conv_geom* g, int prec, const void* packed, const PackedLayout& L,
+                              hipStream_t s) {
+  const ConvRoute route = conv_route(g, prec, SIDE_DGRAD, false);
+  return launch_igemm(p, prec, L.img[0].taps, s, image_ptr(packed, L.ap()), &route);
 }
 
 extern "C" int pcuda_conv2d_dgrad_bnred(const pcuda_conv_geom* g, int prec, const pcuda_src* dy, const void* packed_w_dgrad,
@@ -751,23 +683,12 @@ extern "C" int pcuda_conv2d_dgrad_bnred(const pcuda_conv_geom* g, int prec, cons
       return rc;
     PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv2d_dgrad_bnred: 1x1 layer with tensors the direct kernel does not take");
   }
-  TapSet t = dgrad_taps(g, 0, 0);
-  IgemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = *dy; p.cin = g->cout;
-  p.in_h = g->out_h; p.in_w = g->out_w; p.in_shift = 0; p.in_row = g->out_w;
-  p.y = *dx; p.cout = g->cin; p.out_w = g->in_w;
-  p.lh = g->in_h; p.lw = g->in_w;
-  p.oy_mul = p.ox_mul = 1; p.oy_off = p.ox_off = 0;
-  p.in_step = 1;
-  p.wpack = (const uint16_t*)packed_w_dgrad; p.w_lo_off = 0;
-  p.bias = nullptr; p.slope = 1.f; p.accumulate = accumulate;
+  PackedLayout L;
+  packed_layout(g, prec, SIDE_DGRAD, &L);
+  IgemmParams p = dgrad_params(g, dy, dx, packed_w_dgrad, &L.img[0], g->in_h, g->in_w, 1, 0, 0, accumulate);
   p.stats = red_partials;
   p.red_a = a; p.red_sn = a_sn; p.red_sc = a_sc; p.red_mean = mean; p.red_invstd = invstd;
-  p.n = g->n;
-  const unsigned char* ap_image = ap_layer_ok(g, g->cin, g->cout, prec)
-                                      ? (const unsigned char*)packed_w_dgrad + packed_elems(g->cin, g->cout, t.n, prec) * 2 : nullptr;
-  return launch_igemm(p, prec, t, (hipStream_t)s, ap_image);
+  return launch_dgrad_stats(p, g, prec, packed_w_dgrad, L, (hipStream_t)s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -787,26 +708,15 @@ extern "C" int pcuda_conv2d_dgrad_fold(const pcuda_conv_geom* g, int prec, const
   if (!g->in_up || g->stride != 1 || (g->in_h & 1) || (g->in_w & 3) || direct_dgrad_tiles(g) ||
       (a && ((((uintptr_t)a) & 7) || (a_sn & 1) || (a_sc & 1))))
     PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "conv2d_dgrad_fold: stride-1 MFMA layers behind a nearest-x2 fold, rows of 4k logical pixels");
-  TapSet t = dgrad_taps(g, 0, 0);
-  IgemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = *dy; p.cin = g->cout;
-  p.in_h = g->out_h; p.in_w = g->out_w; p.in_shift = 0; p.in_row = g->out_w;
-  p.y = *dx_half; p.cout = g->cin; p.out_w = g->in_w >> 1;
-  p.lh = g->in_h; p.lw = g->in_w;
-  p.oy_mul = p.ox_mul = 1; p.oy_off = p.ox_off = 0;
-  p.in_step = 1;
-  p.wpack = (const uint16_t*)packed_w_dgrad; p.w_lo_off = 0;
-  p.bias = nullptr; p.slope = 1.f; p.accumulate = 0;
-  p.fold = 1;
+  PackedLayout L;
+  packed_layout(g, prec, SIDE_DGRAD, &L);
+  IgemmParams p = dgrad_params(g, dy, dx_half, packed_w_dgrad, &L.img[0], g->in_h, g->in_w, 1, 0, 0, 0);
+  p.fold = 1; p.out_w = g->in_w >> 1;   // (the route answers at the logical resolution: the 32 x 8 plan has the anti-phase tiles)
   if (a) {
     p.stats = red_partials;
     p.red_a = a; p.red_sn = a_sn; p.red_sc = a_sc; p.red_mean = mean; p.red_invstd = invstd;
   }
-  p.n = g->n;
-  const unsigned char* ap_image = ap_layer_ok(g, g->cin, g->cout, prec)
-                                      ? (const unsigned char*)packed_w_dgrad + packed_elems(g->cin, g->cout, t.n, prec) * 2 : nullptr;
-  return launch_igemm(p, prec, t, (hipStream_t)s, ap_image);
+  return launch_dgrad_stats(p, g, prec, packed_w_dgrad, L, (hipStream_t)s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -821,40 +731,16 @@ extern "C" int pcuda_conv2d_pack_jobs_fill(const pcuda_conv_geom* g, int prec, c
     PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: bad arguments");
   if (prec != PCUDA_PREC_BF16X3 && prec != PCUDA_PREC_BF16) PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: bad precision");
   PackParams* jobs = (PackParams*)host_jobs;
-  const int kk = g->k * g->k;
+  void* const buf[2] = {packed_fwd, packed_dgrad};
   int nj = 0;
-  size_t plane = fill_pack(jobs[nj], w, (uint16_t*)packed_fwd, prec, g->cout, g->cin, (long long)g->cin * kk, kk, fwd_taps(g));
-  job_blocks[nj] = pack_table_blocks(jobs[nj]); ++nj;
-  if (ap_layer_ok(g, g->cout, g->cin, prec)) {   // the anti-phase image behind the forward layout
-    if (nj >= max_jobs) PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: more layouts than job slots");
-    if (!ap_fill_pack(jobs[nj], w, (unsigned char*)packed_fwd + plane * 2, g->cout, g->cin, (long long)g->cin * kk, kk, fwd_taps(g)))
-      PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: anti-phase image of a layer that is not 3x3");
-    job_blocks[nj] = pack_table_blocks(jobs[nj]); ++nj;
-  }
-  if (packed_dgrad && dgrad_pair_ok(g)) {
-    uint16_t* out = (uint16_t*)packed_dgrad;
-    for (int ry = 0; ry < 2; ++ry) {
+  for (int side = 0; side < 2 && buf[side]; ++side) {   // one job per image, in buffer order
+    PackedLayout L;
+    packed_layout(g, prec, side, &L);
+    for (int i = 0; i < L.n; ++i, ++nj) {
       if (nj >= max_jobs) PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: more layouts than job slots");
-      plane = fill_pack(jobs[nj], w, out, prec, 2 * g->cin, g->cout, kk, (long long)g->cin * kk, dgrad_pair_taps(g, ry), true);
-      job_blocks[nj] = pack_table_blocks(jobs[nj]); ++nj;
-      out += plane;
-    }
-  } else if (packed_dgrad) {
-    uint16_t* out = (uint16_t*)packed_dgrad;
-    for (int ry = 0; ry < g->stride; ++ry)
-      for (int rx = 0; rx < g->stride; ++rx) {
-        TapSet t = dgrad_taps(g, ry, rx);
-        if (t.n == 0) continue;
-        if (nj >= max_jobs) PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: more layouts than job slots");
-        plane = fill_pack(jobs[nj], w, out, prec, g->cin, g->cout, kk, (long long)g->cin * kk, t);
-        job_blocks[nj] = pack_table_blocks(jobs[nj]); ++nj;
-        out += plane;
-      }
-    if (ap_layer_ok(g, g->cin, g->cout, prec)) {   // the anti-phase image behind the (single) data-gradient layout
-      if (nj >= max_jobs) PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: more layouts than job slots");
-      if (!ap_fill_pack(jobs[nj], w, (unsigned char*)out, g->cin, g->cout, kk, (long long)g->cin * kk, dgrad_taps(g, 0, 0)))
+      if (!fill_pack(jobs[nj], w, buf[side], prec, L.img[i]))
         PCUDA_FAIL(PCUDA_E_BADARG, "pack_jobs_fill: anti-phase image of a layer that is not 3x3");
-      job_blocks[nj] = pack_table_blocks(jobs[nj]); ++nj;
+      job_blocks[nj] = pack_table_blocks(jobs[nj]);
     }
   }
   return nj;

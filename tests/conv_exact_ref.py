@@ -1,7 +1,7 @@
 """Operand-exact float64 references of the MFMA convolution kernels, and Python mirrors of the variant keys.
 
 The kernels round their two operands to bf16 with round-to-nearest-even (``pack_bf16x2`` / ``split2``, csrc/common.h:77-91;
-the weights in ``pack_kernel``, csrc/conv_igemm.hip:39-41) and multiply on ``v_mfma_f32_32x32x16_bf16``: a bf16 x bf16 product
+the weights in ``pack_multi_kernel``, csrc/conv_igemm.hip:45-47) and multiply on ``v_mfma_f32_32x32x16_bf16``: a bf16 x bf16 product
 has 16 significant bits and is exact in fp32, so all a correct kernel has left is the rounding of its fp32 accumulation.
 
 * bf16 mode: one product plane, hi x hi, hi = bf16(a).

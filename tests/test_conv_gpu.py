@@ -48,6 +48,10 @@ CASES = [
     (2, 64, 128, 29, 29, 4, 2, 2, 1, False, False, 0.2),
     (3, 3, 64, 1, 300, 1, 1, 0, 1, False, True, 1.0),       # PointNet conv1d(k=1): H = 1
     (3, 128, 1024, 1, 300, 1, 1, 0, 1, False, True, 1.0),
+    # parity classes WITHOUT taps (1x1 / stride 2: three of four; 3x3 / stride 3 has none): no packed image, and the data
+    # gradient still has to clear their pixels
+    (2, 16, 16, 16, 16, 1, 2, 0, 1, False, True, 1.0),
+    (2, 8, 8, 17, 17, 2, 3, 0, 1, False, True, 1.0),
 ]
 
 
@@ -336,6 +340,46 @@ def test_table_repack_matches_the_per_layer_pack(dev, prec):
                     assert torch.equal(img.view(torch.uint8), fresh.view(torch.uint8)), (kind, op.cin, op.cout, op.k)
     finally:
         K.set_precision("bf16x3")
+
+
+# one layer per kind of packed layout (cin, cout, k, stride, pad, dil); only the weights matter: n = 1, 16 x 16 maps
+PACK_ALL_LAYERS = [
+    (8, 16, 3, 1, 1, 1),       # one ordinary image per side
+    (64, 64, 3, 1, 1, 1),      # + the anti-phase image on both sides
+    (24, 40, 4, 2, 2, 1),      # paired column classes
+    (4, 8, 4, 2, 2, 1),        # four parity classes
+    (8, 8, 3, 3, 1, 1),        # stride 3: pack_all falls back to one launch per layout
+    (16, 8, 1, 1, 0, 1),
+    (16, 16, 3, 1, 2, 2),
+]
+
+
+@pytest.mark.parametrize("prec", ["bf16x3", "bf16"])
+def test_pack_all_writes_what_pack_fwd_and_pack_dgrad_write(dev, prec):
+    """pcuda_conv2d_pack_all against the two per-side packers: the same bytes in both buffers and nothing past
+    pcuda_conv2d_packed_*_bytes (buffers prefilled with 0xA5, 256 guard bytes behind each).  No tolerance: bytes."""
+    from pointcloududa_amd import kernels as K
+    lib = K.L.lib()
+    pr = K.L.PREC_BF16X3 if prec == "bf16x3" else K.L.PREC_BF16
+    GUARD = 256
+    torch.manual_seed(11)
+    for cin, cout, k, st, pad, dil in PACK_ALL_LAYERS:
+        o = (16 + 2 * pad - dil * (k - 1) - 1) // st + 1
+        g = K.ConvGeom(1, cin, cout, 16, 16, o, o, k, st, pad, dil, 0)
+        w = torch.randn(cout, cin, k, k, device=dev)
+        nb = [lib.pcuda_conv2d_packed_fwd_bytes(K.C.byref(g), pr), lib.pcuda_conv2d_packed_dgrad_bytes(K.C.byref(g), pr)]
+        assert min(nb) > 0
+        new = lambda: [torch.full((b + GUARD,), 0xA5, dtype=torch.uint8, device=dev) for b in nb]
+        both, each = new(), new()
+        K.check(lib.pcuda_conv2d_pack_all(K.C.byref(g), pr, w.data_ptr(), both[0].data_ptr(), both[1].data_ptr(), K._stream()), "pack_all")
+        K.check(lib.pcuda_conv2d_pack_fwd(K.C.byref(g), pr, w.data_ptr(), each[0].data_ptr(), K._stream()), "pack_fwd")
+        K.check(lib.pcuda_conv2d_pack_dgrad(K.C.byref(g), pr, w.data_ptr(), each[1].data_ptr(), K._stream()), "pack_dgrad")
+        torch.cuda.synchronize()
+        for side in range(2):
+            assert torch.equal(both[side], each[side]), (cin, cout, k, st, side)
+            for buf in (both[side], each[side]):
+                assert bool((buf[nb[side]:] == 0xA5).all()), ("guard overwritten", cin, cout, k, st, side)
+                assert not bool((buf[:nb[side]] == 0xA5).all()), ("nothing written", cin, cout, k, st, side)
 
 
 def test_pruned_build_falls_back_to_the_generic_kernels(dev):
