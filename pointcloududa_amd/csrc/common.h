@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/pcuda_hip.h"
@@ -128,6 +129,13 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// an integer environment switch.  `static const int v = env_knob("PCUDA_X", 1);` reads it once per process; switches that
+// tests change inside one process are read where they are used instead
+static inline int env_knob(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

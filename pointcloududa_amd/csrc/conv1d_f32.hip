@@ -403,5 +403,5 @@ extern "C" int pcuda_conv1d_k1_wgrad(const float* x, const float* dy, float* dw,
     else hipLaunchKernelGGL((c1d_wgrad_kernel<1>), grid, dim3(256), 0, s, p);
     PCUDA_CHECK_LAUNCH("c1d_wgrad_kernel");
   }
-  return launch_wgrad_reduce(p.partial, (long long)cout * cin, ks, dw, accumulate, p.db_partial, cout, db, s);
+  return launch_wgrad_reduce(p.partial, (long long)cout * cin, ks, dw, accumulate, 1, p.db_partial, cout, db, s);
 }

@@ -37,8 +37,6 @@ bool direct_enabled(int bit) {
   return (mask & bit) != 0;
 }
 
-bool aligned16(const void* p, long long sn, long long sc) { return (((uintptr_t)p) & 15) == 0 && (sn & 3) == 0 && (sc & 3) == 0; }
-
 // ------------------------------------------------------------------------------------------
 // 1 -> cout channels, 3x3, stride 1, pad 1
 // ------------------------------------------------------------------------------------------
@@ -498,33 +496,35 @@ int direct_dgrad(const pcuda_conv_geom* g, int prec, const pcuda_src* dy, const 
   return 1;
 }
 
-size_t direct_wgrad_workspace(const pcuda_conv_geom* g) {
+// (a block per 256 4x4-pixel items of an image: the slices of the split-K layout)
+int direct_wgrad_slices(const pcuda_conv_geom* g) {
   if (!c1_geom(g) || (g->in_h & 3)) return 0;
-  const long long blocks = (long long)g->n * cdiv((long long)(g->in_w / 4) * (g->in_h / 4), 256);
-  return (size_t)blocks * g->cout * 10 * sizeof(float) + 256;
+  return g->n * cdiv((long long)(g->in_w / 4) * (g->in_h / 4), 256);
 }
 
-int direct_wgrad(const pcuda_conv_geom* g, const pcuda_src* x, const float* dz, long long dz_sn, long long dz_sc, float* dw,
-                 float* db, int accumulate, void* workspace, hipStream_t s, int* rc) {
-  *rc = PCUDA_OK;
-  if (!direct_enabled(2) || !c1_geom(g) || (g->in_h & 3) || x->scale1) return 0;
-  if (!aligned16(x->p1, x->sn1, 4) || !aligned16(dz, dz_sn, dz_sc)) return 0;
+int direct_wgrad(const WgradCall& c) {
+  const pcuda_conv_geom* g = c.g;
+  const pcuda_src* x = c.x;
+  if (!direct_enabled(2) || !c1_geom(g) || (g->in_h & 3) || x->scale1) return WGRAD_NOT_TAKEN;
+  if (!aligned16(x->p1, x->sn1, 4) || !aligned16(c.dy, c.dy_sn, c.dy_sc)) return WGRAD_NOT_TAKEN;
+  // cin = 1: a slab row is [cout][9] = dw's own layout, no transposition in the reduce (one tap)
+  const WgradSlabs sl = wgrad_slabs(c, direct_wgrad_slices(g), 1);
   C1WgParams p;
   p.x = x->p1; p.x_sn = x->sn1;
-  p.dz = dz; p.dz_sn = dz_sn; p.dz_sc = dz_sc;
-  p.partial = (float*)workspace;
+  p.dz = c.dy; p.dz_sn = c.dy_sn; p.dz_sc = c.dy_sc;
+  p.partial = sl.partial;
   p.n = g->n; p.h = g->in_h; p.w = g->in_w; p.cout = g->cout;
-  const int bpi = cdiv((long long)(g->in_w / 4) * (g->in_h / 4), 256);
+  const int bpi = sl.slices / g->n;
   const double flops = 2.0 * g->n * (double)g->out_h * g->out_w * g->cout * 9.0;
   char tag[96];
   snprintf(tag, sizeof(tag), "direct c1 wgrad n%d cout%d %dx%d", g->n, g->cout, g->in_h, g->in_w);
-  ProfScope prof(PCUDA_FAM_CONV_WGRAD, flops, s, tag);
-  p.nblocks = (long long)bpi * g->n;
-  hipLaunchKernelGGL(c1_wgrad_kernel, dim3(bpi, g->n, g->cout >= 8 ? 2 : 1), dim3(256), 0, s, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { pcuda_set_error("c1_wgrad_kernel: %s", hipGetErrorString(e)); *rc = PCUDA_E_LAUNCH; return 1; }
-  // block partials through the split-K reduce of the MFMA weight-gradient kernels (16 waves per 64 outputs, fixed order)
-  const float* pw = (const float*)workspace;
-  *rc = launch_wgrad_reduce(pw, (long long)g->cout * 9, (int)p.nblocks, dw, accumulate, pw + p.nblocks * g->cout * 9, g->cout, db, s);
-  return 1;
+  ProfScope prof(PCUDA_FAM_CONV_WGRAD, flops, c.s, tag);
+  p.nblocks = sl.slices;
+  hipLaunchKernelGGL(c1_wgrad_kernel, dim3(bpi, g->n, g->cout >= 8 ? 2 : 1), dim3(256), 0, c.s, p);
+  PCUDA_CHECK_LAUNCH("c1_wgrad_kernel");
+  // block partials through the split-K reduce of the MFMA weight-gradient kernels (16 waves per 64 outputs, fixed order),
+  // at once even under pcuda_conv2d_wgrad_partial: the job stays empty
+  WgradCall now = c;
+  now.defer = nullptr;
+  return wgrad_finish(now, sl);
 }

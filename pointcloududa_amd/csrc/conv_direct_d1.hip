@@ -24,7 +24,6 @@ bool direct_enabled(int bit) {
   }
   return (mask & bit) != 0;
 }
-bool aligned16(const void* p, long long sn, long long sc) { return (((uintptr_t)p) & 15) == 0 && (sn & 3) == 0 && (sc & 3) == 0; }
 
 struct D1Params {
   const float* dz; long long dz_sn, dz_sc;    // [n][cout][oh][ow]
@@ -293,21 +292,22 @@ int direct_d1_dgrad(const pcuda_conv_geom* g, int prec, const pcuda_src* dy, con
   return 1;
 }
 
-size_t direct_d1_wgrad_workspace(const pcuda_conv_geom* g) {
+// (no bias slab, and D1_WG_BLOCKS slices whatever the launch uses: a layout of its own)
+size_t direct_d1_wgrad_bytes(const pcuda_conv_geom* g) {
   if (!d1_geom(g) || g->cin > 4) return 0;
   return (size_t)D1_WG_BLOCKS * g->cout * g->cin * 16 * sizeof(float) + 256;
 }
 
-int direct_d1_wgrad(const pcuda_conv_geom* g, const pcuda_src* x, const float* dz, long long dz_sn, long long dz_sc, float* dw,
-                    float* db, int accumulate, void* workspace, hipStream_t s, int* rc) {
-  *rc = PCUDA_OK;
-  if (!direct_enabled(32) || !d1_geom(g) || g->cin > 4 || x->scale1 || x->c1 < g->cin || db) return 0;
-  if (!aligned16(x->p1, x->sn1, x->sc1)) return 0;
+int direct_d1_wgrad(const WgradCall& c) {
+  const pcuda_conv_geom* g = c.g;
+  const pcuda_src* x = c.x;
+  if (!direct_enabled(32) || !d1_geom(g) || g->cin > 4 || x->scale1 || x->c1 < g->cin || c.db) return WGRAD_NOT_TAKEN;
+  if (!aligned16(x->p1, x->sn1, x->sc1)) return WGRAD_NOT_TAKEN;
   D1Params p;
   memset(&p, 0, sizeof(p));
-  p.dz = dz; p.dz_sn = dz_sn; p.dz_sc = dz_sc;
+  p.dz = c.dy; p.dz_sn = c.dy_sn; p.dz_sc = c.dy_sc;
   p.x = x->p1; p.x_sn = x->sn1; p.x_sc = x->sc1;
-  p.partial = (float*)workspace;
+  p.partial = (float*)c.workspace;
   p.n = g->n; p.h = g->in_h; p.w = g->in_w; p.oh = g->out_h; p.ow = g->out_w; p.cin = g->cin; p.cout = g->cout;
   const int items = g->n * g->out_h;
   const int blocks = items < D1_WG_BLOCKS ? items : D1_WG_BLOCKS;
@@ -315,13 +315,12 @@ int direct_d1_wgrad(const pcuda_conv_geom* g, const pcuda_src* x, const float* d
   const double flops = 2.0 * g->n * (double)g->out_h * g->out_w * g->cout * (double)g->cin * 16;
   char tag[96];
   snprintf(tag, sizeof(tag), "direct d1 wgrad n%d cin%d cout%d %dx%d", g->n, g->cin, g->cout, g->in_h, g->in_w);
-  ProfScope prof(PCUDA_FAM_CONV_WGRAD, flops, s, tag);
-  const int numel = g->cout * g->cin * 16;
+  ProfScope prof(PCUDA_FAM_CONV_WGRAD, flops, c.s, tag);
 #define D1_WG_LAUNCH(C_)                                                                                              \
   {                                                                                                                   \
     /* (the attribute is per DEVICE: set on every launch rather than once per process -- the call is cheap) */          \
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)d1_wgrad_kernel<C_>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
-    hipLaunchKernelGGL(d1_wgrad_kernel<C_>, dim3(blocks), dim3(256), lds, s, p, items);                               \
+    hipLaunchKernelGGL(d1_wgrad_kernel<C_>, dim3(blocks), dim3(256), lds, c.s, p, items);                             \
   }
   switch (g->cin) {
     case 1: D1_WG_LAUNCH(1) break;
@@ -330,12 +329,14 @@ int direct_d1_wgrad(const pcuda_conv_geom* g, const pcuda_src* x, const float* d
     default: D1_WG_LAUNCH(4) break;
   }
 #undef D1_WG_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { pcuda_set_error("d1_wgrad_kernel: %s", hipGetErrorString(e)); *rc = PCUDA_E_LAUNCH; return 1; }
+  PCUDA_CHECK_LAUNCH("d1_wgrad_kernel");
   // (the block partials go through the split-K reduce of the MFMA weight-gradient kernels: 16 waves per 64 outputs; a
-  // serial loop over the 768 blocks per output ran longer than the FMA kernel itself)
-  *rc = launch_wgrad_reduce((const float*)workspace, numel, blocks, dw, accumulate, nullptr, 0, nullptr, s);
-  return 1;
+  // serial loop over the 768 blocks per output ran longer than the FMA kernel itself), at once even under
+  // pcuda_conv2d_wgrad_partial: the job stays empty
+  const WgradSlabs sl = {p.partial, nullptr, (long long)g->cout * g->cin * 16, blocks, 1};
+  WgradCall now = c;
+  now.defer = nullptr;
+  return wgrad_finish(now, sl);
 }
 
 // ------------------------------------------------------------------------------------------

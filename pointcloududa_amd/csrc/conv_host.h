@@ -137,6 +137,9 @@ static inline bool fast_src_ok(const pcuda_src* x, int cin) {
   return true;
 }
 
+// 16-byte rows: the base pointer and both strides (in floats) of an [n][c][plane] view
+static inline bool aligned16(const void* p, long long sn, long long sc) { return (((uintptr_t)p) & 15) == 0 && (sn & 3) == 0 && (sc & 3) == 0; }
+
 // fast epilogue (buffer stores): an 8-row register group never straddles the two destinations and every
 // destination image spans < 2^30 bytes
 static inline bool fast_dst_ok(const pcuda_dst* y, int cout) {
@@ -256,28 +259,55 @@ int direct_dgrad(const pcuda_conv_geom* g, int prec, const pcuda_src* dy, const 
                  int accumulate, hipStream_t s, int* rc, const float* red_a = nullptr, long long red_sn = 0,
                  long long red_sc = 0, const float* red_mean = nullptr, const float* red_invstd = nullptr,
                  float* red = nullptr);
-size_t direct_wgrad_workspace(const pcuda_conv_geom* g);
-int direct_wgrad(const pcuda_conv_geom* g, const pcuda_src* x, const float* dz, long long dz_sn, long long dz_sc, float* dw,
-                 float* db, int accumulate, void* workspace, hipStream_t s, int* rc);
 int direct_d1_dgrad(const pcuda_conv_geom* g, int prec, const pcuda_src* dy, const void* packed_w_dgrad, const pcuda_dst* dx,
                     int accumulate, size_t cls_elems, hipStream_t s, int* rc);
-size_t direct_d1_wgrad_workspace(const pcuda_conv_geom* g);
-int direct_d1_wgrad(const pcuda_conv_geom* g, const pcuda_src* x, const float* dz, long long dz_sn, long long dz_sc, float* dw,
-                    float* db, int accumulate, void* workspace, hipStream_t s, int* rc);
-int launch_wgrad_reduce_taps(const float* partial, long long numel, int ksplit, float* dw, int accumulate, int ntaps,
-                             const float* db_partial, long long nb, float* db, hipStream_t s);
-size_t wgrad3r_workspace(const pcuda_conv_geom* g);
-int wgrad3r_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc,
-                float* dw, float* db, int accumulate, void* workspace, hipStream_t s, pcuda_reduce_job* defer, int* rc);
-size_t wgrad1_workspace(const pcuda_conv_geom* g);
-int wgrad1_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc,
-               float* dw, float* db, int accumulate, void* workspace, hipStream_t s, pcuda_reduce_job* defer, int* rc);
-size_t wgrad3_workspace(const pcuda_conv_geom* g);
-int wgrad3_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc,
-               float* dw, float* db, int accumulate, void* workspace, hipStream_t s, pcuda_reduce_job* defer, int* rc);
-int launch_wgrad_reduce(const float* partial, long long numel, int ksplit, float* dw, int accumulate, const float* db_partial,
-                        long long nb, float* db, hipStream_t s);
 int direct_d1_forward(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const void* packed_w, const float* bias,
                       float slope, const pcuda_dst* y, float* bn_partials, hipStream_t s, int* rc);
 int direct_d5_forward(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const void* packed_w, const float* bias,
                       float slope, const pcuda_dst* y, float* bn_partials, hipStream_t s, int* rc);
+
+// ------------------------------------------------------------------------------------------
+// Weight gradient.  One call record goes to every route of the table in conv_wgrad.hip (WGRAD_ROUTES: THE place that knows
+// the route order); a route returns WGRAD_NOT_TAKEN or the PCUDA_* result of the launch it made.  Split-K slabs of every
+// route but direct d1: [slices][welems] partial weights, then [slices][cout] partial biases, + 256 bytes.
+// ------------------------------------------------------------------------------------------
+struct WgradCall {
+  const pcuda_conv_geom* g;
+  int prec;
+  const pcuda_src* x;
+  const float* dy;
+  long long dy_sn, dy_sc;
+  float* dw;
+  float* db;                  // or NULL
+  int accumulate;
+  void* workspace;            // pcuda_conv2d_wgrad_workspace_size(g) bytes
+  hipStream_t s;
+  pcuda_reduce_job* defer;    // not NULL: the route fills it instead of launching the reduce (pcuda_conv2d_wgrad_partial)
+};
+enum { WGRAD_NOT_TAKEN = 1 };   // (every PCUDA_* code is <= 0)
+
+struct WgradSlabs {
+  float* partial;
+  float* db_partial;          // NULL without a bias gradient
+  long long welems;
+  int slices, ntaps;          // ntaps > 1: the slabs are [slice][tap][cout * cin], the reduce transposes into OIHW
+};
+static inline size_t wgrad_slab_bytes(const pcuda_conv_geom* g, int slices) {
+  return ((size_t)slices * g->cout * g->cin * g->k * g->k + (size_t)slices * g->cout) * sizeof(float) + 256;
+}
+WgradSlabs wgrad_slabs(const WgradCall& c, int slices, int ntaps);
+// the tail of every route: fills *c.defer, or launches the reduce of the slabs into dw / db
+int wgrad_finish(const WgradCall& c, const WgradSlabs& sl);
+int launch_wgrad_reduce(const float* partial, long long numel, int ksplit, float* dw, int accumulate, int ntaps,
+                        const float* db_partial, long long nb, float* db, hipStream_t s);
+
+int direct_wgrad_slices(const pcuda_conv_geom* g);
+int direct_wgrad(const WgradCall& c);
+size_t direct_d1_wgrad_bytes(const pcuda_conv_geom* g);
+int direct_d1_wgrad(const WgradCall& c);
+int wgrad3r_slices(const pcuda_conv_geom* g);
+int wgrad3r_wgrad(const WgradCall& c);
+int wgrad3_slices(const pcuda_conv_geom* g);
+int wgrad3_wgrad(const WgradCall& c);
+int wgrad1_slices(const pcuda_conv_geom* g);
+int wgrad1_wgrad(const WgradCall& c);

@@ -10,7 +10,7 @@
 //   * the four waves of a workgroup interleave the steps of one contiguous pixel range (a row's 256 consecutive bytes
 //     per round) and add their accumulators in a fixed order through LDS: one slab per workgroup;
 //   * slabs [slice][co][ci] and the bias partials go through the same reduce as every other weight gradient
-//     (launch_wgrad_reduce_taps with one tap): fixed summation order, bit-reproducible;
+//     (wgrad_finish with one tap): fixed summation order, bit-reproducible;
 //   * lazy BatchNorm (affine on load) and the two-source input (zero-copy concatenation) are per-row constants here.
 #include "conv_device.h"
 #include "conv_host.h"
@@ -210,8 +210,7 @@ struct W1Plan {
 };
 
 bool w1_geom(const pcuda_conv_geom* g) {
-  static int off = -1;
-  if (off < 0) { const char* e = getenv("PCUDA_NO_WGRAD1"); off = (e && atoi(e)) ? 1 : 0; }
+  static const bool off = env_knob("PCUDA_NO_WGRAD1", 0) != 0;
   if (off) return false;
   const long long hw = (long long)g->in_h * g->in_w;
   return g->k == 1 && g->stride == 1 && g->pad == 0 && !g->in_up && (hw & 15) == 0 && hw < (1ll << 28) && g->cin >= 16;
@@ -228,8 +227,7 @@ W1Plan w1_plan(const pcuda_conv_geom* g) {
   // slices: ~768 workgroups in all (measured 768 / 1024 / 2048 / 3072: the single-block layers 0.092 / 0.097 / 0.098 / 0.099 ms,
   // the others flat), the slabs (written once, read once) below an eighth of the operand bytes (8 MB at least), every
   // workgroup at least eight steps
-  static int tgt = -1;
-  if (tgt < 0) { const char* e = getenv("PCUDA_WG1_BLOCKS"); tgt = e ? atoi(e) : 768; }
+  static const int tgt = env_knob("PCUDA_WG1_BLOCKS", 768);
   long long want = tgt / tiles;
   const long long welems = (long long)g->cout * g->cin;
   const long long in_bytes = total * 16 * (g->cin + g->cout) * 4;
@@ -249,42 +247,38 @@ W1Plan w1_plan(const pcuda_conv_geom* g) {
 
 }  // namespace
 
-size_t wgrad1_workspace(const pcuda_conv_geom* g) {
-  if (!w1_geom(g)) return 0;
-  const W1Plan w = w1_plan(g);
-  return ((size_t)w.slices * g->cout * g->cin + (size_t)w.slices * g->cout) * sizeof(float) + 256;
-}
+int wgrad1_slices(const pcuda_conv_geom* g) { return w1_geom(g) ? w1_plan(g).slices : 0; }
 
-// returns 1 when it took the launch (*rc = status)
-int wgrad1_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc,
-               float* dw, float* db, int accumulate, void* workspace, hipStream_t s, pcuda_reduce_job* defer, int* rc) {
-  if (!w1_geom(g)) return 0;
-  auto al = [](const void* q, long long sn, long long sc) { return q == nullptr || ((((uintptr_t)q) & 15) == 0 && (sn & 3) == 0 && (sc & 3) == 0); };
+int wgrad1_wgrad(const WgradCall& c) {
+  const pcuda_conv_geom* g = c.g;
+  const pcuda_src* x = c.x;
+  if (!w1_geom(g)) return WGRAD_NOT_TAKEN;
   const int c1 = x->c1 < g->cin ? x->c1 : g->cin;
-  if (!al(x->p1, x->sn1, x->sc1) || (c1 < g->cin && !al(x->p2, x->sn2, x->sc2)) || !al(dy, dy_sn, dy_sc)) return 0;
+  if (!aligned16(x->p1, x->sn1, x->sc1) || (c1 < g->cin && !aligned16(x->p2, x->sn2, x->sc2)) || !aligned16(c.dy, c.dy_sn, c.dy_sc))
+    return WGRAD_NOT_TAKEN;
   // (a second source needs its own affine pointers resolved per row: both NULL or per-source as given)
-  const bool x3 = prec == PCUDA_PREC_BF16X3;
+  const bool x3 = c.prec == PCUDA_PREC_BF16X3;
   const W1Plan w = w1_plan(g);
+  const WgradSlabs sl = wgrad_slabs(c, w.slices, 1);
   W1Params p;
   memset(&p, 0, sizeof(p));
   p.x = *x; p.x.c1 = c1;
   p.cin = g->cin; p.cout = g->cout; p.n = g->n; p.hw = g->in_h * g->in_w;
-  p.dz = dy; p.dz_sn = dy_sn; p.dz_sc = dy_sc;
-  const long long welems = (long long)g->cout * g->cin;
-  p.partial = (float*)workspace;
-  p.db_partial = db ? (float*)workspace + (size_t)w.slices * welems : nullptr;
+  p.dz = c.dy; p.dz_sn = c.dy_sn; p.dz_sc = c.dy_sc;
+  p.partial = sl.partial;
+  p.db_partial = sl.db_partial;
   p.steps_per_wg = w.steps_per_wg; p.wgs_per_image = w.wgs_per_image;
   p.n_ci_tiles = w.n_ci_tiles; p.tiles = w.n_co_tiles * w.n_ci_tiles;
   const long long nwg = (long long)p.tiles * w.slices;
-  if (nwg >= (1ll << 31)) return 0;
+  if (nwg >= (1ll << 31)) return WGRAD_NOT_TAKEN;
   p.xcd = (nwg >= 16 && (nwg & 7) == 0) ? 1 : 0;
   {
     char tag[160];
     snprintf(tag, sizeof(tag), "wgrad1 n%d cin%d cout%d %dx%d k1 slices%d steps%d tile%dx%d", g->n, g->cin, g->cout, g->in_h,
              g->in_w, w.slices, w.steps_per_wg, 32 * w.co_b, 32 * w.ci_b);
-    ProfScope prof(PCUDA_FAM_CONV_WGRAD, 2.0 * g->n * (double)p.hw * g->cout * (double)g->cin, s, tag);
+    ProfScope prof(PCUDA_FAM_CONV_WGRAD, 2.0 * g->n * (double)p.hw * g->cout * (double)g->cin, c.s, tag);
     const dim3 grid((unsigned)nwg);
-#define W1_LAUNCH(X3_, CO_, CI_) hipLaunchKernelGGL((wgrad1_kernel<X3_, CO_, CI_>), grid, dim3(256), 0, s, p)
+#define W1_LAUNCH(X3_, CO_, CI_) hipLaunchKernelGGL((wgrad1_kernel<X3_, CO_, CI_>), grid, dim3(256), 0, c.s, p)
 #define W1_CI(X3_, CO_)                                                \
   do {                                                                 \
     if (w.ci_b == 3) W1_LAUNCH(X3_, CO_, 3);                           \
@@ -295,19 +289,7 @@ int wgrad1_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const flo
     else { if (w.co_b == 2) W1_CI(false, 2); else W1_CI(false, 1); }
 #undef W1_CI
 #undef W1_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pcuda_set_error("wgrad1_kernel: %s", hipGetErrorString(e)); *rc = PCUDA_E_LAUNCH; return 1; }
+    PCUDA_CHECK_LAUNCH("wgrad1_kernel");
   }
-  int nkg = 1;
-  while (nkg < 16 && nkg * 2 <= w.slices) nkg <<= 1;
-  if (defer) {
-    defer->partial = (const float*)workspace; defer->numel = welems; defer->ksplit = w.slices; defer->nkg = nkg;
-    defer->dw = dw; defer->accumulate = accumulate; defer->ntaps = 1;
-    defer->db_partial = (const float*)p.db_partial; defer->nb = db ? g->cout : 0; defer->db = db;
-    *rc = PCUDA_OK;
-    return 1;
-  }
-  *rc = launch_wgrad_reduce_taps((const float*)workspace, welems, w.slices, dw, accumulate, 1, (const float*)p.db_partial,
-                                 db ? g->cout : 0, db, s);
-  return 1;
+  return wgrad_finish(c, sl);
 }

@@ -334,21 +334,27 @@ struct W3Plan {
   int rb, kh, n_co_tiles, n_chunks, tiles_x, tiles_y, ksplit;
 };
 
-bool w3_eligible(const pcuda_conv_geom* g, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc) {
-  static int off = -1;
-  if (off < 0) { const char* e = getenv("PCUDA_NO_WGRAD3"); off = (e && atoi(e)) ? 1 : 0; }
+// the geometry's share of the eligibility: all that the workspace query, which sees no tensors, can know.  Deliberately
+// LOOSER than w3_eligible (neither PCUDA_NO_WGRAD3 nor PCUDA_W3_MINCOUT, cin instead of the two sources): the size only has
+// to cover every layer the route may take.
+bool w3_geom(const pcuda_conv_geom* g) {
+  return g->k == 3 && g->stride == 1 && g->dil == 1 && g->pad == 1 && !g->in_up && (g->out_w % W3_TW) == 0 &&
+         (g->out_h % W3_TH) == 0 && (g->cout & 63) == 0 && (g->cin & 31) == 0;
+}
+
+bool w3_eligible(const WgradCall& c) {
+  const pcuda_conv_geom* g = c.g;
+  const pcuda_src* x = c.x;
+  static const bool off = env_knob("PCUDA_NO_WGRAD3", 0) != 0;
   if (off) return false;
-  if (g->k != 3 || g->stride != 1 || g->dil != 1 || g->pad != 1 || g->in_up) return false;
-  static int mincout = -1;
-  if (mincout < 0) { const char* e = getenv("PCUDA_W3_MINCOUT"); mincout = e ? atoi(e) : 128; }
-  if ((g->out_w % W3_TW) || (g->out_h % W3_TH) || (g->cout & 63) || g->cout < mincout) return false;
+  static const int mincout = env_knob("PCUDA_W3_MINCOUT", 128);
+  if (!w3_geom(g) || g->cout < mincout) return false;
   const int c1 = x->c1 < g->cin ? x->c1 : g->cin;
   if ((c1 & 31) || ((g->cin - c1) & 31)) return false;
   if (!fast_src_ok(x, g->cin)) return false;
-  if (((uintptr_t)x->p1 & 15) || (x->sc1 & 3) || (x->sn1 & 3)) return false;
-  if (c1 < g->cin && (((uintptr_t)x->p2 & 15) || (x->sc2 & 3) || (x->sn2 & 3))) return false;
-  if (((uintptr_t)dy & 15) || (dy_sc & 3) || (dy_sn & 3)) return false;
-  if (((long long)g->cout * dy_sc + (long long)g->out_h * g->out_w) * 4 >= (1ll << 31)) return false;
+  if (!aligned16(x->p1, x->sn1, x->sc1) || (c1 < g->cin && !aligned16(x->p2, x->sn2, x->sc2))) return false;
+  if (!aligned16(c.dy, c.dy_sn, c.dy_sc)) return false;
+  if (((long long)g->cout * c.dy_sc + (long long)g->out_h * g->out_w) * 4 >= (1ll << 31)) return false;
   if ((long long)g->in_h * g->in_w * 4 >= (1ll << 30)) return false;
   return true;
 }
@@ -368,8 +374,7 @@ W3Plan w3_plan(const pcuda_conv_geom* g) {
   w.tiles_y = g->out_h / W3_TH;
   const long long ntiles = (long long)g->n * w.tiles_x * w.tiles_y;
   const int base = w.n_co_tiles * w.n_chunks;
-  static int tgt = -1;
-  if (tgt < 0) { const char* e = getenv("PCUDA_WG3_BLOCKS"); tgt = e ? atoi(e) : 1024; }
+  static const int tgt = env_knob("PCUDA_WG3_BLOCKS", 1024);
   long long ks = tgt / base;
   if (ks < 1) ks = 1;
   if (ks > ntiles) ks = ntiles;
@@ -382,73 +387,51 @@ W3Plan w3_plan(const pcuda_conv_geom* g) {
 
 }  // namespace
 
-size_t wgrad3_workspace(const pcuda_conv_geom* g) {
-  if (g->k != 3 || g->stride != 1 || g->dil != 1 || g->pad != 1 || g->in_up || (g->out_w % W3_TW) || (g->out_h % W3_TH) ||
-      (g->cout & 63) || (g->cin & 31))
-    return 0;
+int wgrad3_slices(const pcuda_conv_geom* g) {
+  if (!w3_geom(g)) return 0;
   const W3Plan w = w3_plan(g);
-  return ((size_t)w.ksplit * w.kh * g->cout * g->cin * 9 + (size_t)w.ksplit * w.kh * g->cout) * sizeof(float) + 256;
+  return w.ksplit * w.kh;
 }
 
-// returns 1 when it took the launch (*rc = status)
-int wgrad3_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc,
-               float* dw, float* db, int accumulate, void* workspace, hipStream_t s, pcuda_reduce_job* defer, int* rc) {
-  if (!w3_eligible(g, x, dy, dy_sn, dy_sc)) return 0;
-  const bool x3 = prec == PCUDA_PREC_BF16X3;
+int wgrad3_wgrad(const WgradCall& c) {
+  const pcuda_conv_geom* g = c.g;
+  if (!w3_eligible(c)) return WGRAD_NOT_TAKEN;
+  const bool x3 = c.prec == PCUDA_PREC_BF16X3;
   const W3Plan w = w3_plan(g);
+  const WgradSlabs sl = wgrad_slabs(c, w.ksplit * w.kh, 9);
   W3Params p;
   memset(&p, 0, sizeof(p));
-  p.x = *x; p.cin = g->cin; p.H = g->in_h; p.W = g->in_w;
-  p.dz = dy; p.dz_sn = dy_sn; p.dz_sc = dy_sc; p.cout = g->cout;
+  p.x = *c.x; p.cin = g->cin; p.H = g->in_h; p.W = g->in_w;
+  p.dz = c.dy; p.dz_sn = c.dy_sn; p.dz_sc = c.dy_sc; p.cout = g->cout;
   p.tiles_x = w.tiles_x; p.tiles_y = w.tiles_y; p.n = g->n;
   p.ksplit = w.ksplit; p.n_chunks = w.n_chunks;
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("PCUDA_W3DBG"); dbg = e ? atoi(e) : 0; }
-    p.dbg = dbg;
-  }
-  const int slices = w.ksplit * w.kh;
-  const long long welems = (long long)g->cout * g->cin * 9;
-  p.partial = (float*)workspace;
-  p.db_partial = db ? (float*)workspace + (size_t)slices * welems : nullptr;
+  static const int dbg = env_knob("PCUDA_W3DBG", 0);
+  p.dbg = dbg;
+  p.partial = sl.partial;
+  p.db_partial = sl.db_partial;
   const size_t lds = (size_t)(x3 ? 2 : 1) * (W3_XPLANE + 32 * w.rb * WG_ZROW);
   p.base = w.n_co_tiles * w.n_chunks;
-  {
-    static int noxcd = -1;
-    if (noxcd < 0) { const char* e = getenv("PCUDA_W3_NOXCD"); noxcd = (e && atoi(e)) ? 1 : 0; }
-    p.xcd = (!noxcd && (w.ksplit % 8) == 0) ? 1 : 0;
-  }
+  static const bool noxcd = env_knob("PCUDA_W3_NOXCD", 0) != 0;
+  p.xcd = (!noxcd && (w.ksplit % 8) == 0) ? 1 : 0;
   const dim3 grid(p.base * w.ksplit);
   {
     char tag[160];
     snprintf(tag, sizeof(tag), "wgrad3 n%d cin%d cout%d %dx%d k3 s1 d1 ksplit%d rb%d lds%zu", g->n, g->cin, g->cout, g->out_h,
              g->out_w, w.ksplit, w.rb, lds);
-    ProfScope prof(PCUDA_FAM_CONV_WGRAD, 2.0 * g->n * (double)g->out_h * g->out_w * g->cout * (double)g->cin * 9, s, tag);
+    ProfScope prof(PCUDA_FAM_CONV_WGRAD, 2.0 * g->n * (double)g->out_h * g->out_w * g->cout * (double)g->cin * 9, c.s, tag);
 #define W3_LAUNCH(X3_, RB_, KH_)                                                                                       \
   do {                                                                                                                  \
     auto kern = wgrad3_kernel<X3_, RB_, KH_>;                                                                          \
     if (lds > 48 * 1024) {   /* (the attribute is per device: set on every launch, the call is cheap) */               \
       hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_HARD); \
-      if (e != hipSuccess) { pcuda_set_error("wgrad3: cannot raise dynamic LDS: %s", hipGetErrorString(e)); *rc = PCUDA_E_LAUNCH; return 1; } \
+      if (e != hipSuccess) PCUDA_FAIL(PCUDA_E_LAUNCH, "wgrad3: cannot raise dynamic LDS: %s", hipGetErrorString(e));  \
     }                                                                                                                   \
-    hipLaunchKernelGGL(kern, grid, dim3(64 * RB_ * 2 * KH_), lds, s, p);                                                \
+    hipLaunchKernelGGL(kern, grid, dim3(64 * RB_ * 2 * KH_), lds, c.s, p);                                              \
   } while (0)
     if (x3) W3_LAUNCH(true, 2, 1);
     else W3_LAUNCH(false, 2, 1);
 #undef W3_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pcuda_set_error("wgrad3_kernel: %s", hipGetErrorString(e)); *rc = PCUDA_E_LAUNCH; return 1; }
+    PCUDA_CHECK_LAUNCH("wgrad3_kernel");
   }
-  int nkg = 1;
-  while (nkg < 16 && nkg * 2 <= slices) nkg <<= 1;
-  if (defer) {
-    defer->partial = (const float*)workspace; defer->numel = welems; defer->ksplit = slices; defer->nkg = nkg;
-    defer->dw = dw; defer->accumulate = accumulate; defer->ntaps = 9;
-    defer->db_partial = (const float*)p.db_partial; defer->nb = db ? g->cout : 0; defer->db = db;
-    *rc = PCUDA_OK;
-    return 1;
-  }
-  *rc = launch_wgrad_reduce_taps((const float*)workspace, welems, slices, dw, accumulate, 9, (const float*)p.db_partial,
-                                 db ? g->cout : 0, db, s);
-  return 1;
+  return wgrad_finish(c, sl);
 }

@@ -332,13 +332,11 @@ struct W3RPlan {
 // conversion switched off (PCUDA_W3R_DEBUG builds, PCUDA_W3RDBG) 32->32 at 256x256 stays at 0.19-0.22 ms, without the loads it
 // runs in 0.13 ms (MFMA-bound: 1060 cycles per 27-MFMA step) -- a lane per row, 32 bytes per lane and step, streams 3.8 TB/s.
 bool w3r_geom(const pcuda_conv_geom* g) {
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("PCUDA_WGRAD3R"); mode = e ? atoi(e) : 1; }
+  static const int mode = env_knob("PCUDA_WGRAD3R", 1);
   if (!mode) return false;
-  static int maxc = -1;
-  if (maxc < 0) { const char* e = getenv("PCUDA_W3R_MAXC"); maxc = e ? atoi(e) : 128; }
-  static int upmaxc = -1;     // PCUDA_W3R_UPMAXC: the up-convolutions (input read at its stored resolution) it takes by default
-  if (upmaxc < 0) { const char* e = getenv("PCUDA_W3R_UPMAXC"); upmaxc = e ? atoi(e) : 512; }
+  static const int maxc = env_knob("PCUDA_W3R_MAXC", 128);
+  // PCUDA_W3R_UPMAXC: the up-convolutions (input read at its stored resolution) it takes by default
+  static const int upmaxc = env_knob("PCUDA_W3R_UPMAXC", 512);
   const int mc = (g->in_up && upmaxc > maxc) ? upmaxc : maxc;
   const bool shape = g->k == 3 && g->stride == 1 && g->pad == 1 && g->dil == 1 && (g->in_w & 31) == 0 && g->in_h >= 4 &&
                      (!g->in_up || (g->in_h & 1) == 0) &&
@@ -365,8 +363,7 @@ W3RPlan w3r_plan(const pcuda_conv_geom* g) {
   while ((long long)g->n * w.strips * w.rsplit * tiles < 256 && g->in_h / (w.rsplit * 2) >= 32) w.rsplit *= 2;
   w.npairs = g->n * w.strips * w.rsplit;
   // one workgroup per CU (four waves with 512 registers each): ~512 workgroups = two rounds; slabs below 32 MB
-  static int tgt = -1;
-  if (tgt < 0) { const char* e = getenv("PCUDA_W3R_BLOCKS"); tgt = e ? atoi(e) : 512; }
+  static const int tgt = env_knob("PCUDA_W3R_BLOCKS", 512);
   long long want = tgt / tiles;
   const long long welems = (long long)g->cout * g->cin * 9;
   if (want * welems * 4 > (32ll << 20)) want = (32ll << 20) / (welems * 4);
@@ -379,64 +376,45 @@ W3RPlan w3r_plan(const pcuda_conv_geom* g) {
 
 }  // namespace
 
-size_t wgrad3r_workspace(const pcuda_conv_geom* g) {
-  if (!w3r_geom(g)) return 0;
-  const W3RPlan w = w3r_plan(g);
-  return ((size_t)w.slices * g->cout * g->cin * 9 + (size_t)w.slices * g->cout) * sizeof(float) + 256;
-}
+int wgrad3r_slices(const pcuda_conv_geom* g) { return w3r_geom(g) ? w3r_plan(g).slices : 0; }
 
-// returns 1 when it took the launch (*rc = status)
-int wgrad3r_try(const pcuda_conv_geom* g, int prec, const pcuda_src* x, const float* dy, long long dy_sn, long long dy_sc,
-                float* dw, float* db, int accumulate, void* workspace, hipStream_t s, pcuda_reduce_job* defer, int* rc) {
-  if (!w3r_geom(g)) return 0;
-  auto al = [](const void* q, long long sn, long long sc) { return q == nullptr || ((((uintptr_t)q) & 15) == 0 && (sn & 3) == 0 && (sc & 3) == 0); };
+int wgrad3r_wgrad(const WgradCall& c) {
+  const pcuda_conv_geom* g = c.g;
+  const pcuda_src* x = c.x;
+  if (!w3r_geom(g)) return WGRAD_NOT_TAKEN;
   const int c1 = x->c1 < g->cin ? x->c1 : g->cin;
-  if (!al(x->p1, x->sn1, x->sc1) || (c1 < g->cin && !al(x->p2, x->sn2, x->sc2)) || !al(dy, dy_sn, dy_sc)) return 0;
-  const bool x3 = prec == PCUDA_PREC_BF16X3;
+  if (!aligned16(x->p1, x->sn1, x->sc1) || (c1 < g->cin && !aligned16(x->p2, x->sn2, x->sc2)) || !aligned16(c.dy, c.dy_sn, c.dy_sc))
+    return WGRAD_NOT_TAKEN;
+  const bool x3 = c.prec == PCUDA_PREC_BF16X3;
   const W3RPlan w = w3r_plan(g);
+  const WgradSlabs sl = wgrad_slabs(c, w.slices, 9);
   W3RParams p;
   memset(&p, 0, sizeof(p));
   p.x = *x; p.x.c1 = c1;
   p.cin = g->cin; p.cout = g->cout; p.n = g->n; p.H = g->in_h; p.W = g->in_w;
-  p.dz = dy; p.dz_sn = dy_sn; p.dz_sc = dy_sc;
-  const long long welems = (long long)g->cout * g->cin * 9;
-  p.partial = (float*)workspace;
-  p.db_partial = db ? (float*)workspace + (size_t)w.slices * welems : nullptr;
+  p.dz = c.dy; p.dz_sn = c.dy_sn; p.dz_sc = c.dy_sc;
+  p.partial = sl.partial;
+  p.db_partial = sl.db_partial;
   p.n_ci_tiles = w.n_ci_tiles; p.tiles = w.n_co_tiles * w.n_ci_tiles;
   p.strips = w.strips; p.rsplit = w.rsplit; p.npairs = w.npairs; p.pairs_per_slice = w.pairs_per_slice;
   const long long nwg = (long long)p.tiles * w.slices;
   p.xcd = (nwg >= 16 && (nwg & 7) == 0) ? 1 : 0;
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("PCUDA_W3RDBG"); dbg = e ? atoi(e) : 0; }
-    p.dbg = dbg;
-  }
+  static const int dbg = env_knob("PCUDA_W3RDBG", 0);
+  p.dbg = dbg;
   {
     char tag[160];
     snprintf(tag, sizeof(tag), "wgrad3r n%d cin%d cout%d %dx%d k3 s1 d1 up%d slices%d pairs%d", g->n, g->cin, g->cout, g->in_h, g->in_w,
              g->in_up ? 1 : 0, w.slices, w.pairs_per_slice);
-    ProfScope prof(PCUDA_FAM_CONV_WGRAD, 2.0 * g->n * (double)g->in_h * g->in_w * g->cout * (double)g->cin * 9, s, tag);
+    ProfScope prof(PCUDA_FAM_CONV_WGRAD, 2.0 * g->n * (double)g->in_h * g->in_w * g->cout * (double)g->cin * 9, c.s, tag);
     const dim3 grid((unsigned)nwg);
     if (g->in_up) {
-      if (x3) hipLaunchKernelGGL((wgrad3r_kernel<true, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((wgrad3r_kernel<false, true>), grid, dim3(256), 0, s, p);
+      if (x3) hipLaunchKernelGGL((wgrad3r_kernel<true, true>), grid, dim3(256), 0, c.s, p);
+      else hipLaunchKernelGGL((wgrad3r_kernel<false, true>), grid, dim3(256), 0, c.s, p);
     } else {
-      if (x3) hipLaunchKernelGGL(wgrad3r_kernel<true>, grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL(wgrad3r_kernel<false>, grid, dim3(256), 0, s, p);
+      if (x3) hipLaunchKernelGGL(wgrad3r_kernel<true>, grid, dim3(256), 0, c.s, p);
+      else hipLaunchKernelGGL(wgrad3r_kernel<false>, grid, dim3(256), 0, c.s, p);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pcuda_set_error("wgrad3r_kernel: %s", hipGetErrorString(e)); *rc = PCUDA_E_LAUNCH; return 1; }
+    PCUDA_CHECK_LAUNCH("wgrad3r_kernel");
   }
-  int nkg = 1;
-  while (nkg < 16 && nkg * 2 <= w.slices) nkg <<= 1;
-  if (defer) {
-    defer->partial = (const float*)workspace; defer->numel = welems; defer->ksplit = w.slices; defer->nkg = nkg;
-    defer->dw = dw; defer->accumulate = accumulate; defer->ntaps = 9;
-    defer->db_partial = (const float*)p.db_partial; defer->nb = db ? g->cout : 0; defer->db = db;
-    *rc = PCUDA_OK;
-    return 1;
-  }
-  *rc = launch_wgrad_reduce_taps((const float*)workspace, welems, w.slices, dw, accumulate, 9, (const float*)p.db_partial,
-                                 db ? g->cout : 0, db, s);
-  return 1;
+  return wgrad_finish(c, sl);
 }

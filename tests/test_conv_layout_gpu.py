@@ -22,16 +22,16 @@ floats keeps every gate's residues and stays on the dense run's kernel: the fore
   fold_ok, dgrad_fold `a` (conv_igemm.hip:444,  pass: fold_pipe (ABI) dense, dx|a = off8 pad2 slice   refuse: fold_pipe (ABI) dx|a = off4 pad1 -> UNSUPPORTED
     :787; conv_ap.hip:123-125)                        ap_up (ABI) likewise                                  (wrapper: dgrad + upsample2_bwd); fold_none: no plan
   fused reduce, `a` 16 B (conv_igemm.hip:746,   pass: pipe_te, ap, rs, rs_aff, pw8 dgrad+bnred      refuse: ... a = mis -> red=separate (same kernel without
-    conv_ap.hip:128, conv_direct.hip:471)             dense, a = slice                                     the reduce, or the plain one)
+    conv_ap.hip:128, conv_direct.hip:469)             dense, a = slice                                     the reduce, or the plain one)
   ap_launch_ok (conv_ap.hip:117-131)            pass: ap, ap_cat, ap_up dense, slice                refuse: x|x2|y|dy|dx|dx2 = mis -> igemm8 / igemm_generic
   rs_try_launch `al` (conv_rs.hip:396)          pass: rs, rs_aff dense, slice                       refuse: x|y|dy|dx = mis -> igemm8
-  aligned16 (conv_direct.hip:411/434/469/511,   pass: c1, pw8, d1a, d1b dense, slice; d1* dgrad     refuse: c1 x|y (-> igemm8, statistics by pcuda_bn_stats),
-    conv_direct_d1.hip:269/305)                       dy, d1* wgrad dy (no gate: scalar reads)              c1 wgrad x|dy, pw8 *, d1* dgrad dx, d1* wgrad x = mis
-  d1 forward 8 B (conv_direct_d1.hip:582)       pass: d1a, d1b fwd dense, x = off8 pad2, y = any    refuse: d1a, d1b fwd x = off4 pad1 -> igemm8
+  aligned16 (conv_direct.hip:409/432/467/509,   pass: c1, pw8, d1a, d1b dense, slice; d1* dgrad     refuse: c1 x|y (-> igemm8, statistics by pcuda_bn_stats),
+    conv_direct_d1.hip:268/305)                       dy, d1* wgrad dy (no gate: scalar reads)              c1 wgrad x|dy, pw8 *, d1* dgrad dx, d1* wgrad x = mis
+  d1 forward 8 B (conv_direct_d1.hip:583)       pass: d1a, d1b fwd dense, x = off8 pad2, y = any    refuse: d1a, d1b fwd x = off4 pad1 -> igemm8
   wgrad3 / wgrad3r / wgrad1 16 B                pass: w3, w3_cat, w3r, w3r_up, w1, w1_cat dense     refuse: x|x2|dy = mis -> wgrad / wgrad8
-  generic wgrad aligned4 (conv_wgrad.hip:318)   pass: wg_al dense (rows of 32)                      refuse: wg_al dy = mis; wg_52, wg_s2 (rows of 52 / 17)
+  generic wgrad aligned4 (conv_wgrad.hip:271)   pass: wg_al dense (rows of 32)                      refuse: wg_al dy = mis; wg_52, wg_s2 (rows of 52 / 17)
   xq: in_w % 4 == 0 only (conv_igemm.hip:427,   on:  ig8_*, pipe_te, fold_pipe, ap* / rs* refused,   off: s2_odd33 dgrad, lrelu_odd (igemm8, rows of 17 / 19),
-    conv_wgrad.hip:359)                               wg_al, wg_52: x|dy = mis are float4 loads off        wg_s2 (rows of 33)
+    conv_wgrad.hip:283)                               wg_al, wg_52: x|dy = mis are float4 loads off        wg_s2 (rows of 33)
                                                       16-byte alignment, right on gfx950
   fast_src_ok / fast_dst_ok (split positions)   pass: ig8_cat 64 + 32, w3_cat 64 + 64               refuse: s2_odd12 dx 12 + 12 (c1 & 7); 48 + 32 / 48 + 16 (c1 & 31)
                                                                                                     once wgrad1 / conv3ap refuse a view: w1_cat x|x2|dy = mis ->

@@ -10,8 +10,8 @@ in float32 on the CPU, chains = 3 in bf16x3 mode, 1 in bf16 mode and for the dir
 activations) -- and the project's old bound on the whole tensor.
 
 INSTANTIATIONS lists what the launch switch statements can start: conv3rs 12 = STATS {0, 1, 2} x ACC x AFF (csrc/conv_rs.hip:441-444),
-conv3ap 8 (csrc/conv_ap.hip:176-183), wgrad3r {bf16, bf16x3} x {plain, UP} (csrc/conv_wgrad3r.hip:420-425), wgrad3 per precision
-(csrc/conv_wgrad3.hip:436-437), wgrad1 per precision x co_b {1, 2} x ci_b {1, 2, 3} (csrc/conv_wgrad1.hip:290-295), and the direct
+conv3ap 8 (csrc/conv_ap.hip:176-183), wgrad3r {bf16, bf16x3} x {plain, UP} (csrc/conv_wgrad3r.hip:410-415), wgrad3 per precision
+(csrc/conv_wgrad3.hip:431-432), wgrad1 per precision x co_b {1, 2} x ci_b {1, 2, 3} (csrc/conv_wgrad1.hip:284-289), and the direct
 kernels behind the seven PCUDA_DIRECT_MASK bits (+ the 1x1 data gradient with the fused reduce, + d1_fwd_kernel) per precision.
 UNREACHABLE, one entry per kernel file: STATS = 1 (the forward's sum / sum of squares) with ACC -- ``pcuda_conv2d_forward`` sets
 ``accumulate = 0`` (csrc/conv_igemm.hip:617) and is the only entry point that passes ``bn_partials`` without ``red_a``, so

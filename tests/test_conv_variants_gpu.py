@@ -10,7 +10,7 @@ alone; chains = 1 in bf16 mode, 3 in bf16x3 mode, below) -- and the project's 1e
 unrounded float64 convolution.
 
 Tables: ``pipe``, ``ig8``, ``wgrad`` with the default dispatcher, and ``wgrad_no_wgrad1`` (PCUDA_NO_WGRAD1=1): the 1x1 /
-stride-1 kernel of csrc/conv_wgrad1.hip (wgrad1_try, in front of the keyed kernels in wgrad_impl, csrc/conv_wgrad.hip:292)
+stride-1 kernel of csrc/conv_wgrad1.hip (wgrad1_wgrad, in front of the generic plan in WGRAD_ROUTES, csrc/conv_wgrad.hip:336)
 takes every 1x1 shape with whole 32-channel chunks and rows of 16k pixels, which is what keys 576-579 (mode 0, one tap, quad
 staging) need too: with cin >= 32 they run only behind that switch.  The anti-phase, row-streaming, wgrad3 and direct kernels
 pre-empt no built key at EVERY shape: the other 123 keys are reached with the default dispatcher.
