@@ -536,7 +536,7 @@ int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, i
  *                 input per channel iff the first word of Philox4x32-10(key = seed, counter = final id) < iarg[4], else its
  *                 pixels are copied.  min_size = 1 merges nothing and recolours per piece.  Integers only; this build's own
  *                 convention (parity with skimage's _enforce_label_connectivity_cython is unpinned; no max_size split, no
- *                 8-connectivity, no downscale to 128 pixels)
+ *                 8-connectivity; the downscale to 128 pixels is pcuda_stylize_scaled's)
  * h w <= 2^24 (32-bit segment sums; PCUDA_E_BADARG above).  workspace: pcuda_stylize_connect_workspace_size bytes, 16-byte
  * aligned, needed for slots > 0, each part rounded up to 16 bytes: [pcuda_stylize_workspace_size bytes, laid out as
  * pcuda_stylize's] [parents int32 b h w] [component sizes uint32 b h w] [segment sums uint32 b h w (c + 1): colour sums, then the
@@ -545,6 +545,29 @@ size_t pcuda_stylize_connect_workspace_size(int b, int h, int w, int c);
 int pcuda_stylize_connect(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
                           const int* iarg, const double* farg, const double* table, const unsigned long long* seed,
                           void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* superpixels at a working size (csrc/spx_scale.hip): pcuda_stylize_connect with an opt-in max_size on SUPERPIXELS slots, the
+ * counterpart of iaa.Superpixels' max_size = 128.  Same parameters and status codes as pcuda_stylize_connect (iarg[5] is
+ * honoured on every SUPERPIXELS slot); a SUPERPIXELS slot additionally reads iarg[6] = max_size = m (pcuda_stylize and
+ * pcuda_stylize_connect never do).  With L = max(h, w):
+ *   m <= 0 or L <= m  the slot is pcuda_stylize_connect's, bit for bit; so is every slot of another opcode
+ *   m >= 1 and L > m  (a SCALED slot) working size h' = max(1, (h m) / L), w' = max(1, (w m) / L) (integer division).  Linear
+ *                     resize R(src[Sh x Sw x c] -> Dh x Dw), per axis with source size S, destination size D and destination
+ *                     index d: a = clip((2 d + 1) S - D, 0, 2 D (S - 1)), i0 = a / (2 D), t = a - 2 D i0, i1 = min(i0 + 1, S - 1);
+ *                     num = (2 Dh - ty) ((2 Dw - tx) p00 + tx p01) + ty ((2 Dw - tx) p10 + tx p11), den = 4 Dh Dw, value =
+ *                     floor((2 num + den) / (2 den)) (64-bit integers).  small = R(slot input -> h' x w'); the grid SLIC of
+ *                     pcuda_stylize runs on small with h', w' in place of h, w everywhere and, for iarg[5] >= 1, the
+ *                     connectivity rule above on the working-size label plane (ids and counters r = y w' + x); the repaint
+ *                     over the pixels of small gives painted; out = R(painted -> h x w), except that a sample none of whose
+ *                     final segments that hold a pixel is replaced gets the slot's input, bit for bit.  Integers only; this
+ *                     build's own convention (parity with imgaug, cv2 and skimage is unpinned)
+ * h w <= 2^24 (PCUDA_E_BADARG above).  workspace: pcuda_stylize_scaled_workspace_size bytes, 16-byte aligned, needed for
+ * slots > 0, each part rounded up to 16 bytes: [pcuda_stylize_connect_workspace_size bytes, laid out as
+ * pcuda_stylize_connect's] [working images uint8 b h w c] [painted working images uint8 b h w c] [one int32 per sample: a
+ * segment was replaced]; 0 for non-positive dims. */
+size_t pcuda_stylize_scaled_workspace_size(int b, int h, int w, int c);
+int pcuda_stylize_scaled(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode,
+                         const int* iarg, const double* farg, const double* table, const unsigned long long* seed,
+                         void* workspace, size_t workspace_bytes, pcuda_stream_t s);
 /* device-side CropAndPad with every defined mode of numpy.pad: iaa.CropAndPad(percent=(-0.05, 0.1), pad_mode=ia.ALL,
  * pad_cval=(0, 255)) of both heavy recipes (data_generator_mscmrseg.py:28-32, 91-95; csrc/croppad.hip) on uint8 images
  * [b][h][w][c], c = 1..4, h, w >= 2, and optional int32 labels [b][h][w], as a per-sample program in device memory: opcode [b]

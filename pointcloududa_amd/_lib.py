@@ -134,6 +134,8 @@ _PROTOS = {
     "pcuda_stylize": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_stylize_connect_workspace_size": (sz, [i32, i32, i32, i32]),
     "pcuda_stylize_connect": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "pcuda_stylize_scaled_workspace_size": (sz, [i32, i32, i32, i32]),
+    "pcuda_stylize_scaled": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_crop_pad_workspace_size": (sz, [i32, i32, i32, i32]),
     "pcuda_crop_pad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "pcuda_match_hist_workspace_size": (sz, [i32, i32, i32, i32, i32]),

@@ -47,4 +47,16 @@ __device__ __forceinline__ uint32_t philox_word0(uint32_t k0, uint32_t k1, uint3
   return c0;
 }
 
+// Working size of a SUPERPIXELS slot whose max_size (iarg[6]) is m, for h x w images: the slot is SCALED iff
+// m >= 1 and L = max(h, w) > m, and then runs on h2 x w2 = max(1, (h m) / L) x max(1, (w m) / L) (the longer side is exactly
+// m); else h2 x w2 = h x w and the return value is false
+__device__ __forceinline__ bool spx_working_size(int h, int w, int m, int& h2, int& w2) {
+  const int L = h > w ? h : w;
+  h2 = h; w2 = w;
+  if (m < 1 || L <= m) return false;
+  const int hs = (int)(((long long)h * m) / L), ws = (int)(((long long)w * m) / L);
+  h2 = hs < 1 ? 1 : hs; w2 = ws < 1 ? 1 : ws;
+  return true;
+}
+
 }  // namespace imgdev

@@ -13,7 +13,9 @@
 //   3. a final segment (all pixels of one final id, 4-connected by induction) takes the colour rdiv(sum_ch, n) over its pixels of
 //      the slot's input iff the first word of Philox4x32-10(key = seed, counter = final id) < iarg[4]; else its pixels are copied
 //   iarg[5] == 0: no pass, the slot is f9's (counter = label k), bit for bit.  min_size == 1 merges nothing and recolours per piece.
-// Not built: skimage's max_size_factor split, 8-connectivity, imgaug's downscale to 128 pixels.
+// Not built: skimage's max_size_factor split, 8-connectivity.  imgaug's downscale to 128 pixels is built in spx_scale.hip
+// (f9c, opt-in: iarg[6] = max_size, read by pcuda_stylize_scaled alone, which runs this pass on the working-size label plane
+// of the scaled samples -- per-sample h' x w', ids r = y w' + x -- through spx_connect_scaled; ConnArgs.scale).
 //
 // pcuda_stylize_connect runs pcuda_stylize's launches unchanged (stylize_run: the superpixel kernel writes its label plane to
 // the workspace and the unconnected image to the slot's output) and, behind every slot, the eight launches below over grids of
@@ -61,14 +63,25 @@ struct ConnArgs {
   unsigned* size;            // [b][h w]
   unsigned* sums;            // [b][h w][c + 1]: colour sums, then the pixel count
   int h, w, c, slots, slot;
+  // f9c, set by pcuda_stylize_scaled alone (0 from pcuda_stylize_connect, which never reads iarg[6]): 1 = the kernels stand
+  // aside for the samples whose slot is scaled, 2 = they run those samples alone, on their working size (rows of w' pixels;
+  // a sample's planes stay h w apart), and the write kernel leaves `flag`
+  int scale;
+  int* flag;                 // [b] (scale == 2): 1 iff a final segment is replaced
 };
 
-// min_size of sample n's slot, 0 when it is not a connected SUPERPIXELS slot (blockIdx-uniform: scalar loads)
-__device__ __forceinline__ int conn_min_size(const ConnArgs& a, int n) {
+// min_size of sample n's slot, 0 when it is not a connected SUPERPIXELS slot or belongs to the other launch of a scaled
+// run (blockIdx-uniform: scalar loads); h x w = the size the sample's planes are walked at
+__device__ __forceinline__ int conn_min_size(const ConnArgs& a, int n, int& h, int& w) {
+  h = a.h; w = a.w;
   const int at = n * a.slots + a.slot;
   if (a.opcode[at] != OP_SUPERPIXELS) return 0;
   const int m = a.iarg[at * kIArgs + 5];
-  return m <= 0 ? 0 : min(m, a.h * a.w);
+  if (a.scale != 0) {
+    const bool scaled = imgdev::spx_working_size(a.h, a.w, a.iarg[at * kIArgs + 6], h, w);
+    if (scaled != (a.scale == 2)) return 0;
+  }
+  return m <= 0 ? 0 : min(m, h * w);
 }
 
 using imgdev::philox_word0;
@@ -99,11 +112,13 @@ __device__ __forceinline__ void conn_unite(int* par, int a, int b) {
 
 __global__ __launch_bounds__(256) void spx_connect_init_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  if (conn_min_size(a, n) == 0) return;
-  const int hw = a.h * a.w, c1 = a.c + 1;
+  int h, w;
+  if (conn_min_size(a, n, h, w) == 0) return;
+  const int hw = h * w, c1 = a.c + 1;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= hw) return;
-  const long long at = (long long)n * hw + i;
+  if (a.scale == 2 && i == 0) a.flag[n] = 0;      // (the superpixel kernel left its own answer: the write kernel's replaces it)
+  const long long at = (long long)n * a.h * a.w + i;
   a.par[at] = i;
   a.size[at] = 0;
   unsigned* q = a.sums + at * c1;
@@ -114,19 +129,21 @@ __global__ __launch_bounds__(256) void spx_connect_init_kernel(const ConnArgs a)
 
 __global__ __launch_bounds__(256) void spx_connect_merge_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  if (conn_min_size(a, n) == 0) return;
-  const int w = a.w, h = a.h, hw = h * w;
+  int h, w;
+  if (conn_min_size(a, n, h, w) == 0) return;
+  const int hw = h * w;
+  const long long plane = (long long)a.h * a.w;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= hw) return;
   const int y = i / w, x = i - y * w;
   const bool right = x + 1 < w, down = y + 1 < h;
-  const uint8_t* lab = a.labels + (long long)n * hw;
+  const uint8_t* lab = a.labels + n * plane;
   const uint8_t* p0 = lab + i;
   const uint8_t* p1 = lab + (right ? i + 1 : i);
   const uint8_t* p2 = lab + (down ? i + w : i);
   const int v0 = *p0, v1 = *p1, v2 = *p2;
   PCUDA_KEEP(p0); PCUDA_KEEP(p1); PCUDA_KEEP(p2);
-  int* par = a.par + (long long)n * hw;
+  int* par = a.par + n * plane;
   if (right && v1 == v0) conn_unite(par, i, i + 1);
   if (down && v2 == v0) conn_unite(par, i, i + w);
 }
@@ -134,11 +151,12 @@ __global__ __launch_bounds__(256) void spx_connect_merge_kernel(const ConnArgs a
 // par[i] = the root of i's tree; a concurrent lane's write replaces a parent by one further up the same tree
 __global__ __launch_bounds__(256) void spx_connect_compress_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  if (conn_min_size(a, n) == 0) return;
-  const int hw = a.h * a.w;
+  int h, w;
+  if (conn_min_size(a, n, h, w) == 0) return;
+  const int hw = h * w;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= hw) return;
-  int* par = a.par + (long long)n * hw;
+  int* par = a.par + (long long)n * a.h * a.w;
   int r = conn_parent(par, i);
   if (r == i) return;
   for (;;) {
@@ -152,13 +170,15 @@ __global__ __launch_bounds__(256) void spx_connect_compress_kernel(const ConnArg
 // size[root] += pixels; runs of one root along memory share one atomic
 __global__ __launch_bounds__(256) void spx_connect_size_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  if (conn_min_size(a, n) == 0) return;
-  const int hw = a.h * a.w;
+  int h, w;
+  if (conn_min_size(a, n, h, w) == 0) return;
+  const int hw = h * w;
+  const long long plane = (long long)a.h * a.w;
   const int i0 = (blockIdx.x * 256 + threadIdx.x) * kRun;
   if (i0 >= hw) return;
   const int i1 = min(i0 + kRun, hw);
-  const int* par = a.par + (long long)n * hw;
-  unsigned* size = a.size + (long long)n * hw;
+  const int* par = a.par + n * plane;
+  unsigned* size = a.size + n * plane;
   int cur = -1;
   unsigned cnt = 0;
   for (int i = i0; i < i1; ++i) {
@@ -178,14 +198,16 @@ __global__ __launch_bounds__(256) void spx_connect_size_kernel(const ConnArgs a)
 // a small root (size < min_size, not pixel 0) hangs itself under its left or upper neighbour's parent
 __global__ __launch_bounds__(256) void spx_connect_link_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  const int min_size = conn_min_size(a, n);
+  int h, w;
+  const int min_size = conn_min_size(a, n, h, w);
   if (min_size == 0) return;
-  const int w = a.w, hw = a.h * w;
+  const int hw = h * w;
+  const long long plane = (long long)a.h * a.w;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= hw || i == 0) return;
-  int* par = a.par + (long long)n * hw;
+  int* par = a.par + n * plane;
   if (conn_parent(par, i) != i) return;
-  const unsigned* ps = a.size + (long long)n * hw + i;
+  const unsigned* ps = a.size + n * plane + i;
   const unsigned sz = *ps;
   PCUDA_KEEP(ps);
   if (sz >= (unsigned)min_size) return;
@@ -200,14 +222,16 @@ __global__ __launch_bounds__(256) void spx_connect_link_kernel(const ConnArgs a)
 // shuffles (stylize.hip's segmented sum) and only the stretch's first lane issues the atomics
 __global__ __launch_bounds__(256) void spx_connect_sum_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  if (conn_min_size(a, n) == 0) return;
-  const int hw = a.h * a.w, c = a.c, c1 = c + 1;
+  int h, w;
+  if (conn_min_size(a, n, h, w) == 0) return;
+  const int hw = h * w, c = a.c, c1 = c + 1;
+  const long long plane = (long long)a.h * a.w;
   const int lane = threadIdx.x & 63;
   const int i0 = (blockIdx.x * 256 + threadIdx.x) * kRun;      // (a lane past the plane walks nothing and keeps cur = -1)
   const int i1 = min(i0 + kRun, hw);
-  const int* par = a.par + (long long)n * hw;
-  const uint8_t* src = a.in + (long long)n * hw * c;
-  unsigned* sums = a.sums + (long long)n * hw * c1;
+  const int* par = a.par + n * plane;
+  const uint8_t* src = a.in + n * plane * c;
+  unsigned* sums = a.sums + n * plane * c1;
   int cur = -1;
   int acc[kMaxC] = {0, 0, 0, 0}, cnt = 0;
   for (int i = i0; i < i1; ++i) {
@@ -263,8 +287,10 @@ __global__ __launch_bounds__(256) void spx_connect_sum_kernel(const ConnArgs a) 
 
 __global__ __launch_bounds__(256) void spx_connect_write_kernel(const ConnArgs a) {
   const int n = blockIdx.y;
-  if (conn_min_size(a, n) == 0) return;
-  const int hw = a.h * a.w, c = a.c, c1 = c + 1;
+  int h, w;
+  if (conn_min_size(a, n, h, w) == 0) return;
+  const int hw = h * w, c = a.c, c1 = c + 1;
+  const long long plane = (long long)a.h * a.w;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= hw) return;
   const int at = n * a.slots + a.slot;
@@ -272,10 +298,10 @@ __global__ __launch_bounds__(256) void spx_connect_write_kernel(const ConnArgs a
   const uint32_t* sd = a.seed + 2 * at;
   asm volatile("" : "+v"(sd));      // a vector address of its own, kept alive below (as stylize.hip)
   const uint32_t k0 = sd[0], k1 = sd[1];
-  const int* pi = a.par + (long long)n * hw + i;
+  const int* pi = a.par + n * plane + i;
   const int id = min(max(*pi, 0), hw - 1);
-  const unsigned* q = a.sums + ((long long)n * hw + id) * c1;
-  const uint8_t* p = a.in + ((long long)n * hw + i) * c;
+  const unsigned* q = a.sums + (n * plane + id) * c1;
+  const uint8_t* p = a.in + (n * plane + i) * c;
   unsigned sum[kMaxC + 1];
   uint8_t v[kMaxC];
 #pragma unroll
@@ -288,7 +314,8 @@ __global__ __launch_bounds__(256) void spx_connect_write_kernel(const ConnArgs a
 #pragma unroll
   for (int ch = 0; ch <= kMaxC; ++ch)
     if (ch == c) cnt = max(sum[ch], 1u);
-  uint8_t* dst = a.out + ((long long)n * hw + i) * c;
+  if (a.scale == 2 && rep) a.flag[n] = 1;      // (zeroed by the init kernel; every writer stores 1)
+  uint8_t* dst = a.out + (n * plane + i) * c;
 #pragma unroll
   for (int ch = 0; ch < kMaxC; ++ch)
     if (ch < c) {
@@ -329,7 +356,29 @@ int connect_slot(void* ctx, int slot, const uint8_t* slot_in, uint8_t* slot_out,
   return PCUDA_OK;
 }
 
+// par, size and sums behind `base` (the connect workspace less pcuda_stylize's own part)
+void conn_layout(ConnArgs& a, void* base, int b, int h, int w, int c) {
+  const size_t px = (size_t)b * h * w;
+  uint8_t* p = (uint8_t*)base;
+  a.par = (int*)p;
+  a.size = (unsigned*)(p + round16(4 * px));
+  a.sums = (unsigned*)(p + 2 * round16(4 * px));
+}
+
 }  // namespace
+
+int spx_connect_scaled(const uint8_t* slot_in, uint8_t* slot_out, const uint8_t* labels, void* conn_workspace, int* flag, int scale,
+                       int b, int h, int w, int c, int slots, int slot, const int* opcode, const int* iarg,
+                       const unsigned long long* seed, pcuda_stream_t s) {
+  ConnCtx k;
+  memset(&k, 0, sizeof(k));
+  k.b = b; k.s = (hipStream_t)s;
+  k.a.opcode = opcode; k.a.iarg = iarg; k.a.seed = reinterpret_cast<const uint32_t*>(seed);
+  k.a.h = h; k.a.w = w; k.a.c = c; k.a.slots = slots;
+  k.a.scale = scale; k.a.flag = flag;
+  conn_layout(k.a, conn_workspace, b, h, w, c);
+  return connect_slot(&k, slot, slot_in, slot_out, labels);
+}
 
 extern "C" size_t pcuda_stylize_connect_workspace_size(int b, int h, int w, int c) {
   if (b <= 0 || h <= 0 || w <= 0 || c <= 0) return 0;
@@ -347,13 +396,8 @@ extern "C" int pcuda_stylize_connect(const uint8_t* in, uint8_t* out, int b, int
   k.b = b; k.s = (hipStream_t)s;
   k.a.opcode = opcode; k.a.iarg = iarg; k.a.seed = reinterpret_cast<const uint32_t*>(seed);
   k.a.h = h; k.a.w = w; k.a.c = c; k.a.slots = slots;
-  if (workspace && b > 0 && h > 0 && w > 0 && c > 0) {
-    const size_t px = (size_t)b * h * w;
-    uint8_t* p = (uint8_t*)workspace + pcuda_stylize_workspace_size(b, h, w, c);
-    k.a.par = (int*)p;
-    k.a.size = (unsigned*)(p + round16(4 * px));
-    k.a.sums = (unsigned*)(p + 2 * round16(4 * px));
-  }
+  if (workspace && b > 0 && h > 0 && w > 0 && c > 0)
+    conn_layout(k.a, (uint8_t*)workspace + pcuda_stylize_workspace_size(b, h, w, c), b, h, w, c);
   return stylize_run(in, out, b, h, w, c, slots, opcode, iarg, farg, table, seed, workspace, workspace_bytes,
-                     pcuda_stylize_connect_workspace_size(b, h, w, c), s, connect_slot, &k);
+                     pcuda_stylize_connect_workspace_size(b, h, w, c), s, connect_slot, &k, 0);
 }

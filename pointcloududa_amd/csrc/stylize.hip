@@ -28,7 +28,9 @@
 //     rdiv(sum, n) for colour, y and x; a centre with n = 0 stays.  After `iters` updates and one last assignment segment k
 //     takes its mean colour rdiv(sum_ch, n) iff the first word of Philox4x32-10(key = seed, counter = (k, 0, 0, 0)) is below
 //     the threshold, else its pixels are copied.  No connectivity pass (spx_connect.hip adds one behind this kernel for slots
-//     that ask for it, through pcuda_stylize_connect; pcuda_stylize never reads iarg[5]), no 128-pixel downscale.
+//     that ask for it, through pcuda_stylize_connect; pcuda_stylize never reads iarg[5]).  imgaug's downscale to 128 pixels
+//     is built in spx_scale.hip (f9c, opt-in: iarg[6] = max_size, read by pcuda_stylize_scaled alone, which launches this
+//     kernel a second time for the scaled samples with their working size h' x w' in place of H x W; StyleArgs.scale).
 //
 // One slot = three launches, and each workgroup reads its sample's opcode with scalar loads and leaves at once when the
 // slot belongs to another kernel (the branch on the opcode is wave-uniform):
@@ -72,6 +74,11 @@ struct StyleArgs {
   int slot;                  // the slot this launch runs; < 0: copy
   int vec_in, vec_out;       // 16-byte loads / stores are aligned
   int word_in, word_out;     // 4-byte loads / stores of a group of four pixels are aligned (C = 3)
+  // f9c, set by pcuda_stylize_scaled alone (0 from pcuda_stylize and pcuda_stylize_connect, which never read iarg[6]):
+  // 1 = the superpixel kernel stands aside for the samples whose slot is scaled, 2 = it runs those samples alone, on
+  // their working size (rows of w' pixels; a sample's planes stay h w apart) and leaves `flag`
+  int scale;
+  int* flag;                 // [b] (scale == 2): 1 iff a segment that holds a pixel is replaced
 };
 
 using imgdev::clampi;
@@ -302,8 +309,14 @@ __global__ __launch_bounds__(kSpxThreads) void stylize_superpixels_kernel(const 
   const int at = n * a.slots + a.slot;
   if (a.opcode[at] != OP_SUPERPIXELS) return;
   const int tid = threadIdx.x, lane = tid & 63;
-  const int c = a.c, w = a.w, h = a.h, hw = h * w;
   const int* ia = a.iarg + at * kIArgs;
+  int h = a.h, w = a.w;
+  if (a.scale != 0) {      // (a kernel argument and scalar loads: workgroup-uniform)
+    const bool scaled = imgdev::spx_working_size(a.h, a.w, ia[6], h, w);
+    if (scaled != (a.scale == 2)) return;
+  }
+  const int c = a.c, hw = h * w;
+  const long long plane = (long long)a.h * a.w;      // (a sample's stride, whatever size it works on)
   const int gy = clampi(ia[0], 1, min(h, kMaxSeg));
   const int gx = clampi(ia[1], 1, min(w, kMaxSeg / gy));
   const int iters = clampi(ia[2], 0, 10);
@@ -312,9 +325,9 @@ __global__ __launch_bounds__(kSpxThreads) void stylize_superpixels_kernel(const 
   PCUDA_KEEP(ia);
   const int K = gy * gx;
   const long long S2 = max(1, hw / K);
-  const uint8_t* src = a.in + (long long)n * hw * c;
-  uint8_t* dst = a.out + (long long)n * hw * c;
-  uint8_t* lab_plane = a.labels + (long long)n * hw;
+  const uint8_t* src = a.in + n * plane * c;
+  uint8_t* dst = a.out + n * plane * c;
+  uint8_t* lab_plane = a.labels + n * plane;
 
   if (tid < K) {
     const int j = tid / gx, i = tid - j * gx;
@@ -405,6 +418,7 @@ __global__ __launch_bounds__(kSpxThreads) void stylize_superpixels_kernel(const 
         const uint32_t k0 = sd[0], k1 = sd[1];
         s_rep[tid] = philox_word0(k0, k1, (uint32_t)tid) < thr ? 1 : 0;
         PCUDA_KEEP(sd);
+        if (a.scale == 2 && s_rep[tid] != 0 && cnt > 0) a.flag[n] = 1;      // (zeroed by the downscale; every writer stores 1)
       }
     }
     __syncthreads();      // (the next pass zeroes a centre's sums in the lane that read them)
@@ -436,7 +450,7 @@ extern "C" size_t pcuda_stylize_workspace_size(int b, int h, int w, int c) {
 
 int stylize_run(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int slots, const int* opcode, const int* iarg,
                 const double* farg, const double* table, const unsigned long long* seed, void* workspace, size_t workspace_bytes,
-                size_t workspace_need, pcuda_stream_t s, StyleSlotHook hook, void* ctx) {
+                size_t workspace_need, pcuda_stream_t s, StyleSlotHook hook, void* ctx, int scale) {
   if (!in || !out) PCUDA_FAIL(PCUDA_E_BADARG, "stylize: null pointer");
   if (in == out) PCUDA_FAIL(PCUDA_E_BADARG, "stylize: in == out (the input is never written)");
   if (b <= 0 || b > 65535 || h <= 0 || w <= 0 || h > 32768 || w > 32768 || c <= 0 || c > kMaxC ||
@@ -452,6 +466,7 @@ int stylize_run(const uint8_t* in, uint8_t* out, int b, int h, int w, int c, int
   a.opcode = opcode; a.iarg = iarg; a.farg = farg; a.table = table; a.seed = reinterpret_cast<const uint32_t*>(seed);
   a.h = h; a.w = w; a.c = c; a.slots = slots;
   a.labels = (uint8_t*)workspace;
+  a.scale = scale;
   uint8_t* spare = slots > 0 ? (uint8_t*)workspace + round16((size_t)b * h * w) : nullptr;
   const long long per_sample = (long long)h * w * c, hw = (long long)h * w;
   const long long lanes = c == 3 ? (cdiv(per_sample, 16) > cdiv(hw, 4) ? cdiv(per_sample, 16) : cdiv(hw, 4)) : cdiv(per_sample, 16);
@@ -488,5 +503,19 @@ extern "C" int pcuda_stylize(const uint8_t* in, uint8_t* out, int b, int h, int 
                              const int* iarg, const double* farg, const double* table, const unsigned long long* seed,
                              void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
   return stylize_run(in, out, b, h, w, c, slots, opcode, iarg, farg, table, seed, workspace, workspace_bytes, 0, s, nullptr,
-                     nullptr);
+                     nullptr, 0);
+}
+
+int stylize_superpixels_scaled(const uint8_t* small, uint8_t* painted, uint8_t* labels, int* flag, int b, int h, int w, int c,
+                               int slots, int slot, const int* opcode, const int* iarg, const unsigned long long* seed,
+                               pcuda_stream_t s) {
+  StyleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = small; a.out = painted; a.labels = labels; a.flag = flag;
+  a.opcode = opcode; a.iarg = iarg; a.seed = reinterpret_cast<const uint32_t*>(seed);
+  a.h = h; a.w = w; a.c = c; a.slots = slots; a.slot = slot;
+  a.scale = 2;
+  hipLaunchKernelGGL(stylize_superpixels_kernel, dim3(b), dim3(kSpxThreads), 0, (hipStream_t)s, a);
+  PCUDA_CHECK_LAUNCH("stylize_superpixels_kernel");
+  return PCUDA_OK;
 }

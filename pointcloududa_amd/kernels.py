@@ -1037,23 +1037,34 @@ def geometric(images_u8, labels, opcode, iarg, farg, seed, out=None, labels_out=
     return out, labels_out
 
 
+def _stylize(name, images_u8, opcode, iarg, farg, table, seed, out):
+    images_u8, (b, h, w, c) = _images("stylize", images_u8)
+    slots, arrays = _program("stylize", b, opcode, seed, iarg=(iarg, torch.int32, 12), farg=(farg, torch.float64, 16),
+                             table=(table, torch.float64, 768))
+    out = _out("stylize", out, images_u8)
+    size_fn, run_fn = getattr(L.lib(), "pcuda_%s_workspace_size" % name), getattr(L.lib(), "pcuda_" + name)
+    nbytes = size_fn(b, h, w, c) if slots > 0 else 0
+    ws = _workspace(nbytes, images_u8.device)
+    check(run_fn(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, *(t.data_ptr() for t in arrays), _ptr(ws), nbytes,
+                 _stream()), name)
+    return out
+
+
 def stylize(images_u8, opcode, iarg, farg, table, seed, out=None, connect=False):
     """A per-sample stylize program over uint8 ``[B,H,W,C]`` images (``pcuda_stylize``): ``opcode`` int32 ``[B,S]``, ``iarg`` int32
     ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed`` int64 ``[B,S]`` (the bits of the 64-bit
     Philox key), all on the device, ``S`` = 0..8 -> a new uint8 tensor (the input is never written).  ``connect=True`` goes
     through ``pcuda_stylize_connect`` (and its larger workspace): SUPERPIXELS slots with ``iarg[5] > 0`` get the connectivity
-    pass; without it ``iarg[5]`` is never read."""
-    images_u8, (b, h, w, c) = _images("stylize", images_u8)
-    slots, arrays = _program("stylize", b, opcode, seed, iarg=(iarg, torch.int32, 12), farg=(farg, torch.float64, 16),
-                             table=(table, torch.float64, 768))
-    out = _out("stylize", out, images_u8)
-    size_fn, run_fn = (L.lib().pcuda_stylize_connect_workspace_size, L.lib().pcuda_stylize_connect) if connect else \
-        (L.lib().pcuda_stylize_workspace_size, L.lib().pcuda_stylize)
-    nbytes = size_fn(b, h, w, c) if slots > 0 else 0
-    ws = _workspace(nbytes, images_u8.device)
-    check(run_fn(images_u8.data_ptr(), out.data_ptr(), b, h, w, c, slots, *(t.data_ptr() for t in arrays), _ptr(ws), nbytes,
-                 _stream()), "stylize_connect" if connect else "stylize")
-    return out
+    pass; without it ``iarg[5]`` is never read.  Neither reads ``iarg[6]`` (``stylize_scaled`` does)."""
+    return _stylize("stylize_connect" if connect else "stylize", images_u8, opcode, iarg, farg, table, seed, out)
+
+
+def stylize_scaled(images_u8, opcode, iarg, farg, table, seed, out=None):
+    """``stylize`` through ``pcuda_stylize_scaled`` (f9c; a larger workspace again), which serves connected and unconnected slots
+    alike: ``iarg[5]`` is honoured as with ``connect=True``, and SUPERPIXELS slots whose ``iarg[6]`` = max_size is at least 1 and
+    below ``max(H, W)`` run at their working size.  With ``iarg[6] = 0`` everywhere it is ``stylize(.., connect=True)`` bit for
+    bit."""
+    return _stylize("stylize_scaled", images_u8, opcode, iarg, farg, table, seed, out)
 
 
 def crop_pad(images_u8, labels, opcode, iarg, out=None, labels_out=None):

@@ -31,7 +31,8 @@ images and the masks in front of the f6 launch.  ``Superpixels``, ``SimplexNoise
 ``"heavy_device"`` and ``"mscmrseg_aug2_device"`` keep drawing what they drew without the three.  ``CropAndPad`` with all ten
 modes of ``numpy.pad`` (``pad_mode=ia.ALL``) lives in ``utils/croppad.py`` (f14) and is re-exported here (``CropPadProgram``,
 ``crop_pad_aug``, ``MODE_NAMES``): the presets ``"heavy_refpad_device"`` and ``"mscmrseg_aug2_refpad_device"`` are the two full
-recipes with it.  Histogram matching against a
+recipes with it; ``"heavy_connected_device"`` / ``"mscmrseg_aug2_connected_device"`` add connected superpixels (f9b) and
+``"heavy_scaled_device"`` / ``"mscmrseg_aug2_scaled_device"`` imgaug's ``max_size = 128`` working size on top (f9c).  Histogram matching against a
 fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
 ``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
 in front of everything else.  A reference per sample, drawn from a ``HistReferenceBank`` that stays on the device (f10b):
@@ -56,11 +57,11 @@ from .photometric import (PHOTOMETRIC_PRESET, PhotoProgram, emboss_weights, gaus
                           sample_program, sharpen_weights, upload_program)
 from .geometric import GeoProgram, geometric_aug, upload_geo_program  # noqa: F401
 from .stylize import (StyleProgram, directed_edge_weights, edge_detect_weights, simplex_grid, stylize_aug, superpixel_grid,  # noqa: F401
-                      superpixel_min_size, upload_style_program)
+                      superpixel_min_size, superpixel_working_size, upload_style_program)
 from .histmatch import HistReference, HistReferenceBank, match_histograms, reference_tables  # noqa: F401
 from .croppad import MODE_NAMES, CropPadProgram, crop_pad_aug, upload_crop_pad_program  # noqa: F401
-from .heavy import (AUG2_CONNECTED_PRESET, AUG2_DEVICE_PRESET, AUG2_FULL_PRESET, AUG2_REFPAD_PRESET, HEAVY_CONNECTED_PRESET,  # noqa: F401
-                    HEAVY_DEVICE_PRESET, HEAVY_FULL_PRESET, HEAVY_REFPAD_PRESET, HeavyPlan, _check_interp, _check_preset, heavy_aug,
+from .heavy import (AUG2_CONNECTED_PRESET, AUG2_DEVICE_PRESET, AUG2_FULL_PRESET, AUG2_REFPAD_PRESET, AUG2_SCALED_PRESET,  # noqa: F401
+                    HEAVY_CONNECTED_PRESET, HEAVY_DEVICE_PRESET, HEAVY_FULL_PRESET, HEAVY_REFPAD_PRESET, HEAVY_SCALED_PRESET, HeavyPlan, _check_interp, _check_preset, heavy_aug,
                     sample_geo_program, sample_heavy_plan, sample_style_program)
 
 
@@ -181,7 +182,7 @@ class AugmentedBatches:
     non-blocking copies.  ``last_params`` holds the parameters of the batch yielded last; with
     ``photometric_preset`` a ``PhotoProgram`` is drawn after them from the same ``rng`` (``last_program``) and applied to the
     uint8 images in front of the warp.  With ``heavy_preset`` (``"heavy_device"``, ``"mscmrseg_aug2_device"``, their ``_full_``,
-    ``_refpad_`` or ``_connected_`` twins) ``preset`` must
+    ``_refpad_``, ``_connected_`` or ``_scaled_`` twins) ``preset`` must
     be ``None``: a ``HeavyPlan`` is drawn per batch (``last_plan``) and the assembler gets identity parameters;
     ``heavy_interp="cubic"`` (f8b) draws it with ``sample_heavy_plan(.., interp="cubic")`` -- order-3 elastic warps and a share of
     cubic noise upscales, one more ``rng.random(B)`` per batch --, ``"linear"`` (the default) as before.  With

@@ -29,6 +29,7 @@ HEAVY_DEVICE_PRESET, AUG2_DEVICE_PRESET = "heavy_device", "mscmrseg_aug2_device"
 HEAVY_FULL_PRESET, AUG2_FULL_PRESET = "heavy_full_device", "mscmrseg_aug2_full_device"
 HEAVY_REFPAD_PRESET, AUG2_REFPAD_PRESET = "heavy_refpad_device", "mscmrseg_aug2_refpad_device"
 HEAVY_CONNECTED_PRESET, AUG2_CONNECTED_PRESET = "heavy_connected_device", "mscmrseg_aug2_connected_device"
+HEAVY_SCALED_PRESET, AUG2_SCALED_PRESET = "heavy_scaled_device", "mscmrseg_aug2_scaled_device"
 
 _PHOTO_BLOCK = tuple(("p", e) for e in range(9))
 # the reference's list order: Superpixels, blur, sharpen, emboss, SimplexNoiseAlpha, noise, dropout, invert, add, hue, ...
@@ -57,6 +58,11 @@ _PRESETS = {
 # slot (f9b)
 _PRESETS[HEAVY_CONNECTED_PRESET] = dict(_PRESETS[HEAVY_REFPAD_PRESET], connected=True)
 _PRESETS[AUG2_CONNECTED_PRESET] = dict(_PRESETS[AUG2_REFPAD_PRESET], connected=True)
+# the two _connected_ recipes, draw for draw, with imgaug's max_size = 128 on every Superpixels slot: the grid and min_size
+# are those of the working size (f9c).  A table of its own: tests/golden/aug_draw_digests.json records the draws of every
+# preset of _PRESETS, while these two are pinned by their relation to their _connected_ twins (tests/test_spx_scaled.py)
+_SCALED_PRESETS = {HEAVY_SCALED_PRESET: dict(_PRESETS[HEAVY_CONNECTED_PRESET], scaled=True),
+                   AUG2_SCALED_PRESET: dict(_PRESETS[AUG2_CONNECTED_PRESET], scaled=True)}
 _SOMETIMES = {("g", ENTRY_ELASTIC), ("g", ENTRY_PIECEWISE), ("g", ENTRY_PERSPECTIVE), ("s", St.ENTRY_SUPERPIXELS)}
 _OUTER_P = {ENTRY_FLIPLR: FLIP_LR_P, ENTRY_FLIPUD: FLIP_UD_P, ENTRY_CROP_AND_PAD: SOMETIMES_P, ENTRY_AFFINE: SOMETIMES_P}
 _STAGE_TYPES = {"p": PhotoProgram, "g": GeoProgram, "s": StyleProgram, "c": CropPadProgram}
@@ -65,8 +71,10 @@ _STAGE_TYPES = {"p": PhotoProgram, "g": GeoProgram, "s": StyleProgram, "c": Crop
 def _check_preset(preset):
     if preset == "heavy":
         raise NotImplementedError(HEAVY_MESSAGE)
+    if preset in _SCALED_PRESETS:
+        return _SCALED_PRESETS[preset]
     if preset not in _PRESETS:
-        raise ValueError("unknown heavy preset %r (have: %s)" % (preset, ", ".join(sorted(_PRESETS))))
+        raise ValueError("unknown heavy preset %r (have: %s)" % (preset, ", ".join(sorted(set(_PRESETS) | set(_SCALED_PRESETS)))))
     return _PRESETS[preset]
 
 
@@ -153,7 +161,9 @@ def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: i
     with direction U(0, 1); 1..3 grids of 2..16 cells per side, nearest | bilinear, min | mean | max, sigmoid with a threshold
     from N(0, 5)) and AddToHueAndSaturation (v integer in -20..20: ds = v, dh = floor(v 180 / 255 + 0.5)), each only for the
     samples whose ``SomeOf((0, 5))`` drew it.  The ``_connected_`` presets draw what their ``_refpad_`` twins draw and give every
-    Superpixels slot ``min_size = superpixel_min_size(gy, gx, h, w)``.  ``interp="cubic"``: one more ``rng.random(batch)`` after
+    Superpixels slot ``min_size = superpixel_min_size(gy, gx, h, w)``; the ``_scaled_`` presets draw the same again and give
+    every Superpixels slot ``max_size = 128``, with the grid and ``min_size`` of ``superpixel_working_size(h, w, 128)``.
+    ``interp="cubic"``: one more ``rng.random(batch)`` after
     every other draw; the SimplexNoiseAlpha slot of sample ``i`` upscales cubically where it is below ``NOISE_CUBIC_P``."""
     cubic = _check_interp(interp)
     spec = _check_preset(preset)
@@ -168,7 +178,8 @@ def sample_style_program(batch: int, preset: str, rng: np.random.Generator, h: i
         s = 0
         for k in sty:
             if on[i, k]:
-                St.encode_style(prog, i, s, entries[k][1], d, h, w, connected=bool(spec.get("connected")))
+                St.encode_style(prog, i, s, entries[k][1], d, h, w, connected=bool(spec.get("connected")),
+                                            scaled=bool(spec.get("scaled")))
                 s += 1
     if cubic:
         _cubic_upscale(prog, cubic_draw)
@@ -210,6 +221,12 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
     ``min_size = superpixel_min_size(gy, gx, h, w)`` in ``iarg[5]`` of every Superpixels slot (connected segments,
     ``csrc/spx_connect.hip``); every other array of the plan equals the ``_refpad_`` plan of the same generator state.
 
+    ``"heavy_scaled_device"`` and ``"mscmrseg_aug2_scaled_device"`` (f9c): the ``_connected_`` presets, draw for draw, with
+    ``max_size = stylize.SUPERPIXELS_MAX_SIZE`` (128, imgaug's default) in ``iarg[6]`` of every Superpixels slot
+    (``csrc/spx_scale.hip``); ``iarg[0:2]`` (the grid) and ``iarg[5]`` (``min_size``) of those slots are computed for
+    ``superpixel_working_size(h, w, 128)``, every other array of the plan equals the ``_connected_`` plan of the same
+    generator state.
+
     ``interp="cubic"`` (f8b, any preset): every elastic slot has order 3 and, after every other draw of the call, one
     ``rng.random(batch)`` decides per sample whether its SimplexNoiseAlpha slot upscales cubically (below ``NOISE_CUBIC_P``);
     every other array of the plan equals the ``"linear"`` plan of the same generator state."""
@@ -240,7 +257,8 @@ def sample_heavy_plan(batch: int, preset: str, rng: np.random.Generator, h: int,
                         if kind == "p":
                             encode_photo(prog, i, s, entry, dp, dp["seed"][i, entry])
                         elif kind == "s":
-                            St.encode_style(prog, i, s, entry, ds, h, w, connected=bool(spec.get("connected")))
+                            St.encode_style(prog, i, s, entry, ds, h, w, connected=bool(spec.get("connected")),
+                                            scaled=bool(spec.get("scaled")))
                         elif kind == "c":
                             t, r, bt, l = dg["crop"][i]
                             prog.set_crop_and_pad(i, crop_pad_pixels(t, h), crop_pad_pixels(r, w), crop_pad_pixels(bt, h),

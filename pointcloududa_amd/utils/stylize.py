@@ -50,8 +50,29 @@ id is below the threshold.  ``superpixel_min_size(gy, gx, H, W) = max(1, (H W) /
 ``min_size_factor = 0.5``; the presets ``"heavy_connected_device"`` and ``"mscmrseg_aug2_connected_device"`` are the ``_refpad_``
 presets with it on every Superpixels slot.  ``stylize_aug`` takes the connected entry point iff ``program.needs_connect()``.
 skimage is not installed next to the reference: parity with ``_enforce_label_connectivity_cython`` is unpinned, the rule is
-this build's own (``tests/golden/spx_connect.npz``, ``scripts/make_spx_connect_golden.py``); skimage's ``max_size_factor`` split,
-8-connectivity and imgaug's downscale to 128 pixels are not built.
+this build's own (``tests/golden/spx_connect.npz``, ``scripts/make_spx_connect_golden.py``); skimage's ``max_size_factor`` split
+and 8-connectivity are not built.
+
+Superpixels at a working size (f9c, ``csrc/spx_scale.hip``, opt-in): ``iarg[6]`` = ``max_size`` = m of a SUPERPIXELS slot, the
+counterpart of imgaug's ``max_size=128`` (``SUPERPIXELS_MAX_SIZE``).  The slot is *scaled* iff ``m >= 1`` and ``L = max(H, W) > m``;
+otherwise (0 is what ``_clear`` leaves) it is the slot above, with or without ``min_size``, bit for bit.  A scaled slot works
+on ``h' x w' = superpixel_working_size(H, W, m) = (max(1, (H m) // L), max(1, (W m) // L))`` (imgaug computes ``int(H * (m / L))``
+in floating point; the integer form makes the longer side exactly m).  The linear resize ``R(src[Sh x Sw x C] -> Dh x Dw)``
+is, per axis with source size S, destination size D and destination index d: ``a = clip((2 d + 1) S - D, 0, 2 D (S - 1))``
+(the coordinate ``(d + 0.5) S / D - 0.5`` times ``2 D``, clamped into the image), ``i0 = a // (2 D)``, ``t = a - 2 D i0``, ``i1 =
+min(i0 + 1, S - 1)``; ``num = (2 Dh - ty) ((2 Dw - tx) p00 + tx p01) + ty ((2 Dw - tx) p10 + tx p11)``, ``den = 4 Dh Dw``, value =
+``floor((2 num + den) / (2 den))``: two taps per axis, half-pixel centres, round half up, 64-bit integers and no float (a
+float64 restatement of the same formula differs by a grey level where rounding error decides a tie).  ``small = R(slot input
+-> h' x w')``; the grid SLIC above runs on ``small`` with ``h', w'`` in place of ``H, W`` everywhere; ``min_size >= 1`` runs f9b's
+rule on the working-size label plane (ids and Philox counters ``r = y w' + x``); the repaint with ``rdiv(sum, n)`` over the
+pixels of ``small`` gives ``painted``; ``out = R(painted -> H x W)`` -- unless no final segment that holds a pixel is
+replaced: then the sample's output is the slot's input bit for bit, not the blurred round trip (recalled as imgaug's own
+shortcut, which cannot be checked here: this build's choice).  For a scaled slot ``validate`` and ``encode_style(..,
+scaled=True)`` measure ``gy``, ``gx`` and ``min_size`` against the working size.  The presets ``"heavy_scaled_device"`` and
+``"mscmrseg_aug2_scaled_device"`` are the ``_connected_`` presets with ``max_size = 128`` on every Superpixels slot.
+``stylize_aug`` takes the scaled entry point iff ``program.needs_scale(H, W)``.  imgaug, cv2 and skimage are not installed
+next to the reference: parity with their resize and with imgaug's shortcut is unpinned, the rule is this build's own
+(``tests/golden/spx_scaled.npz``, ``scripts/make_spx_scaled_golden.py``).
 
 The value is uint8 again between two slots.  imgaug / cv2 / skimage are not vendored by the reference: parity with imgaug is
 unpinned, the convention is this build's own and is pinned by ``tests/golden/stylize.npz`` (``scripts/make_stylize_golden.py``:
@@ -59,8 +80,9 @@ a vectorised numpy restatement and an independent one -- plain Python integers f
 noise-alpha).  Divergences from imgaug: hue / saturation follow the integer formulas above (cv2's uint8 HSV tables differ by
 a grey level in places) and one value moves both (``per_channel`` is not built); the simplex noise is this file's (gradient
 from Philox, grids of at most 16 x 16; the cubic upscale is the Keys kernel in float64, not cv2's fixed-point tables, and the
-samplers draw it only with ``interp="cubic"``, for a share of ``NOISE_CUBIC_P`` of the slots); the superpixels are a grid SLIC without
-imgaug's downscale to 128 pixels, and without a connectivity pass unless ``min_size`` asks for one (above).  The string ``"heavy"`` keeps raising (imgaug's parameter
+samplers draw it only with ``interp="cubic"``, for a share of ``NOISE_CUBIC_P`` of the slots); the superpixels are a grid SLIC, at
+full resolution unless ``max_size`` asks for imgaug's working size, and without a connectivity pass unless ``min_size`` asks
+for one (above).  The string ``"heavy"`` keeps raising (imgaug's parameter
 stream is not reproduced)."""
 from __future__ import annotations
 
@@ -89,6 +111,7 @@ MAX_CONNECT_PIXELS = 1 << 24      # connected slots: the segment sums are 32-bit
 STYLE_ENTRY_NAMES = ("superpixels", "simplex_noise_alpha", "hue_saturation")
 SUPERPIXELS_P_REPLACE, SUPERPIXELS_SEGMENTS = (0.0, 1.0), (20, 200)
 SUPERPIXELS_UPDATES, SUPERPIXELS_COMPACTNESS = 5, 10
+SUPERPIXELS_MAX_SIZE = 128        # imgaug's default max_size (f9c): what the _scaled_ presets put into iarg[6]
 EDGE_ALPHA, EDGE_DIRECTION = (0.5, 1.0), (0.0, 1.0)
 HUE_VALUE = (-20, 20)
 # this build's own (imgaug's defaults where it has one): 1..3 grids of 2..16 cells per side, nearest or bilinear with equal
@@ -231,6 +254,17 @@ def superpixel_min_size(gy: int, gx: int, h: int, w: int) -> int:
     return max(1, (int(h) * int(w)) // (2 * int(gy) * int(gx)))
 
 
+def superpixel_working_size(h: int, w: int, max_size: int):
+    """(h', w') a SUPERPIXELS slot with ``max_size`` works on (f9c): ``(max(1, (h m) // L), max(1, (w m) // L))`` with ``L = max(h,
+    w)`` iff ``m >= 1`` and ``L > m`` (the longer side becomes exactly m), else ``(h, w)``.  Integers only, this build's own
+    (imgaug computes ``int(h * (m / L))`` in floating point; parity is unpinned)"""
+    h, w, m = int(h), int(w), int(max_size)
+    big = max(h, w)
+    if m < 1 or big <= m:
+        return h, w
+    return max(1, (h * m) // big), max(1, (w * m) // big)
+
+
 @dataclass
 class StyleProgram(SlotProgram):
     """``opcode`` int32 ``[B,S]``, ``iarg`` int32 ``[B,S,12]``, ``farg`` float64 ``[B,S,16]``, ``table`` float64 ``[B,S,768]``, ``seed``
@@ -261,11 +295,13 @@ class StyleProgram(SlotProgram):
         self.farg[i, s, 9] = thresh
 
     def set_superpixels(self, i, s, gy, gx, p_replace, seed, iters=SUPERPIXELS_UPDATES, compactness=SUPERPIXELS_COMPACTNESS,
-                        min_size=0):
-        """``min_size`` (``iarg[5]``): 0 = f9's slot; >= 1 = connected segments (f9b, ``superpixel_min_size``)"""
+                        min_size=0, max_size=0):
+        """``min_size`` (``iarg[5]``): 0 = f9's slot; >= 1 = connected segments (f9b, ``superpixel_min_size``).  ``max_size``
+        (``iarg[6]``): 0 = at full resolution; >= 1 = at the working size wherever the image's longer side exceeds it (f9c;
+        ``gy``, ``gx`` and ``min_size`` then belong to ``superpixel_working_size(h, w, max_size)``)"""
         self._clear(i, s, OP_SUPERPIXELS)
         self.iarg[i, s, :4] = (int(gy), int(gx), int(iters), int(math.floor(float(compactness) ** 2 + 0.5)))
-        self.iarg[i, s, 5] = int(min_size)
+        self.iarg[i, s, 5], self.iarg[i, s, 6] = int(min_size), int(max_size)
         self.farg[i, s, 0], self.farg[i, s, 1] = p_replace, compactness
         self.seed[i, s] = seed
 
@@ -273,13 +309,19 @@ class StyleProgram(SlotProgram):
         """any SUPERPIXELS slot with ``iarg[5] > 0`` (a host-side look at the program)"""
         return bool(np.any((self.opcode == OP_SUPERPIXELS) & (self.iarg[..., 5] > 0)))
 
+    def needs_scale(self, h: int, w: int) -> bool:
+        """any SUPERPIXELS slot that is scaled on ``h x w`` images: ``1 <= iarg[6] < max(h, w)`` (a host-side look)"""
+        m = self.iarg[..., 6]
+        return bool(np.any((self.opcode == OP_SUPERPIXELS) & (m >= 1) & (m < max(int(h), int(w)))))
+
     def validate(self, h: Optional[int] = None, w: Optional[int] = None, channels: Optional[int] = None) -> None:
         """Raises ``ValueError`` (naming the field) for a program the kernels are not defined on: shapes and dtypes, more
         than 8 slots, unknown opcodes, non-finite ``farg`` / ``table``; hue on C other than 3, dh outside [-180, 180] or ds
         outside [-255, 255]; a grid count outside 1..3, a grid side outside 2..16, an unknown upscale or aggregation, a sigmoid
         flag that is not 0 / 1, table values outside [0, 1], a threshold beyond +/-1000; gy or gx below 1 or above H / W,
         ``gy gx > 256``, updates outside 0..10, M2 outside 0..2^20, p_replace outside [0, 1], min_size outside 0..H W, or
-        min_size > 0 on more than 2^24 pixels."""
+        min_size > 0 on more than 2^24 pixels; max_size below 0 and, for a slot that ``max_size`` scales on ``h x w`` (f9c), gy
+        or gx above the working size's h' / w', min_size above h' w', or more than 2^24 pixels."""
         self._check_arrays(OP_SUPERPIXELS)
         op, ia, fa, tb = self.opcode, self.iarg, self.farg, self.table
         if channels is not None and not 1 <= channels <= 4:
@@ -314,6 +356,21 @@ class StyleProgram(SlotProgram):
         m = op == OP_SUPERPIXELS
         i, f = ia[m], fa[m]
         if len(i):
+            if np.any(i[:, 6] < 0):
+                raise ValueError("StyleProgram: SUPERPIXELS max_size (iarg[6]) must be at least 0")
+            if h is not None and w is not None:      # f9c: a scaled slot's grid and min_size belong to its working size
+                big, m = max(h, w), i[:, 6].astype(np.int64)
+                sc = (m >= 1) & (big > m)
+                if h * w > MAX_CONNECT_PIXELS and np.any(sc):
+                    raise ValueError("StyleProgram: SUPERPIXELS max_size (iarg[6]) below the longer side takes images of at most "
+                                     "2^24 pixels, got %d x %d" % (h, w))
+                hs, ws = np.maximum(1, (h * m) // big), np.maximum(1, (w * m) // big)
+                if np.any(sc & ((i[:, 0] > hs) | (i[:, 1] > ws))):
+                    raise ValueError("StyleProgram: SUPERPIXELS gy, gx (iarg[0:2]) must be in 1..h', 1..w' of the working size "
+                                     "that max_size (iarg[6]) gives")
+                if np.any(sc & (i[:, 5].astype(np.int64) > hs * ws)):
+                    raise ValueError("StyleProgram: SUPERPIXELS min_size (iarg[5]) must be in 0..h' w' of the working size that "
+                                     "max_size (iarg[6]) gives")
             if np.any(i[:, 0] < 1) or np.any(i[:, 1] < 1) or (h is not None and np.any(i[:, 0] > h)) or \
                     (w is not None and np.any(i[:, 1] > w)):
                 raise ValueError("StyleProgram: SUPERPIXELS gy, gx (iarg[0:2]) must be in 1..H, 1..W")
@@ -360,12 +417,17 @@ def draw_style(b: int, rng: np.random.Generator):
         hue=rng.integers(HUE_VALUE[0], HUE_VALUE[1] + 1, b))
 
 
-def encode_style(prog: StyleProgram, i: int, s: int, entry: int, d, h: int, w: int, connected: bool = False) -> None:
-    """``connected``: Superpixels slots get ``min_size = superpixel_min_size(gy, gx, h, w)`` (the ``_connected_`` presets)"""
+def encode_style(prog: StyleProgram, i: int, s: int, entry: int, d, h: int, w: int, connected: bool = False,
+                 scaled: bool = False) -> None:
+    """``connected``: Superpixels slots get ``min_size = superpixel_min_size(gy, gx, h, w)`` (the ``_connected_`` presets).
+    ``scaled``: they get ``max_size = SUPERPIXELS_MAX_SIZE``, and the grid and ``min_size`` are those of the working size
+    ``superpixel_working_size(h, w, 128)`` (the ``_scaled_`` presets)"""
     if entry == ENTRY_SUPERPIXELS:
-        gy, gx = superpixel_grid(int(d["sp_n"][i]), h, w)
+        m = SUPERPIXELS_MAX_SIZE if scaled else 0
+        hs, ws = superpixel_working_size(h, w, m)
+        gy, gx = superpixel_grid(int(d["sp_n"][i]), hs, ws)
         prog.set_superpixels(i, s, gy, gx, d["sp_p"][i], d["sp_seed"][i],
-                             min_size=superpixel_min_size(gy, gx, h, w) if connected else 0)
+                             min_size=superpixel_min_size(gy, gx, hs, ws) if connected else 0, max_size=m)
     elif entry == ENTRY_NOISE_ALPHA:
         wts = edge_detect_weights(d["na_alpha"][i]) if d["na_kind"][i] == 0 else directed_edge_weights(d["na_alpha"][i], d["na_dir"][i])
         grids = [simplex_grid(int(d["na_size"][i, k, 0]), int(d["na_size"][i, k, 1]), int(d["na_seed"][i, k]))
@@ -389,4 +451,7 @@ def stylize_aug(images: torch.Tensor, program: Optional[StyleProgram] = None) ->
     if images.dtype != torch.uint8 or images.dim() != 4:
         raise TypeError("stylize_aug: uint8 [B,H,W,C] images")
     b, h, w, c = images.shape
-    return K.stylize(images, *upload_style_program(program, b, h, w, c, images.device), connect=program.needs_connect())
+    arrays = upload_style_program(program, b, h, w, c, images.device)
+    if program.needs_scale(h, w):
+        return K.stylize_scaled(images, *arrays)
+    return K.stylize(images, *arrays, connect=program.needs_connect())
