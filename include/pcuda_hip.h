@@ -375,6 +375,12 @@ int pcuda_assemble_batch(const float* images_hwc, const int* mask_labels, int b,
  * device floats, no host read; NaNs are skipped.  workspace: pcuda_minmax_workspace_size() bytes */
 size_t pcuda_minmax_workspace_size(void);
 int pcuda_minmax(const float* x, long long numel, float* out2, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* fp32 -> uint8 with the device (min, max) pair pcuda_minmax wrote (data_generator_mmwhs.py:248-249), in fp32 with every
+ * operation rounded on its own: q = trunc(((x - min) * 255) / (max - min)) clamped to [0, 255]; max == min gives 0
+ * everywhere (0 / 0 in the reference), a NaN element gives 0.  The integers PCUDA_AUG_MINMAX below quantises each gathered
+ * texel to, written out, so that the uint8 stages can run between the quantisation and the warp.  No host read, no
+ * workspace; x and q 16-byte aligned take the wide path, anything else one element per lane. */
+int pcuda_quantize_u8(const float* x, long long numel, const float* minmax, uint8_t* q, pcuda_stream_t s);
 /* device-side light augmentation fused with the batch assembly above (light_aug data_generator_mmwhs.py:87-122 +
  * :245-274; simple_aug data_generator_mscmrseg.py:135-167 + :305-317): per sample one inverse 2x3 matrix
  * inv_mats[b][6] (float64, device; output pixel (x, y) of the FULL image -> source coordinate
@@ -397,6 +403,13 @@ int pcuda_augment_assemble(const void* images_hwc, int images_u8, const int* mas
                            int num_classes, const double* inv_mats, const int* order, const int* cval, int rescale,
                            const float* minmax, float* images_chw, uint8_t* onehot, uint8_t* full_mask, int* labels_full,
                            uint8_t* images_u8_full, pcuda_stream_t s);
+/* the second half of the min-max round trip for images that are uint8 already (pcuda_quantize_u8, then any uint8 stages):
+ * pcuda_augment_assemble on uint8 images with out = min + float(q') * (max - min) / 255 in fp32 (data_generator_mmwhs.py:254);
+ * minmax = the device (min, max) pair, required.  Every other argument and output as above. */
+int pcuda_augment_assemble_dequant(const uint8_t* images_hwc, const int* mask_labels, int b, int h, int w, int c, int crop,
+                                   int num_classes, const double* inv_mats, const int* order, const int* cval,
+                                   const float* minmax, float* images_chw, uint8_t* onehot, uint8_t* full_mask,
+                                   int* labels_full, uint8_t* images_u8_full, pcuda_stream_t s);
 /* device-side photometric augmentation: the photometric operators of ImageProcessor.augmentation2
  * (data_generator_mscmrseg.py:87-132; called at :305-309) on uint8 images [b][h][w][c], c = 1..4, as a per-sample program
  * of `slots` (0..8) slots in device memory: opcode [b][slots], iarg [b][slots][4], farg [b][slots][16] (float64),

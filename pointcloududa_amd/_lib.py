@@ -125,6 +125,8 @@ _PROTOS = {
     "pcuda_minmax_workspace_size": (sz, []),
     "pcuda_minmax": (i32, [vp, i64, vp, vp, sz, vp]),
     "pcuda_augment_assemble": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "pcuda_quantize_u8": (i32, [vp, i64, vp, vp, vp]),
+    "pcuda_augment_assemble_dequant": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pcuda_photometric_workspace_size": (sz, [i32, i32, i32, i32]),
     "pcuda_photometric": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "pcuda_geometric_workspace_size": (sz, [i32, i32, i32, i32, i32]),

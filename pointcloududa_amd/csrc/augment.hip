@@ -1,7 +1,8 @@
 // Device-side light augmentation of the loader path: horizontal / vertical flips and one affine
 // warp per sample (data_generator_mmwhs.py:87-122 light_aug, data_generator_mscmrseg.py:135-167 simple_aug), fused with the
 // batch assembly of pointwise.hip (centre crop, channel-last -> channel-first, labels -> one-hot) and with the MM-WHS
-// batch-global min-max rescale to uint8 and back (data_generator_mmwhs.py:246-254).
+// batch-global min-max rescale to uint8 and back (data_generator_mmwhs.py:246-254).  The two halves of that round trip also
+// stand alone (f6b: pcuda_quantize_u8, pcuda_augment_assemble_dequant), so that uint8 stages can run between them.
 //
 // Convention (this build's own: imgaug / cv2 are not vendored by the reference, parity of the sub-pixel rule is unpinned;
 // pinned against scipy.ndimage.affine_transform(mode="grid-constant") by tests/golden/augment.npz):
@@ -84,6 +85,57 @@ __global__ __launch_bounds__(64) void minmax_final_kernel(const float* __restric
   }
   wave_minmax(lo, hi);
   if (threadIdx.x == 0) { out2[0] = lo; out2[1] = hi; }
+}
+
+// ------------------------------------------------------------------------------------------
+// fp32 -> uint8 with the (min, max) pair above: the joint in front of the uint8 stages (data_generator_mmwhs.py:248-249)
+// ------------------------------------------------------------------------------------------
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kQuantBlocks = 4096;
+constexpr int kQuantPerLane = 16;      // four float4 loads -> one 16-byte store
+
+// images = (images - img_min) * 255. / (img_max - img_min); np.array(images, dtype=np.uint8): fp32, every operation rounded
+// on its own, truncation.  The kernel moves 5 bytes per element, so the true division costs nothing that shows (the warp's
+// texel_value runs it per gathered texel and therefore multiplies by a reciprocal outside a band; same integers).
+// max == min (0 / 0 in the reference): 0; a NaN element: 0 (fmaxf returns the other operand)
+__device__ __forceinline__ uint32_t quantize_one(float x, float mn, float range) {
+  float q = ((x - mn) * 255.f) / range;
+  q = range != 0.f ? q : 0.f;
+  return (uint32_t)(int)fminf(fmaxf(q, 0.f), 255.f);
+}
+
+__device__ __forceinline__ uint32_t quantize_four(f32x4 v, float mn, float range) {
+  return quantize_one(v.x, mn, range) | (quantize_one(v.y, mn, range) << 8) | (quantize_one(v.z, mn, range) << 16) |
+         (quantize_one(v.w, mn, range) << 24);
+}
+
+// vec (x and q 16-byte aligned): a lane owns 16 consecutive elements; the last numel % 16 elements, and everything when a
+// pointer is misaligned, go one element per lane
+__global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restrict__ x, long long numel, int vec,
+                                                          const float* __restrict__ minmax, uint8_t* __restrict__ q) {
+  const float mn = minmax[0], range = minmax[1] - mn;
+  const long long tid = blockIdx.x * 256ll + threadIdx.x, nthr = 256ll * gridDim.x;
+  long long done = 0;
+  if (vec) {
+    const long long n16 = numel / kQuantPerLane;
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+    u32x4* q16 = reinterpret_cast<u32x4*>(q);
+    for (long long i = tid; i < n16; i += nthr) {
+      const f32x4* p = x4 + 4 * i;
+      const f32x4 v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
+      q16[i] = u32x4{quantize_four(v0, mn, range), quantize_four(v1, mn, range), quantize_four(v2, mn, range),
+                     quantize_four(v3, mn, range)};
+      PCUDA_KEEP(p);
+    }
+    done = n16 * kQuantPerLane;
+  }
+  for (long long i = done + tid; i < numel; i += nthr) {
+    const float* p = x + i;
+    const float v = *p;
+    q[i] = (uint8_t)quantize_one(v, mn, range);
+    PCUDA_KEEP(p);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -343,23 +395,40 @@ extern "C" int pcuda_minmax(const float* x, long long numel, float* out2, void* 
   return PCUDA_OK;
 }
 
-extern "C" int pcuda_augment_assemble(const void* images_hwc, int images_u8, const int* mask_labels, int b, int h, int w, int c,
-                                      int crop, int num_classes, const double* inv_mats, const int* order, const int* cval,
-                                      int rescale, const float* minmax, float* images_chw, uint8_t* onehot,
-                                      uint8_t* full_mask, int* labels_full, uint8_t* images_u8_full, pcuda_stream_t s) {
-  if (!images_hwc || !inv_mats || !order || !cval) PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: null pointer");
+extern "C" int pcuda_quantize_u8(const float* x, long long numel, const float* minmax, uint8_t* q, pcuda_stream_t s) {
+  if (!x || !minmax || !q || numel <= 0) PCUDA_FAIL(PCUDA_E_BADARG, "quantize_u8: bad arguments");
+  const int vec = (((uintptr_t)x | (uintptr_t)q) & 15) == 0;
+  const long long per = vec ? 256ll * kQuantPerLane : 256ll * 4;
+  const long long want = (numel + per - 1) / per;
+  const int blocks = (int)(want > kQuantBlocks ? kQuantBlocks : want);
+  ProfScope prof(PCUDA_FAM_POINTWISE, (double)numel * 5.0, (hipStream_t)s);
+  hipLaunchKernelGGL(quantize_u8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, x, numel, vec, minmax, q);
+  PCUDA_CHECK_LAUNCH("quantize_u8_kernel");
+  return PCUDA_OK;
+}
+
+// the host side of both assemble entries: dequant = uint8 images through augment_assemble_kernel<true, PCUDA_AUG_MINMAX>
+static int augment_assemble_run(const char* who, bool dequant, const void* images_hwc, int images_u8, const int* mask_labels,
+                                int b, int h, int w, int c, int crop, int num_classes, const double* inv_mats, const int* order,
+                                const int* cval, int rescale, const float* minmax, float* images_chw, uint8_t* onehot,
+                                uint8_t* full_mask, int* labels_full, uint8_t* images_u8_full, pcuda_stream_t s) {
+  if (!images_hwc || !inv_mats || !order || !cval) PCUDA_FAIL(PCUDA_E_BADARG, "%s: null pointer", who);
   if (!images_chw && !onehot && !full_mask && !labels_full && !images_u8_full)
-    PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: null pointer (no output)");
+    PCUDA_FAIL(PCUDA_E_BADARG, "%s: null pointer (no output)", who);
   if (b <= 0 || b > 65535 || h <= 0 || w <= 0 || c <= 0 || (long long)h * w * c >= (1ll << 31))
-    PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: bad dims");
-  if ((onehot || full_mask || labels_full) && !mask_labels) PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: null pointer (mask_labels)");
-  if (onehot && num_classes < 2) PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: num_classes < 2 with a one-hot output");
-  if (rescale != PCUDA_AUG_NONE && rescale != PCUDA_AUG_MINMAX && rescale != PCUDA_AUG_DIV255)
-    PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: bad rescale mode");
-  if (rescale == PCUDA_AUG_MINMAX && (images_u8 || !minmax))
-    PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: the min-max rescale takes fp32 images and a device (min, max) pair");
-  if (rescale == PCUDA_AUG_DIV255 && !images_u8) PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: the /255 rescale takes uint8 images");
-  if (images_u8_full && !images_u8) PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: a uint8 image output takes uint8 images");
+    PCUDA_FAIL(PCUDA_E_BADARG, "%s: bad dims", who);
+  if ((onehot || full_mask || labels_full) && !mask_labels) PCUDA_FAIL(PCUDA_E_BADARG, "%s: null pointer (mask_labels)", who);
+  if (onehot && num_classes < 2) PCUDA_FAIL(PCUDA_E_BADARG, "%s: num_classes < 2 with a one-hot output", who);
+  if (dequant) {
+    if (!minmax) PCUDA_FAIL(PCUDA_E_BADARG, "%s: null pointer (minmax)", who);
+  } else {
+    if (rescale != PCUDA_AUG_NONE && rescale != PCUDA_AUG_MINMAX && rescale != PCUDA_AUG_DIV255)
+      PCUDA_FAIL(PCUDA_E_BADARG, "%s: bad rescale mode", who);
+    if (rescale == PCUDA_AUG_MINMAX && (images_u8 || !minmax))
+      PCUDA_FAIL(PCUDA_E_BADARG, "%s: the min-max rescale takes fp32 images and a device (min, max) pair", who);
+  }
+  if (rescale == PCUDA_AUG_DIV255 && !images_u8) PCUDA_FAIL(PCUDA_E_BADARG, "%s: the /255 rescale takes uint8 images", who);
+  if (images_u8_full && !images_u8) PCUDA_FAIL(PCUDA_E_BADARG, "%s: a uint8 image output takes uint8 images", who);
   AugArgs a;
   memset(&a, 0, sizeof(a));
   a.y0 = 0; a.x0 = 0; a.oh = h; a.ow = w;
@@ -367,7 +436,7 @@ extern "C" int pcuda_augment_assemble(const void* images_hwc, int images_u8, con
     const int hc = crop / 2;
     a.y0 = h / 2 - hc; a.x0 = w / 2 - hc; a.oh = 2 * hc; a.ow = 2 * hc;
     if (a.y0 < 0 || a.x0 < 0 || a.y0 + a.oh > h || a.x0 + a.ow > w || hc <= 0)
-      PCUDA_FAIL(PCUDA_E_BADARG, "augment_assemble: crop larger than the image");
+      PCUDA_FAIL(PCUDA_E_BADARG, "%s: crop larger than the image", who);
   }
   a.img = images_hwc; a.lab = mask_labels; a.inv = inv_mats; a.order = order; a.cval = cval; a.minmax = minmax;
   a.img_out = images_chw; a.onehot = onehot; a.fullmask = full_mask; a.lab_full = labels_full; a.img_u8_full = images_u8_full;
@@ -387,7 +456,9 @@ extern "C" int pcuda_augment_assemble(const void* images_hwc, int images_u8, con
                  all_pix * (mask_labels ? 4.0 : 0.0) + (full ? all_pix : 0.0), (hipStream_t)s);
 #define PCUDA_AUG_LAUNCH(U8, MODE)                                                                                     \
   hipLaunchKernelGGL((augment_assemble_kernel<U8, MODE>), grid, dim3(256), 0, (hipStream_t)s, a)
-  if (images_u8) {
+  if (dequant) {
+    PCUDA_AUG_LAUNCH(true, PCUDA_AUG_MINMAX);
+  } else if (images_u8) {
     if (rescale == PCUDA_AUG_DIV255) PCUDA_AUG_LAUNCH(true, PCUDA_AUG_DIV255);
     else PCUDA_AUG_LAUNCH(true, PCUDA_AUG_NONE);
   } else {
@@ -397,4 +468,22 @@ extern "C" int pcuda_augment_assemble(const void* images_hwc, int images_u8, con
 #undef PCUDA_AUG_LAUNCH
   PCUDA_CHECK_LAUNCH("augment_assemble_kernel");
   return PCUDA_OK;
+}
+
+extern "C" int pcuda_augment_assemble(const void* images_hwc, int images_u8, const int* mask_labels, int b, int h, int w, int c,
+                                      int crop, int num_classes, const double* inv_mats, const int* order, const int* cval,
+                                      int rescale, const float* minmax, float* images_chw, uint8_t* onehot,
+                                      uint8_t* full_mask, int* labels_full, uint8_t* images_u8_full, pcuda_stream_t s) {
+  return augment_assemble_run("augment_assemble", false, images_hwc, images_u8, mask_labels, b, h, w, c, crop, num_classes, inv_mats,
+                              order, cval, rescale, minmax, images_chw, onehot, full_mask, labels_full, images_u8_full, s);
+}
+
+// uint8 images that pcuda_quantize_u8 made (and the uint8 stages changed) back to fp32 behind the warp:
+// images = img_min + images.astype(np.float32) * (img_max - img_min) / 255. (data_generator_mmwhs.py:254)
+extern "C" int pcuda_augment_assemble_dequant(const uint8_t* images_hwc, const int* mask_labels, int b, int h, int w, int c, int crop,
+                                              int num_classes, const double* inv_mats, const int* order, const int* cval,
+                                              const float* minmax, float* images_chw, uint8_t* onehot, uint8_t* full_mask,
+                                              int* labels_full, uint8_t* images_u8_full, pcuda_stream_t s) {
+  return augment_assemble_run("augment_assemble_dequant", true, images_hwc, 1, mask_labels, b, h, w, c, crop, num_classes, inv_mats,
+                              order, cval, PCUDA_AUG_MINMAX, minmax, images_chw, onehot, full_mask, labels_full, images_u8_full, s);
 }

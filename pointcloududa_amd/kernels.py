@@ -960,27 +960,24 @@ def minmax(x):
 AUG_NONE, AUG_MINMAX, AUG_DIV255 = 0, 1, 2
 
 
-def augment_assemble(images_hwc, mask_labels, inv_mats, order, cval, num_classes=5, crop=0, rescale=AUG_NONE, minmax=None,
-                     want_images=True, want_onehot=True, want_full_mask=False, want_labels=False, want_u8=False):
-    """Flips + affine + rescale + batch assembly in one launch (``pcuda_augment_assemble``).  images ``[B,H,W,C]`` fp32 or
-    uint8, labels ``[B,H,W]`` int32 or None, ``inv_mats`` float64 ``[B,2,3]``, ``order`` / ``cval`` int32 ``[B]``, all on
-    the device -> dict with the outputs asked for: ``images`` fp32 ``[B,C,h,w]``, ``onehot`` uint8 ``[B,K,h,w]`` (cropped),
-    ``full_mask`` uint8 ``[B,H,W]``, ``labels`` int32 ``[B,H,W]``, ``images_u8`` uint8 ``[B,H,W,C]`` (full size)."""
-    if images_hwc.dtype not in (torch.float32, torch.uint8):
-        raise TypeError("augment_assemble: fp32 or uint8 images")
+def _augment_assemble(what, dequant, images_hwc, mask_labels, inv_mats, order, cval, num_classes, crop, rescale, minmax,
+                      want_images, want_onehot, want_full_mask, want_labels, want_u8):
+    """the body of ``augment_assemble`` and ``augment_assemble_dequant``: checks, output tensors, one launch"""
+    if images_hwc.dtype not in ((torch.uint8,) if dequant else (torch.float32, torch.uint8)):
+        raise TypeError("%s: %s images" % (what, "uint8" if dequant else "fp32 or uint8"))
     _req(images_hwc, images_hwc.dtype)
     _req(inv_mats, torch.float64); _req(order, torch.int32); _req(cval, torch.int32)
     images_hwc = images_hwc.contiguous()
     b, h, w, c = images_hwc.shape
     if tuple(inv_mats.shape) != (b, 2, 3) or tuple(order.shape) != (b,) or tuple(cval.shape) != (b,):
-        raise ValueError("augment_assemble: per-sample parameters do not match the batch of %d" % b)
+        raise ValueError("%s: per-sample parameters do not match the batch of %d" % (what, b))
     dev = images_hwc.device
     oh, ow = (2 * (crop // 2), 2 * (crop // 2)) if crop else (h, w)
     if mask_labels is not None:
         _req(mask_labels, torch.int32)
         mask_labels = mask_labels.contiguous()
         if tuple(mask_labels.shape) != (b, h, w):
-            raise ValueError("augment_assemble: mask shape %r does not match the images" % (tuple(mask_labels.shape),))
+            raise ValueError("%s: mask shape %r does not match the images" % (what, tuple(mask_labels.shape)))
     else:
         want_onehot = want_full_mask = want_labels = False
     out = {}
@@ -996,13 +993,53 @@ def augment_assemble(images_hwc, mask_labels, inv_mats, order, cval, num_classes
         out["images_u8"] = torch.empty((b, h, w, c), dtype=torch.uint8, device=dev)
     if minmax is not None:
         _req(minmax)
-    check(L.lib().pcuda_augment_assemble(images_hwc.data_ptr(), int(images_hwc.dtype == torch.uint8), _ptr(mask_labels), b, h, w, c,
-                                         int(crop), int(num_classes), inv_mats.contiguous().data_ptr(),
-                                         order.contiguous().data_ptr(), cval.contiguous().data_ptr(), int(rescale),
-                                         _ptr(minmax), _ptr(out.get("images")), _ptr(out.get("onehot")),
-                                         _ptr(out.get("full_mask")), _ptr(out.get("labels")), _ptr(out.get("images_u8")),
-                                         _stream()), "augment_assemble")
+    head = (images_hwc.data_ptr(),) if dequant else (images_hwc.data_ptr(), int(images_hwc.dtype == torch.uint8))
+    mid = (_ptr(minmax),) if dequant else (int(rescale), _ptr(minmax))
+    fn = L.lib().pcuda_augment_assemble_dequant if dequant else L.lib().pcuda_augment_assemble
+    check(fn(*head, _ptr(mask_labels), b, h, w, c, int(crop), int(num_classes), inv_mats.contiguous().data_ptr(),
+             order.contiguous().data_ptr(), cval.contiguous().data_ptr(), *mid, _ptr(out.get("images")), _ptr(out.get("onehot")),
+             _ptr(out.get("full_mask")), _ptr(out.get("labels")), _ptr(out.get("images_u8")), _stream()), what)
     return out
+
+
+def augment_assemble(images_hwc, mask_labels, inv_mats, order, cval, num_classes=5, crop=0, rescale=AUG_NONE, minmax=None,
+                     want_images=True, want_onehot=True, want_full_mask=False, want_labels=False, want_u8=False):
+    """Flips + affine + rescale + batch assembly in one launch (``pcuda_augment_assemble``).  images ``[B,H,W,C]`` fp32 or
+    uint8, labels ``[B,H,W]`` int32 or None, ``inv_mats`` float64 ``[B,2,3]``, ``order`` / ``cval`` int32 ``[B]``, all on
+    the device -> dict with the outputs asked for: ``images`` fp32 ``[B,C,h,w]``, ``onehot`` uint8 ``[B,K,h,w]`` (cropped),
+    ``full_mask`` uint8 ``[B,H,W]``, ``labels`` int32 ``[B,H,W]``, ``images_u8`` uint8 ``[B,H,W,C]`` (full size)."""
+    return _augment_assemble("augment_assemble", False, images_hwc, mask_labels, inv_mats, order, cval, num_classes, crop, rescale,
+                             minmax, want_images, want_onehot, want_full_mask, want_labels, want_u8)
+
+
+def quantize_u8(x, minmax, out=None):
+    """fp32 tensor and the device ``(min, max)`` pair of ``minmax(x)`` -> uint8 tensor of ``x``'s shape
+    (``pcuda_quantize_u8``): ``trunc(((x - min) * 255) / (max - min))`` in fp32, clamped to [0, 255]; ``max == min`` and NaN
+    elements give 0.  No host read.  ``x`` and ``out`` may be any views with contiguous elements (a misaligned one takes the
+    kernel's one-element path)."""
+    _req(x); _req(minmax)
+    if minmax.numel() != 2 or not minmax.is_contiguous():
+        raise ValueError("quantize_u8: minmax is the contiguous (min, max) pair of kernels.minmax")
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or out.shape != x.shape or not out.is_contiguous():
+        raise ValueError("quantize_u8: out must be a contiguous uint8 tensor of shape %s" % list(x.shape))
+    check(L.lib().pcuda_quantize_u8(x.data_ptr(), x.numel(), minmax.data_ptr(), out.data_ptr(), _stream()), "quantize_u8")
+    return out
+
+
+def augment_assemble_dequant(images_u8, mask_labels, inv_mats, order, cval, minmax, num_classes=5, crop=0, want_images=True,
+                             want_onehot=True, want_full_mask=False, want_labels=False, want_u8=False):
+    """``augment_assemble`` on uint8 images that ``quantize_u8`` made, back to fp32 behind the warp
+    (``pcuda_augment_assemble_dequant``): ``images = min + float(q') * (max - min) / 255``; ``minmax`` is the device pair the
+    images were quantised with.  Outputs as ``augment_assemble``."""
+    if minmax is None:
+        raise TypeError("augment_assemble_dequant: minmax is required (the pair the images were quantised with)")
+    if minmax.numel() != 2 or not minmax.is_contiguous():
+        raise ValueError("augment_assemble_dequant: minmax is the contiguous (min, max) pair of kernels.minmax")
+    return _augment_assemble("augment_assemble_dequant", True, images_u8, mask_labels, inv_mats, order, cval, num_classes, crop,
+                             AUG_MINMAX, minmax, want_images, want_onehot, want_full_mask, want_labels, want_u8)
 
 
 def photometric(images_u8, opcode, iarg, farg, seed, out=None):

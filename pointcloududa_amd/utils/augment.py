@@ -36,7 +36,9 @@ recipes with it; ``"heavy_connected_device"`` / ``"mscmrseg_aug2_connected_devic
 fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
 ``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
 in front of everything else.  A reference per sample, drawn from a ``HistReferenceBank`` that stays on the device (f10b):
-``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``.
+``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``.  fp32 batches
+reach the uint8 stages through ``rescale="minmax_u8"`` (f6b: ``quantize_minmax``, then the plan or program, then the dequantising
+assemble), which is the MM-WHS generator's ``-aug heavy`` branch.
 
 This module is the facade: the parameters and matrices of the light pipeline live in ``utils/affine.py``, the heavy recipes
 (presets, ``sample_heavy_plan``, ``heavy_aug``, ``sample_geo_program``, ``sample_style_program``) in ``utils/heavy.py``, the frame all
@@ -65,6 +67,26 @@ from .heavy import (AUG2_CONNECTED_PRESET, AUG2_DEVICE_PRESET, AUG2_FULL_PRESET,
                     sample_geo_program, sample_heavy_plan, sample_style_program)
 
 
+RESCALES = ("minmax", "minmax_u8", "div255", None)
+
+
+def _check_rescale(who, rescale):
+    if rescale is not None and not (isinstance(rescale, str) and rescale in RESCALES):
+        raise ValueError("%s: rescale must be 'minmax', 'minmax_u8', 'div255' or None, got %r" % (who, rescale))
+
+
+def quantize_minmax(images_f32: torch.Tensor):
+    """``data_generator_mmwhs.py:246-249`` on the device: fp32 ``[B,H,W,C]`` images -> ``(q uint8 [B,H,W,C], minmax [2])`` with
+    the batch-global ``(min, max)`` pair kept on the device (``kernels.minmax``) and ``q = trunc((x - min) * 255 / (max - min))``
+    in fp32 (``kernels.quantize_u8``); ``max == min`` gives 0 everywhere.  ``kernels.augment_assemble_dequant`` takes both back
+    to fp32 behind the uint8 stages."""
+    if not torch.is_tensor(images_f32) or images_f32.dtype != torch.float32 or images_f32.dim() != 4:
+        raise TypeError("quantize_minmax: fp32 [B,H,W,C] images")
+    images_f32 = images_f32.contiguous()
+    mm = K.minmax(images_f32)
+    return K.quantize_u8(images_f32, mm), mm
+
+
 def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optional[AugmentParams], num_classes: int = 5,
                   crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
                   firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True,
@@ -79,7 +101,12 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
     warp, ``min + float(q') * (max - min) / 255``, all fp32.  ``max == min`` is undefined in the reference (a NaN cast to
     uint8); here ``q`` is 0 everywhere, so every output equals ``min``.  ``"div255"``: warp, ``float32(q') / 255``.
     ``None``: no quantisation, the fp32 values themselves are gathered / interpolated; with ``params=None`` or
-    all-identity parameters this is ``assemble_batch`` bit for bit.
+    all-identity parameters this is ``assemble_batch`` bit for bit.  ``"minmax_u8"`` (fp32 images; the MM-WHS generator's
+    ``-aug heavy`` branch, ``data_generator_mmwhs.py:245-263``): the same round trip with the uint8 images written out in
+    between, so that a ``heavy`` plan and a ``photometric`` program run on them: ``match_hist`` on fp32, min / max, quantise
+    (``quantize_minmax``), plan, program, then the warp with ``min + float(q') * (max - min) / 255``
+    (``kernels.augment_assemble_dequant``).  Without a plan or program it is the fused ``"minmax"`` launch, whose bits it
+    shares; uint8 images raise ``TypeError``.
 
     ``resample_verts`` re-samples the point cloud from the FULL-size warped mask (``:255-263``); the mask is written by the
     same launch (``fused_mask``) or by a second launch of the kernel over the full image.  Otherwise ``verts`` (integer
@@ -88,11 +115,12 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
 
     ``photometric``: a ``PhotoProgram`` applied to the uint8 images in front of the warp (``photometric_aug``: the
     photometric part of ``augmentation2``, ``data_generator_mscmrseg.py:87-132``); masks and vertices are untouched by it.  fp32
-    images (``rescale="minmax"``) with a program raise ``TypeError``.
+    images (``rescale="minmax"``) with a program raise ``TypeError``; ``rescale="minmax_u8"`` is the way in for them.
 
     ``heavy``: a ``HeavyPlan`` (``sample_heavy_plan``: the reference's default ``augmentation``, ``data_generator_mscmrseg.py:20-84``)
     run on the uint8 images AND the masks in front of everything else (``heavy_aug``); with ``resample_verts`` the point
-    cloud is drawn from the full-size warped mask, as without a plan.  fp32 images with a plan raise ``TypeError``.
+    cloud is drawn from the full-size warped mask, as without a plan.  fp32 images with a plan raise ``TypeError`` unless
+    ``rescale="minmax_u8"`` quantises them first.
 
     ``match_hist``: a ``HistReference``; the raw images (fp32 or uint8) are histogram-matched against it before anything else
     (``match_histograms``: ``data_generator_mmwhs.py:236-237``, the generator's ``-mh``), so the batch min / max of
@@ -100,10 +128,17 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
     images; masks and vertices are untouched.  ``params=None, rescale=None`` is then the generator's ``aug=''`` branch.  With a
     ``HistReferenceBank`` sample ``i`` is matched to reference ``match_hist_index[i]`` (``match_histograms``' ``index``: a host
     sequence, an int32 device tensor, or ``None`` for a bank of ``B`` or of one)."""
+    _check_rescale("augment_batch", rescale)
     if match_hist is not None:
         images_hwc = match_histograms(images_hwc, match_hist, index=match_hist_index)
     elif match_hist_index is not None:
         raise TypeError("augment_batch: match_hist_index goes with match_hist (a HistReferenceBank)")
+    mm = None
+    if rescale == "minmax_u8":
+        if images_hwc.dtype != torch.float32:
+            raise TypeError("augment_batch: the min-max rescale takes fp32 images")
+        if heavy is not None or photometric is not None:      # (without uint8 stages the fused "minmax" launch: same bits)
+            images_hwc, mm = quantize_minmax(images_hwc)
     if heavy is not None:
         if rescale == "minmax" or images_hwc.dtype != torch.uint8:
             raise TypeError("augment_batch: a heavy plan takes uint8 images (rescale='div255' or None)")
@@ -116,8 +151,9 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
             raise TypeError("augment_batch: a photometric program takes uint8 images (rescale='div255' or None)")
         images_hwc = photometric_aug(images_hwc, photometric)
     inv, order, cval = upload_params(params, b, h, w, dev)
-    mm = None
-    if rescale == "minmax":
+    if mm is not None:
+        mode = None      # quantised above: the dequantising assemble
+    elif rescale in ("minmax", "minmax_u8"):
         if images_hwc.dtype != torch.float32:
             raise TypeError("augment_batch: the min-max rescale takes fp32 images")
         mode, mm = K.AUG_MINMAX, K.minmax(images_hwc)
@@ -125,16 +161,16 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
         if images_hwc.dtype != torch.uint8:
             raise TypeError("augment_batch: the /255 rescale takes uint8 images")
         mode = K.AUG_DIV255
-    elif rescale is None:
-        mode = K.AUG_NONE
     else:
-        raise ValueError("augment_batch: rescale must be 'minmax', 'div255' or None, got %r" % (rescale,))
-    out = K.augment_assemble(images_hwc, lab, inv, order, cval, num_classes, crop_size, mode, mm,
-                             want_full_mask=resample_verts and fused_mask)
+        mode = K.AUG_NONE
+
+    def assemble(**want):
+        if mode is None:
+            return K.augment_assemble_dequant(images_hwc, lab, inv, order, cval, mm, num_classes, crop_size, **want)
+        return K.augment_assemble(images_hwc, lab, inv, order, cval, num_classes, crop_size, mode, mm, **want)
+    out = assemble(want_full_mask=resample_verts and fused_mask)
     if resample_verts:
-        full = out["full_mask"] if fused_mask else K.augment_assemble(
-            images_hwc, lab, inv, order, cval, num_classes, crop_size, mode, mm, want_images=False, want_onehot=False,
-            want_full_mask=True)["full_mask"]
+        full = out["full_mask"] if fused_mask else assemble(want_images=False, want_onehot=False, want_full_mask=True)["full_mask"]
         if firsts is None:
             firsts = torch.zeros(b, dtype=torch.int32, device=dev)
         verts = masks_to_pointclouds(full, firsts)
@@ -189,7 +225,9 @@ class AugmentedBatches:
     ``match_hist_reference`` (an ``[H,W,C]`` numpy image) its tables are built and uploaded once (``match_hist``) and every batch
     is histogram-matched against it first.  With ``match_hist_bank`` (a ``HistReferenceBank``) every sample is matched to a
     reference drawn from the bank: ``rng.integers(R, size=B)`` is the FIRST draw of a batch (``last_match_index``), made only
-    when a bank is given, so without one the generator is consumed exactly as before."""
+    when a bank is given, so without one the generator is consumed exactly as before.  ``rescale="minmax_u8"`` (fp32 batches)
+    goes with every kind of preset and consumes the generator draw for draw as ``"div255"`` does: with
+    ``heavy_preset="heavy_refpad_device"`` it is the MM-WHS generator's ``-aug heavy`` branch."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
@@ -197,6 +235,7 @@ class AugmentedBatches:
                  match_hist_reference: Optional[np.ndarray] = None, match_hist_bank: Optional[HistReferenceBank] = None,
                  heavy_interp: str = "linear"):
         _check_interp(heavy_interp)
+        _check_rescale("AugmentedBatches", rescale)
         if match_hist_reference is not None and match_hist_bank is not None:
             raise ValueError("AugmentedBatches: match_hist_reference (one image for every sample) or match_hist_bank, not both")
         if match_hist_bank is not None and not isinstance(match_hist_bank, HistReferenceBank):
