@@ -945,6 +945,48 @@ int pcuda_jaccard_bwd(const void* truth, int truth_is_u8, int n, int c, long lon
                       float* dprobs, const void* workspace, pcuda_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * Dice loss (the -dice switch both training scripts parse and never read; csrc/dice_loss.hip)
+ * ---------------------------------------------------------------------------------- */
+/* This build's own rule (the reference builds kornia.losses.DiceLoss() and never calls it; parity with any kornia version is
+ * unpinned, and kornia's + eps on its one-hot tensor is not reproduced).  p: probabilities, y: one-hot truth,
+ *   PCUDA_OV_DICE_CLASS   I_c = sum p y, S_c = sum (p + y) over (batch, pixels): loss = 1 - mean_c 2 I_c / (S_c + eps)
+ *   PCUDA_OV_DICE_SAMPLE  I_n, S_n over (classes, pixels) of sample n:           loss = mean_n (1 - 2 I_n / (S_n + eps))
+ *   d loss / d p = -(2 / M) (y / (S + eps) - I / (S + eps)^2) with the sums of the element's own class or sample, M = c or n.
+ * All three families: a forward call leaves the coefficients 1 / (S + eps), I / (S + eps)^2 in its workspace and the
+ * backward call reads them there (eps is an argument of the forward only; the same n, c, hw, overlap / reduce on both);
+ * partial sums of different samples never share a row, the final reduce runs in a fixed order in double: the same bits
+ * from run to run, any n (it is not laid on a grid's y axis).  Never allocate, never synchronise; arguments are checked
+ * before any launch (PCUDA_E_BADARG, PCUDA_E_UNSUPPORTED above the class limit of the fused form, PCUDA_E_WORKSPACE). */
+#define PCUDA_OV_DICE_CLASS 1
+#define PCUDA_OV_DICE_SAMPLE 2
+/* pcuda_seg_loss_fwd / _bwd with a Dice overlap term: out2 = [bce | double-softmax ce, dice], c = 1..8;
+ * dlogits = g_main * d main / do + g_ov * d dice / do (a NULL seed is 1).  workspace_size: 0 for arguments the calls reject */
+size_t pcuda_seg_loss_ov_workspace_size(int n, int c, long long hw, int overlap);
+int pcuda_seg_loss_ov_fwd(const float* logits, const uint8_t* onehot, int mode, int overlap, double eps, int n, int c,
+                          long long hw, float* out2, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+int pcuda_seg_loss_ov_bwd(const float* logits, const uint8_t* onehot, int mode, int overlap, int n, int c, long long hw,
+                          const float* g_main, const float* g_ov, float* dlogits, const void* workspace,
+                          size_t workspace_bytes, pcuda_stream_t s);
+/* Dice on given probabilities, the twin of pcuda_jaccard_*: probs fp32 dense [n][c][hw]; truth fp32 or uint8, same shape;
+ * reduce = PCUDA_OV_DICE_CLASS | PCUDA_OV_DICE_SAMPLE; c = 1..16.  bwd: dprobs = gout * d loss / d probs (gout NULL: 1) */
+size_t pcuda_dice_workspace_size(int n, int c, long long hw, int reduce);
+int pcuda_dice_fwd(const float* probs, const void* truth, int truth_is_u8, int n, int c, long long hw, int reduce, float eps,
+                   float* loss, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+int pcuda_dice_bwd(const void* truth, int truth_is_u8, int n, int c, long long hw, int reduce, const float* gout,
+                   float* dprobs, const void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* Dice per sample on logits [n][c][hw] and a label map [n][hw] (uint8 or int64): p = softmax over the channels, computed
+ * inside; the one-hot tensor is never written.  A label outside [0, c) belongs to no class (nothing to I, only p to S) and
+ * is counted: bad_count (device, may be NULL) is zeroed and receives their number (an integer atomic).  c = 1..16.
+ * bwd: dlogits = gout * d loss / d logits */
+size_t pcuda_dice_labels_workspace_size(int n, int c, long long hw);
+int pcuda_dice_labels_fwd(const float* logits, const void* labels, int labels_are_i64, int n, int c, long long hw, float eps,
+                          float* loss, unsigned long long* bad_count, void* workspace, size_t workspace_bytes,
+                          pcuda_stream_t s);
+int pcuda_dice_labels_bwd(const float* logits, const void* labels, int labels_are_i64, int n, int c, long long hw,
+                          const float* gout, float* dlogits, const void* workspace, size_t workspace_bytes,
+                          pcuda_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * mask -> surface point cloud sampler (utils/npy2point.py:7-18,101-125)
  * ---------------------------------------------------------------------------------- */
 /* canonical surface-vertex list of b binary masks [b][h][w] (uint8, >0 = foreground):

@@ -197,7 +197,14 @@ def _cfg_from(args, variant, opts) -> TrainCfg:
                     d4lr=lr(o4, 2.5e-5), d_momentum=mom, softmax=bool(g("softmax", True)), w1=float(g("w1", 1.0)),
                     w2=float(g("w2", 1.0)), w4=float(g("w4", 1.0)), n_class=int(g("n_class", 0)) or _n_class(args),
                     etpls=bool(g("etpls", False)), Tetpls=bool(g("Tetpls", False)), d4aux=bool(g("d4aux", False)),
-                    gen_sgd=isinstance(og, (torch.optim.SGD, FusedSGD)))
+                    gen_sgd=isinstance(og, (torch.optim.SGD, FusedSGD)), dice=_dice_from(args))
+
+
+def _dice_from(args) -> str:
+    """``args.dice`` (-dice, "whether to use dice loss instead of jaccard loss") -> TrainCfg.dice: truthy means the per-class
+    term, the counterpart of the Jaccard term it replaces; a string ("class" / "sample" / "") is taken as given"""
+    d = getattr(args, "dice", False)
+    return d if isinstance(d, str) else ("class" if d else "")
 
 
 def _n_class(args) -> int:
@@ -254,6 +261,7 @@ def _trainer_for(model_gen, model_dis1, model_dis2, model_dis4, opts, args, vari
     tr._wp.fill_(tr.cfg.wp)
     for k in ("w1", "w2", "w4"):
         setattr(tr.cfg, k, float(getattr(args, k, getattr(tr.cfg, k))))
+    tr.cfg.dice = _dice_from(args)           # (not part of the cache key above)
     return tr
 
 
@@ -327,7 +335,7 @@ def valid_model_with_one_dataset(variant, args, seg_model, data_generator, hd: b
     ms = variant == "mscmrseg"
     d4 = bool(getattr(args, "d4", False)) or (not ms and bool(getattr(args, "d4aux", False)))
     r = V.valid_model_with_one_dataset(seg_model, batches(), d4=d4, variant=variant, softmax=bool(getattr(args, "softmax", True)),
-                                       hd=hd)
+                                       hd=hd, dice=_dice_from(args))
     seg_model.eval()                                   # the reference leaves the model in eval mode (:60)
     if not ms:
         r["vert_loss"] = r.pop("valid_vert_loss")

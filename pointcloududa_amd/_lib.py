@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("PCUDA_LIB") or os.path.join(_HERE, "lib", "libpcuda_h
 
 PREC_BF16X3, PREC_BF16 = 0, 1
 ACT_SIGMOID, ACT_SOFTMAX = 0, 1
+OV_DICE_CLASS, OV_DICE_SAMPLE = 1, 2      # PCUDA_OV_*: the Dice term / reduction of the pcuda_seg_loss_ov_* and pcuda_dice_* calls
 FAM_CONV_FWD, FAM_CONV_WGRAD, FAM_POINTWISE, FAM_DENSE_F32 = 0, 1, 2, 3
 
 c_f32p = C.c_void_p      # all device pointers travel as integers
@@ -115,6 +116,15 @@ _PROTOS = {
     "pcuda_jaccard_workspace_size": (sz, [i32]),
     "pcuda_jaccard_fwd": (i32, [vp, vp, i32, i32, i32, i64, f32, vp, vp, sz, vp]),
     "pcuda_jaccard_bwd": (i32, [vp, i32, i32, i32, i64, f32, vp, vp, vp, vp]),
+    "pcuda_seg_loss_ov_workspace_size": (sz, [i32, i32, i64, i32]),
+    "pcuda_seg_loss_ov_fwd": (i32, [vp, vp, i32, i32, C.c_double, i32, i32, i64, vp, vp, sz, vp]),
+    "pcuda_seg_loss_ov_bwd": (i32, [vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp, sz, vp]),
+    "pcuda_dice_workspace_size": (sz, [i32, i32, i64, i32]),
+    "pcuda_dice_fwd": (i32, [vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, sz, vp]),
+    "pcuda_dice_bwd": (i32, [vp, i32, i32, i32, i64, i32, vp, vp, vp, sz, vp]),
+    "pcuda_dice_labels_workspace_size": (sz, [i32, i32, i64]),
+    "pcuda_dice_labels_fwd": (i32, [vp, vp, i32, i32, i32, i64, f32, vp, vp, vp, sz, vp]),
+    "pcuda_dice_labels_bwd": (i32, [vp, vp, i32, i32, i32, i64, vp, vp, vp, sz, vp]),
     "pcuda_bce_const_fwd": (i32, [vp, i64, f32, vp, vp, vp]),
     "pcuda_bce_const_bwd": (i32, [vp, i64, f32, vp, f32, vp, vp]),
     "pcuda_nn_loss_workspace_floats": (sz, [i32, i32]),

@@ -5,12 +5,10 @@
 //   domain BCE(const)    train_mscmrseg.py:224-226
 //   batch_NN_loss        utils/loss.py:40-76
 //   Dice metric          utils/utils.py:32-40 + utils/metric.py:5-36
-#include "common.h"
+#include "loss_device.h"
 
 #define MAXC 16
 #define SMOOTHF 1e-7f
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---------------------------------------------------------------------------- entropy
 // one thread per pixel, channels strided by hw (coalesced per channel)
@@ -422,10 +420,6 @@ __global__ void dice_final_kernel(const unsigned long long* __restrict__ cnt, in
 }
 
 // ============================================================================ host wrappers
-namespace {
-inline int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
-}
-
 extern "C" int pcuda_entropy_fwd(const float* logits, int mode, float norm, float* ent, float* prob, int n, int c,
                                  long long hw, pcuda_stream_t s) {
   if (!logits || !ent || n <= 0 || c <= 0 || c > MAXC || hw <= 0) PCUDA_FAIL(PCUDA_E_BADARG, "entropy_fwd: bad arguments");

@@ -876,6 +876,108 @@ def jaccard_bwd(truth, shape, eps, ws, gout):
     return dp
 
 
+_OVERLAP = {"dice": L.OV_DICE_CLASS, "dice_sample": L.OV_DICE_SAMPLE, "class": L.OV_DICE_CLASS, "sample": L.OV_DICE_SAMPLE}
+
+
+def _overlap(name):
+    """'dice' / 'class' (per class) or 'dice_sample' / 'sample' (per sample) -> PCUDA_OV_*"""
+    if name not in _OVERLAP:
+        raise ValueError("Dice term %r: one of %s" % (name, ", ".join(sorted(_OVERLAP))))
+    return _OVERLAP[name]
+
+
+def seg_loss_ov_fwd(logits, onehot, mode="sigmoid", overlap="dice", eps=1e-7):
+    """seg_loss_fwd with a Dice overlap term ('dice': per class, 'dice_sample': per sample) -> (out2 = [main, dice], workspace)"""
+    _req(logits)
+    _req(onehot, torch.uint8)
+    ov = _overlap(overlap)
+    n, c = logits.shape[:2]
+    hw = logits.numel() // (n * c)
+    lib = L.lib()
+    nb = lib.pcuda_seg_loss_ov_workspace_size(n, c, hw, ov)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=logits.device)
+    out2 = torch.empty(2, dtype=torch.float32, device=logits.device)
+    check(lib.pcuda_seg_loss_ov_fwd(logits.data_ptr(), onehot.data_ptr(), _mode(mode), ov, float(eps), n, c, hw,
+                                    out2.data_ptr(), ws.data_ptr(), nb, _stream()), "seg_loss_ov_fwd")
+    return out2, ws
+
+
+def seg_loss_ov_bwd(logits, onehot, mode, overlap, ws, g_main=None, g_ov=None):
+    n, c = logits.shape[:2]
+    hw = logits.numel() // (n * c)
+    d = torch.empty_like(logits)
+    check(L.lib().pcuda_seg_loss_ov_bwd(logits.data_ptr(), onehot.data_ptr(), _mode(mode), _overlap(overlap), n, c, hw,
+                                        _ptr(g_main), _ptr(g_ov), d.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "seg_loss_ov_bwd")
+    return d
+
+
+def dice_fwd(probs, truth, eps, reduce="class"):
+    """probs fp32 [n,c,...]; truth one-hot, fp32 or uint8, same shape; reduce 'class' | 'sample' -> (loss scalar, workspace,
+    the truth tensor the kernel read)"""
+    _req(probs)
+    red = _overlap(reduce)
+    if truth.dtype not in (torch.float32, torch.uint8):
+        truth = truth.float()
+    _req(truth, truth.dtype)
+    if truth.shape != probs.shape:
+        raise ValueError("dice: `true` %r and probabilities %r differ in shape" % (tuple(truth.shape), tuple(probs.shape)))
+    probs, truth = probs.contiguous(), truth.contiguous()
+    n, c = probs.shape[:2]
+    hw = probs.numel() // (n * c)
+    lib = L.lib()
+    nb = lib.pcuda_dice_workspace_size(n, c, hw, red)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=probs.device)
+    loss = torch.empty((), dtype=torch.float32, device=probs.device)
+    check(lib.pcuda_dice_fwd(probs.data_ptr(), truth.data_ptr(), 1 if truth.dtype == torch.uint8 else 0, n, c, hw, red,
+                             float(eps), loss.data_ptr(), ws.data_ptr(), nb, _stream()), "dice_fwd")
+    return loss, ws, truth
+
+
+def dice_bwd(truth, shape, reduce, ws, gout):
+    n, c = shape[:2]
+    hw = 1
+    for d in shape[2:]:
+        hw *= d
+    dp = torch.empty(shape, dtype=torch.float32, device=truth.device)
+    check(L.lib().pcuda_dice_bwd(truth.data_ptr(), 1 if truth.dtype == torch.uint8 else 0, n, c, hw, _overlap(reduce),
+                                 _ptr(gout), dp.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dice_bwd")
+    return dp
+
+
+def dice_labels_fwd(logits, labels, eps=1e-6):
+    """logits fp32 [n,c,...]; labels uint8 or int64 [n,...] -> (loss scalar, workspace, the labels the kernel read, the device
+    counter (int64 scalar) of labels outside [0, c))"""
+    _req(logits)
+    if labels.dtype not in (torch.uint8, torch.int64):
+        raise TypeError("dice_labels: uint8 or int64 labels, got %s" % labels.dtype)
+    _req(labels, labels.dtype)
+    logits, labels = logits.contiguous(), labels.contiguous()
+    n, c = logits.shape[:2]
+    hw = logits.numel() // (n * c)
+    if labels.numel() != n * hw:
+        raise ValueError("dice_labels: labels %r do not match logits %r" % (tuple(labels.shape), tuple(logits.shape)))
+    lib = L.lib()
+    nb = lib.pcuda_dice_labels_workspace_size(n, c, hw)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    bad = torch.empty((), dtype=torch.int64, device=logits.device)
+    check(lib.pcuda_dice_labels_fwd(logits.data_ptr(), labels.data_ptr(), 1 if labels.dtype == torch.int64 else 0, n, c, hw,
+                                    float(eps), loss.data_ptr(), bad.data_ptr(), ws.data_ptr(), nb, _stream()),
+          "dice_labels_fwd")
+    return loss, ws, labels, bad
+
+
+def dice_labels_bwd(logits, labels, ws, gout):
+    n, c = logits.shape[:2]
+    hw = logits.numel() // (n * c)
+    d = torch.empty_like(logits)
+    check(L.lib().pcuda_dice_labels_bwd(logits.data_ptr(), labels.data_ptr(), 1 if labels.dtype == torch.int64 else 0, n, c,
+                                        hw, _ptr(gout), d.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "dice_labels_bwd")
+    return d
+
+
 def bce_const_fwd(x, label, want_acc=False):
     _req(x)
     x = x.contiguous()

@@ -49,6 +49,9 @@ class TrainCfg:
     Tetpls: bool = False             # -Tetpls: target entropy mean added to the adversarial loss (:245-247)
     d4aux: bool = False              # -d4aux: point head trained (and its target loss reported) without d4 (:220,248,256)
     gen_sgd: bool = False            # -sgd: SGD(momentum .95, weight decay 5e-4) for the segmenter (:453-459)
+    # -dice ("use dice loss instead of jaccard loss"; parsed by both scripts, read by neither): "" Jaccard, "class" the
+    # per-class Dice term in its place, "sample" the per-sample one (utils/loss.py; this build's own rule)
+    dice: str = ""
 
 
 class AdversarialTrainer:
@@ -172,7 +175,7 @@ class AdversarialTrainer:
         # 1. supervised pass on the source batch (train_mscmrseg.py:200-213)
         o_s, _, vert_s = self.gen(img_a)
         self._mark("fwd_src.end")
-        l_main, l_jac = L.seg_loss(o_s, mask_a_u8, mode)
+        l_main, l_jac = L.seg_loss(o_s, mask_a_u8, mode, L.overlap_for(c.dice))
         seeds_t, seeds_g = [l_main, l_jac], [one, one]
         aux = c.d4aux and not ms
         pre_s = None
@@ -192,7 +195,9 @@ class AdversarialTrainer:
             out["ver_s_loss"] = l_pt.detach()
             seeds_t.append(l_pt)
             seeds_g.append(self._wp)
-        out["loss_bce"], out["loss_jac"] = l_main.detach(), l_jac.detach()
+        out["loss_bce"], out["loss_jac"] = l_main.detach(), l_jac.detach()      # loss_jac: the overlap term, whichever it is
+        if c.dice:
+            out["loss_dice"] = out["loss_jac"]
         # 2. (forward half) adversarial pass on the target batch (:218-241).  The reference runs the source batch's
         # backward pass first; nothing in it feeds the target forward (weights change only in the optimisers, BatchNorm's
         # running statistics are updated by the forward passes, in this same order), so the forward goes first and

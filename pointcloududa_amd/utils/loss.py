@@ -5,6 +5,11 @@ forms the train step uses.
   signatures (loss.py:5-37, 40-76), backed by the fused kernels.
 * ``seg_loss(logits, onehot_u8, mode)``: BCE + Jaccard (train_mscmrseg.py:202-203) or the
   "double softmax" cross-entropy + Jaccard (train_mmwhs.py:212-218) in one pass each way.
+  ``overlap="dice"`` / ``"dice_sample"`` puts a Dice term in the Jaccard term's place (the scripts' ``-dice``).
+* ``dice_loss(true, logits, eps, activation, reduce)`` / ``DiceLoss(eps)``: Dice with ``jaccard_loss``'s signature, and an
+  ``nn.Module`` with the surface of the ``kornia.losses.DiceLoss()`` both scripts build and never call.  The rule is this
+  build's own (include/pcuda_hip.h): parity with any kornia version is unpinned, kornia's ``+ eps`` on its one-hot tensor is
+  not reproduced.
 * ``entropy_map(logits, mode, normalise)``: -p log(p + 1e-7) [/ log C] (train_mscmrseg.py:222;
   train_mmwhs.py:224,242), optionally also returning p.
 * ``bce_logits_const(d_out, label, weight)``: weight * BCE-with-logits against a constant map
@@ -41,9 +46,46 @@ class _SegLossFn(torch.autograd.Function):
         return d, None, None
 
 
-def seg_loss(logits, onehot_u8, mode="sigmoid"):
-    """-> (bce_or_ce, jaccard) scalars.  onehot_u8: uint8 one-hot [B,C,H,W] (utils.py:25-29 layout)."""
-    return _SegLossFn.apply(logits, onehot_u8, mode)
+class _SegLossOvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, onehot, mode, overlap, eps):
+        logits = logits.contiguous()
+        out2, ws = K.seg_loss_ov_fwd(logits, onehot, mode, overlap, eps)
+        ctx.logits, ctx.onehot, ctx.mode, ctx.overlap, ctx.ws = logits, onehot, mode, overlap, ws
+        ctx.set_materialize_grads(False)
+        return out2[0], out2[1]
+
+    @staticmethod
+    def backward(ctx, g_main, g_ov):
+        dev = ctx.logits.device
+        g_main = _zero(dev) if g_main is None else g_main.contiguous()
+        g_ov = _zero(dev) if g_ov is None else g_ov.contiguous()
+        d = K.seg_loss_ov_bwd(ctx.logits, ctx.onehot, ctx.mode, ctx.overlap, ctx.ws, g_main, g_ov)
+        return d, None, None, None, None
+
+
+# eps of the fused Dice terms: per class the fused Jaccard's, per sample kornia.losses.DiceLoss's default
+_OVERLAP_EPS = {"dice": 1e-7, "dice_sample": 1e-6}
+
+
+def overlap_for(dice):
+    """the ``dice`` setting of the train step and the validation functions ("" | "class" | "sample") -> ``seg_loss``'s overlap"""
+    names = {"": "jaccard", "class": "dice", "sample": "dice_sample"}
+    if dice not in names:
+        raise ValueError("dice %r is none of '', 'class', 'sample'" % (dice,))
+    return names[dice]
+
+
+def seg_loss(logits, onehot_u8, mode="sigmoid", overlap="jaccard"):
+    """-> (bce_or_ce, overlap term) scalars.  onehot_u8: uint8 one-hot [B,C,H,W] (utils.py:25-29 layout).  ``overlap``:
+    "jaccard" (what the reference trains with), "dice" (per class, the Jaccard term's twin: 1 - mean_c 2 I_c / (S_c + 1e-7))
+    or "dice_sample" (per sample, kornia's documented formula: mean_n (1 - 2 I_n / (S_n + 1e-6))); the Dice rules are this
+    build's own."""
+    if overlap == "jaccard":
+        return _SegLossFn.apply(logits, onehot_u8, mode)
+    if overlap not in _OVERLAP_EPS:
+        raise ValueError("seg_loss: overlap %r is none of 'jaccard', 'dice', 'dice_sample'" % (overlap,))
+    return _SegLossOvFn.apply(logits, onehot_u8, mode, overlap, _OVERLAP_EPS[overlap])
 
 
 class _JaccardFn(torch.autograd.Function):
@@ -79,6 +121,92 @@ def jaccard_loss(true, logits, eps=1e-7, activation=True):
     else:
         probas = logits
     return _JaccardFn.apply(probas, true, float(eps))
+
+
+class _DiceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, probs, true, eps, reduce):
+        loss, ws, truth = K.dice_fwd(probs, true, eps, reduce)
+        ctx.truth, ctx.ws, ctx.reduce, ctx.shape = truth, ws, reduce, tuple(probs.shape)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None
+        return K.dice_bwd(ctx.truth, ctx.shape, ctx.reduce, ctx.ws, gout.contiguous()), None, None, None
+
+
+def dice_loss(true, logits, eps=1e-7, activation=True, reduce="class"):
+    """Dice with ``jaccard_loss``'s signature and branches: ``logits`` [B,C,H,W] go through a softmax over the channels
+    (``activation=True``) or already are probabilities; C == 1 pairs [sigmoid, 1 - sigmoid] with ``true`` broadcast over both
+    channels, as ``jaccard_loss`` does; ``true``: one-hot [B,C,H,W] (float or uint8).  ``reduce="class"``:
+    1 - mean_c 2 I_c / (S_c + eps) with the sums over (batch, pixels); ``"sample"``: mean_n (1 - 2 I_n / (S_n + eps)) with
+    the sums over (classes, pixels).  This build's own rule (the reference never evaluates a Dice loss).  Differentiable
+    w.r.t. ``logits``."""
+    if reduce not in ("class", "sample"):
+        raise ValueError("dice_loss: reduce %r is neither 'class' nor 'sample'" % (reduce,))
+    num_classes = logits.shape[1]
+    if num_classes == 1:
+        pos = entropy_map(logits, "sigmoid", False, want_prob=True)[1]
+        probas = torch.cat([pos, 1 - pos], dim=1)
+        return _DiceFn.apply(probas, true.float().expand_as(probas).contiguous(), float(eps), reduce)
+    if activation:
+        probas = entropy_map(logits, "softmax", False, want_prob=True)[1]
+    else:
+        probas = logits
+    return _DiceFn.apply(probas, true, float(eps), reduce)
+
+
+class _DiceLabelsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, eps):
+        logits = logits.contiguous()
+        loss, ws, labels, bad = K.dice_labels_fwd(logits, labels, eps)
+        ctx.logits, ctx.labels, ctx.ws = logits, labels, ws
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(bad)
+        return loss, bad
+
+    @staticmethod
+    def backward(ctx, gout, gbad=None):
+        if gout is None:
+            return None, None, None
+        return K.dice_labels_bwd(ctx.logits, ctx.labels, ctx.ws, gout.contiguous()), None, None
+
+
+class DiceLoss(torch.nn.Module):
+    """``kornia.losses.DiceLoss``'s surface (what both scripts build into ``dic_loss``): ``forward(input, target)`` with
+    fp32 logits [B,C,H,W] and int64 or uint8 labels [B,H,W] -> mean_n (1 - 2 I_n / (S_n + eps)), I_n = sum p y,
+    S_n = sum (p + y) over (classes, pixels), p = softmax(input) over the channels.  The softmax runs inside the kernel and
+    no one-hot tensor is written.  This build's own rule: parity with any kornia version is unpinned and kornia's ``+ eps``
+    on its one-hot tensor is not reproduced.  A label outside [0, C) belongs to no class and is counted on the device
+    (``self.bad_labels`` after a call); ``check=True`` reads that counter (one synchronisation) and raises ValueError."""
+
+    def __init__(self, eps: float = 1e-6, check: bool = False) -> None:
+        super().__init__()
+        self.eps, self.check, self.bad_labels = float(eps), bool(check), None
+
+    def forward(self, input, target):       # noqa: A002 -- kornia's argument names
+        if not torch.is_tensor(input) or not torch.is_tensor(target):
+            raise TypeError("DiceLoss: input and target are tensors")
+        if input.dim() != 4:
+            raise ValueError("DiceLoss: input is [B,C,H,W], got %r" % (tuple(input.shape),))
+        if target.dim() != 3:
+            raise ValueError("DiceLoss: target is [B,H,W], got %r" % (tuple(target.shape),))
+        if input.shape[0] != target.shape[0] or input.shape[-2:] != target.shape[-2:]:
+            raise ValueError("DiceLoss: input %r and target %r differ in batch or spatial size"
+                             % (tuple(input.shape), tuple(target.shape)))
+        if input.device != target.device:
+            raise ValueError("DiceLoss: input on %s, target on %s" % (input.device, target.device))
+        loss, bad = _DiceLabelsFn.apply(input, target, self.eps)
+        self.bad_labels = bad
+        if self.check:
+            nbad = int(bad.item())
+            if nbad:
+                raise ValueError("DiceLoss: %d labels outside [0, %d)" % (nbad, input.shape[1]))
+        return loss
 
 
 class _EntropyFn(torch.autograd.Function):

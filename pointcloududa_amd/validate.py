@@ -41,16 +41,18 @@ def predict_labels(seg_model, x: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def valid_batch(seg_model, x: torch.Tensor, y_onehot_u8: torch.Tensor, z: Optional[torch.Tensor] = None,
-                d4: bool = True, variant: str = "mscmrseg", softmax: bool = True, hd: bool = False) -> Dict[str, torch.Tensor]:
+                d4: bool = True, variant: str = "mscmrseg", softmax: bool = True, hd: bool = False,
+                dice: str = "") -> Dict[str, torch.Tensor]:
     """One iteration of the reference's validation loop; ``seg_model`` must be in eval mode.  Returns device scalars.
     ``variant="mscmrseg"`` (``train_mscmrseg.py:67-92``): loss = BCE + Jaccard + point NN loss (l1 + l2 + l3), vert_loss
     (l3 or -1), dice = mean of classes 1..3.  ``variant="mmwhs"`` (``train_mmwhs.py:65-90``): l1 = double-softmax CE
     (``softmax``) or BCE, loss = l1 + l2 WITHOUT the point term (:82), dice = mean of classes 1..4 (``metrics2``).
     ``hd``: also "hd_rows", the fp64 ``surface_metrics(gt, pred)`` rows of those classes with the batch's label maps
-    taken as one [B,H,W] volume (column 1: hd, column 7: empty flags)."""
+    taken as one [B,H,W] volume (column 1: hd, column 7: empty flags).  ``dice``: "" (l2 = Jaccard), "class" or "sample":
+    the Dice term of ``TrainCfg.dice`` in its place."""
     prediction, _, vert_s = seg_model(x)
     ms = variant == "mscmrseg"
-    l1, l2 = L.seg_loss(prediction, y_onehot_u8, "sigmoid" if (ms or not softmax) else "softmax")
+    l1, l2 = L.seg_loss(prediction, y_onehot_u8, "sigmoid" if (ms or not softmax) else "softmax", L.overlap_for(dice))
     loss = l1 + l2
     if d4 and vert_s is not None and z is not None:
         vert = L.batch_NN_loss(vert_s, z)
@@ -68,7 +70,7 @@ def valid_batch(seg_model, x: torch.Tensor, y_onehot_u8: torch.Tensor, z: Option
 
 
 def valid_model_with_one_dataset(seg_model, batches: Iterable, d4: bool = True, variant: str = "mscmrseg",
-                                 softmax: bool = True, hd: bool = False) -> Dict[str, float]:
+                                 softmax: bool = True, hd: bool = False, dice: str = "") -> Dict[str, float]:
     """``train_mscmrseg.py:53-99``: means over the batches of dice / loss / valid_vert_loss.  ``batches`` yields
     ``(x, y_onehot_u8, z)`` device tensors.  ``hd=True`` adds "hd": the mean over the batches of the mean over the
     classes of medpy ``hd(gt, pred)``; a class empty on either side of any batch raises medpy's RuntimeError at the
@@ -79,7 +81,7 @@ def valid_model_with_one_dataset(seg_model, batches: Iterable, d4: bool = True, 
     rows = []
     try:
         for x, y, z in batches:
-            r = valid_batch(seg_model, x, y, z, d4, variant, softmax, hd)
+            r = valid_batch(seg_model, x, y, z, d4, variant, softmax, hd, dice)
             for k in acc:
                 acc[k].append(r[k])
             if hd:
