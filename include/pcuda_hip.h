@@ -1020,6 +1020,46 @@ int pcuda_adam_step_dev(float* p, const float* g, float* m, float* v, long long 
 int pcuda_sgd_step(float* p, const float* g, float* mom, long long numel, float lr, float momentum,
                    float weight_decay, int first_step, float grad_scale, pcuda_stream_t s);
 
+/* guarded steps: gradient-norm clipping and non-finite skip decided on the device (no host round trip, so a captured
+ * graph of the step replays the decision with the gradient it finds).
+ *
+ * The guard record is 8 four-byte words of device memory owned by the caller, zeroed once:
+ *   [0] float norm     global L2 norm of g * grad_scale over the ranges
+ *   [1] float coef     max_norm > 0 ? min(1, max_norm / (norm + 1e-6f)) : 1   (fp32; a NaN norm gives a NaN coef, as
+ *                      torch.nn.utils.clip_grad_norm_ does)
+ *   [2] int   finite   isfinite(norm): a sum that overflows fp32 counts as non-finite
+ *   [3] int   skipped  cumulative: calls that decided "skip"   (skip_nonfinite != 0 and finite == 0)
+ *   [4] int   applied  cumulative: all other calls
+ *   [5] int   skip     this call's decision, 0 or 1
+ *   [6..7]             reserved
+ *
+ * pcuda_grad_norm: `ranges` is HOST memory, nranges x (offset, numel) in elements of g, 1 <= nranges <=
+ * PCUDA_GUARD_MAX_RANGES, numel >= 0; a range may start at any element, elements outside the ranges are never read.
+ * x = g[i] * grad_scale in fp32, x * x accumulated in double in a fixed order (lane, wave, workgroup partial; a second
+ * one-workgroup launch sums the partials per range in a fixed order and writes the record): no atomics, the same bits on
+ * every call.  norm = (float)sqrt(total).  range_sumsq (device, nranges doubles; may be NULL) receives each range's sum.
+ * workspace: PCUDA_GRAD_NORM_WORKSPACE_BYTES of device memory, 8-byte aligned. */
+#define PCUDA_GUARD_MAX_RANGES 16
+#define PCUDA_GUARD_RECORD_BYTES 32
+#define PCUDA_GRAD_NORM_WORKSPACE_BYTES 16384
+int pcuda_grad_norm(const float* g, const long long* ranges, int nranges, float grad_scale, float max_norm,
+                    int skip_nonfinite, void* record, double* range_sumsq, void* workspace, size_t workspace_bytes,
+                    pcuda_stream_t s);
+/* pcuda_adam_step_dev / pcuda_sgd_step with gi = (g[i] * grad_scale) * record.coef (two rounded fp32 products; coef == 1
+ * gives the unguarded kernels' bits).  With skip_nonfinite != 0 and record.finite == 0 nothing is stored: p, m, v, mom
+ * keep their bits, *step_dev is not incremented (the conditional increment takes the place of the unconditional one),
+ * *init_dev is not set.  With skip_nonfinite == 0 a non-finite norm propagates as clip_grad_norm_(error_if_nonfinite=
+ * False) followed by the step does.
+ * SGD: *init_dev (device int32) is "the momentum buffer is initialised" (torch.optim.SGD's first step copies the gradient
+ * into it); with mark_init != 0 it is set behind this call's update when the step is applied -- pass 0 for all but the last
+ * of the contiguous ranges of one step.  init_dev may be NULL when momentum == 0. */
+int pcuda_adam_step_guarded(float* p, const float* g, float* m, float* v, long long numel, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, int* step_dev, float grad_scale,
+                            const void* record, int skip_nonfinite, pcuda_stream_t s);
+int pcuda_sgd_step_guarded(float* p, const float* g, float* mom, long long numel, float lr, float momentum,
+                           float weight_decay, int* init_dev, int mark_init, float grad_scale, const void* record,
+                           int skip_nonfinite, pcuda_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

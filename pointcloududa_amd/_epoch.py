@@ -262,6 +262,13 @@ def _trainer_for(model_gen, model_dis1, model_dis2, model_dis4, opts, args, vari
     for k in ("w1", "w2", "w4"):
         setattr(tr.cfg, k, float(getattr(args, k, getattr(tr.cfg, k))))
     tr.cfg.dice = _dice_from(args)           # (not part of the cache key above)
+    # guarded optimiser steps: args.clip / args.clip_d (max gradient norm of the segmenter / of each discriminator, 0 = off)
+    # and args.skip_nonfinite, set on adopted optimisers too.  A namespace with none of the three leaves a fused optimiser
+    # the caller built with its own guard as it is.
+    if any(hasattr(args, k) for k in ("clip", "clip_d", "skip_nonfinite")) or tr.cfg.clip_gen or tr.cfg.clip_dis or tr.cfg.skip_nonfinite:
+        tr.cfg.clip_gen, tr.cfg.clip_dis = float(getattr(args, "clip", 0.0) or 0.0), float(getattr(args, "clip_d", 0.0) or 0.0)
+        tr.cfg.skip_nonfinite = bool(getattr(args, "skip_nonfinite", False))
+        tr.apply_guard_cfg()
     return tr
 
 
@@ -303,8 +310,17 @@ def train_epoch(variant, args, model_gen, model_dis2, model_dis4, model_dis1=Non
     res: Dict[str, float] = {}
     if steps:
         keys = sorted(acc)
-        means = torch.stack([torch.stack([t.float() for t in acc[k]]).mean() for k in keys]).tolist()     # ONE sync per epoch
+        rows = [torch.stack([t.float() for t in acc[k]]).mean() for k in keys]
+        guard = [k for k in keys if k.startswith("skipped_")]
+        if guard:      # steps in which any guarded optimiser skipped its update
+            rows.append(torch.stack([torch.stack([t.float() for t in acc[k]]) for k in guard]).amax(0).sum())
+        means = torch.stack(rows).tolist()                               # ONE sync per epoch
         m = dict(zip(keys, means))
+        if guard:
+            res["skipped_steps"] = means[-1]
+        for k in keys:
+            if k.startswith(("grad_norm_", "skipped_")):
+                res[k] = m[k]
         res["seg_loss"] = m["loss_bce"] + m["loss_jac"]                  # mean of per-step (bce + jaccard).item(), :211
         for k in _MEAN_KEYS:
             if k in m:

@@ -203,6 +203,9 @@ _PROTOS = {
     "pcuda_adam_step": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "pcuda_adam_step_dev": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp]),
     "pcuda_sgd_step": (i32, [vp, vp, vp, i64, f32, f32, f32, i32, f32, vp]),
+    "pcuda_grad_norm": (i32, [vp, C.POINTER(i64), i32, f32, f32, i32, vp, vp, vp, sz, vp]),
+    "pcuda_adam_step_guarded": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp]),
+    "pcuda_sgd_step_guarded": (i32, [vp, vp, vp, i64, f32, f32, f32, vp, i32, f32, vp, i32, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())
@@ -211,6 +214,7 @@ _lib = None
 
 PCUDA_E_UNSUPPORTED = -2      # include/pcuda_hip.h
 PCUDA_ABI_VERSION = 5         # include/pcuda_hip.h: the header this binding was written against
+GUARD_MAX_RANGES, GUARD_RECORD_WORDS, GRAD_NORM_WORKSPACE_BYTES = 16, 8, 16384      # PCUDA_GUARD_* / PCUDA_GRAD_NORM_*
 
 
 def lib():

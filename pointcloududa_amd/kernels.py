@@ -1864,6 +1864,51 @@ def sgd_step(p, g, mom, lr, momentum, weight_decay, first_step, grad_scale=1.0):
                                  1 if first_step else 0, grad_scale, _stream()), "sgd_step")
 
 
+def guard_record(device):
+    """A zeroed guard record (``pcuda_grad_norm``): int32 words; [0] norm and [1] coef are fp32 (``.view(torch.float32)``),
+    [2] finite, [3] skipped and [4] applied (cumulative), [5] this step's decision."""
+    return torch.zeros(L.GUARD_RECORD_WORDS, dtype=torch.int32, device=device)
+
+
+def grad_norm(g, ranges, grad_scale, max_norm, skip_nonfinite, record, range_sumsq=None, workspace=None):
+    """Global L2 norm of ``g * grad_scale`` over ``ranges`` (``(offset, numel)`` pairs in elements of the flat fp32 buffer
+    ``g``) into the device ``record``, with the clip coefficient for ``max_norm`` (<= 0: none) and the skip decision; each
+    range's own sum of squares goes to the float64 tensor ``range_sumsq`` when given.  Two launches, no atomics."""
+    _req(g)
+    _req(record, torch.int32)
+    ranges = [(int(o), int(n)) for o, n in ranges]
+    if record.numel() < L.GUARD_RECORD_WORDS or not record.is_contiguous() or not g.is_contiguous():
+        raise ValueError("grad_norm: the record holds %d int32 words; flat contiguous buffers only" % L.GUARD_RECORD_WORDS)
+    if any(o < 0 or n < 0 or o + n > g.numel() for o, n in ranges):
+        raise ValueError("grad_norm: a range lies outside the buffer")
+    if range_sumsq is not None:
+        _req(range_sumsq, torch.float64)
+        if range_sumsq.numel() < len(ranges) or not range_sumsq.is_contiguous():
+            raise ValueError("grad_norm: range_sumsq holds one float64 per range")
+    if workspace is None:
+        workspace = torch.empty(L.GRAD_NORM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=g.device)
+    arr = (C.c_longlong * (2 * len(ranges)))(*[x for r in ranges for x in r])
+    check(L.lib().pcuda_grad_norm(g.data_ptr(), arr, len(ranges), grad_scale, max_norm, 1 if skip_nonfinite else 0,
+                                  record.data_ptr(), _ptr(range_sumsq), workspace.data_ptr(),
+                                  workspace.numel() * workspace.element_size(), _stream()), "grad_norm")
+
+
+def adam_step_guarded(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_t, record, skip_nonfinite, grad_scale=1.0):
+    """``adam_step_dev`` with the gradient scaled by the record's clip coefficient; with ``skip_nonfinite`` and a non-finite
+    norm in the record nothing is stored and ``step_t`` stays."""
+    check(L.lib().pcuda_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1,
+                                          beta2, eps, weight_decay, step_t.data_ptr(), grad_scale, record.data_ptr(),
+                                          1 if skip_nonfinite else 0, _stream()), "adam_step_guarded")
+
+
+def sgd_step_guarded(p, g, mom, lr, momentum, weight_decay, init_t, mark_init, record, skip_nonfinite, grad_scale=1.0):
+    """``sgd_step`` with the clip coefficient of the record and "momentum buffer initialised" in the int32 device tensor
+    ``init_t`` (set behind the update when ``mark_init`` and the step is applied)."""
+    check(L.lib().pcuda_sgd_step_guarded(p.data_ptr(), g.data_ptr(), _ptr(mom), p.numel(), lr, momentum, weight_decay,
+                                         _ptr(init_t), 1 if mark_init else 0, grad_scale, record.data_ptr(),
+                                         1 if skip_nonfinite else 0, _stream()), "sgd_step_guarded")
+
+
 # ------------------------------------------------------------------------------------------
 # profiling
 # ------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ from typing import Optional
 import torch
 from torch import nn
 
+from . import _lib
 from . import kernels as K
 
 _ALIGN = 64   # elements: every parameter starts on a 256-B boundary
@@ -85,6 +86,93 @@ class _FlatOptimizer:
     def zero_grad(self):
         self.g.zero_()
 
+    # ---- guarded steps: clip by the global gradient norm / skip a non-finite gradient, decided on the device
+    guard = None          # the device record (kernels.guard_record); allocated only when a guard is on
+    max_grad_norm, skip_nonfinite = 0.0, False
+
+    @property
+    def guarded(self) -> bool:
+        return self.max_grad_norm > 0.0 or self.skip_nonfinite
+
+    def set_guard(self, max_grad_norm: float = 0.0, skip_nonfinite: bool = False):
+        """``max_grad_norm`` > 0: the step scales the gradient by ``min(1, max_grad_norm / (norm + 1e-6))``, torch's
+        ``clip_grad_norm_``; ``skip_nonfinite``: a step whose gradient norm is not finite changes nothing.  Both off (the
+        default): ``step`` issues the unguarded kernels and no guard state exists.  Not to be changed under a captured
+        graph of the step (the choice of kernels is part of the capture)."""
+        was = self.guarded
+        self.max_grad_norm, self.skip_nonfinite = float(max_grad_norm), bool(skip_nonfinite)
+        if self.guarded and not was and self.guard is not None:
+            self._guard_state()       # unguarded steps may have run in between
+        if self.guarded and self.guard is None:
+            self.guard = K.guard_record(self.p.device)
+            self._norm_ws = torch.empty(_lib.GRAD_NORM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=self.p.device)
+            self._norm_ranges, self._norm_groups = self._group_ranges()
+            self._range_sumsq = torch.zeros(len(self._norm_ranges), dtype=torch.float64, device=self.p.device)
+            self._guard_state()
+
+    def _guard_state(self):
+        """further device state of the guarded step (FusedSGD: "momentum buffer initialised")"""
+
+    def _update_ranges(self):
+        """(lo, hi) pieces of the flat buffers the step updates"""
+        return [(0, self.p.numel())]
+
+    def _group_ranges(self):
+        """The updated pieces cut at the boundaries of the module's top-level children (``encoder.``, ``decoder.``, ...):
+        the ranges of the norm launch, so that it leaves each group's own sum of squares next to the total.  Falls back to
+        the uncut pieces when there would be more than the launch takes."""
+        cuts, off, last = [], 0, None
+        for name, p in self.module.named_parameters():
+            top = name.split(".")[0] + "."
+            if top != last:
+                cuts.append((off, top))
+                last = top
+            off += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+        cuts.append((off, None))
+        ranges, groups = [], []
+        for lo, hi in self._update_ranges():
+            for (c0, top), (c1, _) in zip(cuts[:-1], cuts[1:]):
+                a, b = max(lo, c0), min(hi, c1)
+                if b > a:
+                    ranges.append((a, b - a))
+                    groups.append(top)
+        if len(ranges) > _lib.GUARD_MAX_RANGES:
+            ranges, groups = [(lo, hi - lo) for lo, hi in self._update_ranges()], [None] * len(self._update_ranges())
+        return ranges, groups
+
+    def _norm(self, grad_scale: float):
+        K.grad_norm(self.g, self._norm_ranges, grad_scale, self.max_grad_norm, self.skip_nonfinite, self.guard,
+                    self._range_sumsq, self._norm_ws)
+
+    @property
+    def grad_norm(self):
+        """0-dim fp32 view of the record: the last guarded step's global norm of ``g * grad_scale``"""
+        return self.guard[:1].view(torch.float32)[0]
+
+    @property
+    def clip_coef(self):
+        return self.guard[1:2].view(torch.float32)[0]
+
+    @property
+    def skipped(self):
+        """0-dim int32 view of the record: guarded steps skipped so far"""
+        return self.guard[3]
+
+    def grad_norms(self, prefixes):
+        """Sums of squares (float64 device tensor, one per prefix) of the last guarded step's scaled gradient over the
+        parameters whose names start with each prefix -- whole top-level groups (``"encoder."``, ``"decoder."``, ...), read
+        from the ranges of the same launch that produced ``grad_norm``.  No transfer."""
+        if self.guard is None:
+            raise RuntimeError("grad_norms: this optimiser runs unguarded (max_grad_norm / skip_nonfinite are off)")
+        rows = []
+        for pre in prefixes:
+            hit = [i for i, g_ in enumerate(self._norm_groups) if g_ is not None and g_.startswith(pre)]
+            if not hit or any(g_ is not None and pre.startswith(g_) and pre != g_ for g_ in self._norm_groups):
+                raise ValueError("grad_norms: %r is not a top-level parameter group of this module (%s)"
+                                 % (pre, ", ".join(sorted({g_ for g_ in self._norm_groups if g_}))))
+            rows.append(self._range_sumsq[hit].sum())
+        return torch.stack(rows)
+
     # ---- torch.optim-format state (what the reference's checkpoints hold: callbacks.py:61-94)
     def _slices(self):
         """(offset, numel, shape) of every parameter inside the flat buffers, in module.parameters() order --
@@ -141,7 +229,8 @@ class _FlatOptimizer:
 
 
 class FusedAdam(_FlatOptimizer):
-    def __init__(self, module, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, skip_prefixes=None):
+    def __init__(self, module, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, skip_prefixes=None,
+                 max_grad_norm=0.0, skip_nonfinite=False):
         super().__init__(module, lr)
         self.betas, self.eps, self.wd = betas, eps, weight_decay
         # ``skip_prefixes``: names of the parameters whose ``.grad`` stays None in the reference (torch.optim.Adam holds no
@@ -151,12 +240,18 @@ class FusedAdam(_FlatOptimizer):
         self.v = torch.zeros_like(self.p)
         # the step count lives on the device (the kernel increments it): a captured graph of the step replays right
         self.step_t = torch.zeros(1, dtype=torch.int32, device=self.p.device)
+        self.set_guard(max_grad_norm, skip_nonfinite)
 
     def step(self, grad_scale: float = 1.0):
         self.steps += 1   # host-side count of step() calls (not advanced by graph replays; see state_dict)
         self.module._wgen = getattr(self.module, "_wgen", 0) + 1   # packed conv weights are stale now
-        K.adam_step_dev(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                        self.step_t, grad_scale)
+        if self.guarded:
+            self._norm(grad_scale)      # over the whole buffer: a parameter without a gradient adds zeros
+            K.adam_step_guarded(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                self.step_t, self.guard, self.skip_nonfinite, grad_scale)
+        else:
+            K.adam_step_dev(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                            self.step_t, grad_scale)
         K.repack_owner(self.module)   # every packed conv-weight layout of the network, one launch behind the update
 
     def state_dict(self):
@@ -205,7 +300,8 @@ class FusedAdam(_FlatOptimizer):
 
 
 class FusedSGD(_FlatOptimizer):
-    def __init__(self, module, lr=2.5e-5, momentum=0.99, weight_decay=0.0005, skip_prefixes=()):
+    def __init__(self, module, lr=2.5e-5, momentum=0.99, weight_decay=0.0005, skip_prefixes=(), max_grad_norm=0.0,
+                 skip_nonfinite=False):
         super().__init__(module, lr)
         self.momentum, self.wd = momentum, weight_decay
         self.buf = torch.zeros_like(self.p) if momentum != 0 else None
@@ -224,12 +320,31 @@ class FusedSGD(_FlatOptimizer):
                 off += n
             if off > lo:
                 self.ranges.append((lo, off))
+        self.set_guard(max_grad_norm, skip_nonfinite)
+
+    def _update_ranges(self):
+        return list(self.ranges)
+
+    def _guard_state(self):
+        # "the momentum buffer is initialised", on the device: a skipped first step must not consume the initialisation
+        # and a replayed graph cannot re-read ``self.steps``.  Continues from the host flag the unguarded steps kept.
+        if getattr(self, "init_t", None) is None:
+            self.init_t = torch.zeros(1, dtype=torch.int32, device=self.p.device)
+        if self.steps > 0:
+            self.init_t.fill_(1)
 
     def step(self, grad_scale: float = 1.0):
         self.module._wgen = getattr(self.module, "_wgen", 0) + 1
-        for lo, hi in self.ranges:
-            K.sgd_step(self.p[lo:hi], self.g[lo:hi], None if self.buf is None else self.buf[lo:hi], self.lr, self.momentum,
-                       self.wd, self.steps == 0, grad_scale)
+        if self.guarded:
+            self._norm(grad_scale)      # one call over the updated ranges only
+            for i, (lo, hi) in enumerate(self.ranges):
+                K.sgd_step_guarded(self.p[lo:hi], self.g[lo:hi], None if self.buf is None else self.buf[lo:hi], self.lr,
+                                   self.momentum, self.wd, self.init_t, i == len(self.ranges) - 1, self.guard,
+                                   self.skip_nonfinite, grad_scale)
+        else:
+            for lo, hi in self.ranges:
+                K.sgd_step(self.p[lo:hi], self.g[lo:hi], None if self.buf is None else self.buf[lo:hi], self.lr,
+                           self.momentum, self.wd, self.steps == 0, grad_scale)
         self.steps += 1
         K.repack_owner(self.module)
 
@@ -239,7 +354,9 @@ class FusedSGD(_FlatOptimizer):
     def torch_state_dict(self):
         """The state in ``torch.optim.SGD.state_dict()`` form."""
         state = {}
-        if self.buf is not None and self.steps > 0:
+        # guarded: whether a step has been APPLIED is on the device (a run of skipped steps leaves the buffer unwritten)
+        initialised = self.steps > 0 if self.guard is None else bool(int(self.init_t.item()))
+        if self.buf is not None and initialised:
             for i, (o, n, shp) in enumerate(self._slices()):
                 if not any(lo <= o and o + n <= hi for lo, hi in self.ranges):
                     continue          # a skipped parameter (.grad is None in the reference): torch.optim.SGD holds no state for it
@@ -262,3 +379,5 @@ class FusedSGD(_FlatOptimizer):
                     self.buf[o:o + n].copy_(st["momentum_buffer"].reshape(-1))
                     loaded = True
         self.steps = 1 if loaded else 0   # "first step" only decides whether the momentum buffer is initialised
+        if self.guard is not None:
+            self.init_t.fill_(self.steps)

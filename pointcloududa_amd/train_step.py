@@ -52,6 +52,12 @@ class TrainCfg:
     # -dice ("use dice loss instead of jaccard loss"; parsed by both scripts, read by neither): "" Jaccard, "class" the
     # per-class Dice term in its place, "sample" the per-sample one (utils/loss.py; this build's own rule)
     dice: str = ""
+    # guarded optimiser steps (optim.py; this build's own, the reference has neither): clip the segmenter's / each
+    # discriminator's gradient by its global L2 norm (0: off), and skip an update whose gradient norm is not finite --
+    # both decided on the device, inside the step
+    clip_gen: float = 0.0
+    clip_dis: float = 0.0
+    skip_nonfinite: bool = False
 
 
 class AdversarialTrainer:
@@ -78,6 +84,7 @@ class AdversarialTrainer:
         self.opt_d1 = mk(self.dis1, c.d1lr) if self.dis1 is not None else None
         self.opt_d2 = mk(self.dis2, c.d2lr) if self.dis2 is not None else None
         self.opt_d4 = mk(self.dis4, c.d4lr) if self.dis4 is not None else None
+        self.apply_guard_cfg()
         dev = next(self.gen.parameters()).device
         self._one = torch.ones((), dtype=torch.float32, device=dev)
         self._wp = torch.full((), float(c.wp), dtype=torch.float32, device=dev)
@@ -117,7 +124,8 @@ class AdversarialTrainer:
         import torch.distributed as dist
         for opt in [self.opt_gen] + self._d_opts():
             bufs = [opt.p] + [t for t in (getattr(opt, "m", None), getattr(opt, "v", None), getattr(opt, "buf", None),
-                                          getattr(opt, "step_t", None)) if t is not None]
+                                          getattr(opt, "step_t", None), getattr(opt, "guard", None),
+                                          getattr(opt, "init_t", None)) if t is not None]
             bufs += [b for b in opt.module.buffers() if b.numel() > 0]
             for t in bufs:
                 dist.broadcast(t, src=src, group=self.group)
@@ -130,6 +138,27 @@ class AdversarialTrainer:
             # cached by an earlier forward pass are stale on every rank but ``src``
             opt.module._wgen = getattr(opt.module, "_wgen", 0) + 1
             K.repack_owner(opt.module)
+
+    def apply_guard_cfg(self):
+        """``cfg.clip_gen`` / ``clip_dis`` / ``skip_nonfinite`` onto the optimisers as they stand (built here or adopted).
+        A captured graph of the step holds the kernels of the setting it was captured with: a change drops it."""
+        c = self.cfg
+        changed = False
+        for o, clip in [(self.opt_gen, c.clip_gen)] + [(o, c.clip_dis) for o in self._d_opts()]:
+            if (o.max_grad_norm, o.skip_nonfinite) != (float(clip), bool(c.skip_nonfinite)):
+                o.set_guard(clip, c.skip_nonfinite)
+                changed = True
+        if changed and getattr(self, "_graph", None) is not None:
+            self._graph = self._graph_b = None
+
+    def _guard_outputs(self, out):
+        """per-step guard metrics of the guarded optimisers, copied out of their records (the next step rewrites those):
+        the gradient norm the update saw and whether it skipped (0 / 1), as device scalars like every other metric"""
+        for nm, o in (("gen", self.opt_gen), ("d1", self.opt_d1), ("d2", self.opt_d2), ("d4", self.opt_d4)):
+            if o is not None and o.guarded:
+                out["grad_norm_" + nm] = o.grad_norm.clone()
+                out["skipped_" + nm] = o.guard[5].to(torch.float32)
+        return out
 
     def _dis(self):
         return [m for m in (self.dis1, self.dis2, self.dis4) if m is not None]
@@ -422,6 +451,8 @@ class AdversarialTrainer:
         if g_work is not None:      # no discriminator configured
             self.opt_gen.finish_all_reduce(g_work)
             self.opt_gen.step(g_scale)
+        if not compute_only:
+            self._guard_outputs(out)
 
     # ------------------------------------------------------------------ the same iteration as one hipGraph
     def apply_updates(self, grad_scale: float = 1.0):
@@ -474,6 +505,7 @@ class AdversarialTrainer:
                     gb = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gb, capture_error_mode="thread_local"):
                         self.apply_updates(scale)
+                        self._guard_outputs(self._gout)      # the norm kernels and their metrics belong to graph B
                     self._graph_b = gb
                 self._graph = graph
             except Exception as e:   # noqa: BLE001 -- any capture failure means: stay eager
