@@ -340,7 +340,9 @@ int pcuda_sum_all(const float* x, long long numel, double scale, float* out, voi
 /* segmentation loss: mode SIGMOID: BCE(sigmoid(o), y) + jaccard(sigmoid(o), y)
  *                    mode SOFTMAX: cross_entropy(softmax(o), argmax y) ("double softmax") + jaccard(softmax(o), y)
  * y: one-hot uint8 [n][c][hw].  out[0] = bce|ce, out[1] = jaccard.  workspace from *_workspace_size.
- * pass 1 (fwd) leaves the per-class sums in the workspace; bwd reuses them. */
+ * c = 1..8 (PCUDA_E_UNSUPPORTED above).  pass 1 (fwd) leaves the per-class sums and the coefficient pairs 1 / U_c, I_c / U_c^2
+ * in the workspace; bwd reads the pairs there.  (csrc/losses.hip: the overlap kernels of csrc/loss_device.h with the Jaccard
+ * policy; csrc/dice_loss.hip runs the same kernels with the Dice policy) */
 size_t pcuda_seg_loss_workspace_size(int n, int c, long long hw);
 int pcuda_seg_loss_fwd(const float* logits, const uint8_t* onehot, int mode, int n, int c, long long hw,
                        float* out2, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
@@ -945,7 +947,8 @@ int pcuda_jaccard_bwd(const void* truth, int truth_is_u8, int n, int c, long lon
                       float* dprobs, const void* workspace, pcuda_stream_t s);
 
 /* ------------------------------------------------------------------------------------
- * Dice loss (the -dice switch both training scripts parse and never read; csrc/dice_loss.hip)
+ * Dice loss (the -dice switch both training scripts parse and never read; csrc/dice_loss.hip: the per-class kernels are
+ * the overlap family of csrc/loss_device.h with the Dice policy, the per-sample reduction and the label-map form are its own)
  * ---------------------------------------------------------------------------------- */
 /* This build's own rule (the reference builds kornia.losses.DiceLoss() and never calls it; parity with any kornia version is
  * unpinned, and kornia's + eps on its one-hot tensor is not reproduced).  p: probabilities, y: one-hot truth,

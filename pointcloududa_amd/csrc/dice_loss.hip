@@ -7,73 +7,17 @@
 //
 // Every forward is: block partial rows (fp32) -> a fixed-order reduce in double -> the scalars and the coefficients
 // a = 1 / (S + eps), b = I / (S + eps)^2 per class or per sample, left in the workspace for the backward pass.  No floating
-// point atomics: the same bits from run to run.  A per-sample partial row belongs to ONE sample: the grid of a per-sample
-// pass is (sample, chunk) pairs laid out on the x axis (n * bps blocks; n is not bounded by a grid's y limit).
+// point atomics: the same bits from run to run.  The per-class kernels are the overlap family's (loss_device.h) with the Dice
+// policy, the ones losses.hip runs with the Jaccard policy; what is here is what only Dice has: the per-sample reduction and
+// the label-map form.  A per-sample partial row belongs to ONE sample: the grid of a per-sample pass is (sample, chunk) pairs
+// laid out on the x axis (n * bps blocks; n is not bounded by a grid's y limit).
 #include "loss_device.h"
 
-#define DICE_MAXC 16       // classes of the stand-alone forms
-#define OV_MAXC 8          // classes of the fused form (as seg_loss)
 #define OV_BLOCKS 1024     // blocks a (sample, chunk) forward pass aims at (more only where n alone exceeds it)
 #define DICE_BLOCKS 256    // block cap (per class) of the stand-alone per-class pass
-#define WS_HEAD 64         // doubles in front of every workspace: the reduced sums
 
-// ---------------------------------------------------------------------------- shared pieces
-// the block's sum of every accumulator -> one partial row (waves in a fixed order)
-template <int NACC>
-__device__ __forceinline__ void block_store_row(const float (&acc)[NACC], float* __restrict__ row) {
-  __shared__ float sh[4][NACC];
-#pragma unroll
-  for (int k = 0; k < NACC; ++k) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC)
-    row[threadIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
-
-// sum over the 256 threads of a block, fixed order; every thread gets it
-__device__ __forceinline__ double block_tree_sum(double s, double* red) {
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// per-class reduce of `nblocks` partial rows of nacc = 2 c + off floats: [main (off = 1)] [I_0..I_{c-1}] [S_0..S_{c-1}]
-//   sums[a] = every accumulator in double; coef[2k], coef[2k+1] = a_k, b_k; out = [main / numel_main,] 1 - mean_c 2I/(S+eps)
-__global__ __launch_bounds__(256) void dice_class_final_kernel(const float* __restrict__ part, int nblocks, int c, int off,
-                                                              double numel_main, double eps, double* __restrict__ sums,
-                                                              float* __restrict__ coef, float* __restrict__ out) {
-  __shared__ double sh[2 * DICE_MAXC + 1];
-  __shared__ double red[256];
-  const int nacc = 2 * c + off;
-  for (int a = 0; a < nacc; ++a) {
-    double s = 0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) s += (double)part[(long long)b * nacc + a];
-    const double tot = block_tree_sum(s, red);
-    if (threadIdx.x == 0) { sums[a] = tot; sh[a] = tot; }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < c) {
-    const double I = sh[off + threadIdx.x], d = sh[off + c + threadIdx.x] + eps;
-    coef[2 * threadIdx.x] = (float)(1.0 / d);
-    coef[2 * threadIdx.x + 1] = (float)(I / (d * d));
-  }
-  if (threadIdx.x == 0) {
-    double t = 0;
-    for (int k = 0; k < c; ++k) t += 2.0 * sh[off + k] / (sh[off + c + k] + eps);
-    if (off) out[0] = (float)(sh[0] / numel_main);
-    out[off] = (float)(1.0 - t / c);
-  }
-}
-
-// per-sample reduce, stage 1: one wave per sample over its bps partial rows of NACC floats: [main (NACC = 3)] [I] [S]
+// ---------------------------------------------------------------------------- per-sample reduce
+// stage 1: one wave per sample over its bps partial rows of NACC floats: [main (NACC = 3)] [I] [S]
 //   coef[2n], coef[2n+1] = a_n, b_n; samp[2n] = 2 I_n / (S_n + eps), samp[2n+1] = the sample's main sum
 template <int NACC>
 __global__ __launch_bounds__(256) void dice_sample_reduce_kernel(const float* __restrict__ part, int n, int bps, double eps,
@@ -91,10 +35,9 @@ __global__ __launch_bounds__(256) void dice_sample_reduce_kernel(const float* __
 #pragma unroll
   for (int k = 0; k < NACC; ++k) acc[k] = wave_sum_d(acc[k]);
   if (lane == 0) {
-    const double I = acc[NACC - 2], d = acc[NACC - 1] + eps;
-    coef[2ll * smp] = (float)(1.0 / d);
-    coef[2ll * smp + 1] = (float)(I / (d * d));
-    samp[2ll * smp] = 2.0 * I / d;
+    const double I = acc[NACC - 2], S = acc[NACC - 1];
+    overlap_coef<DiceOv>(I, S, eps, coef[2ll * smp], coef[2ll * smp + 1]);
+    samp[2ll * smp] = DiceOv::term(I, DiceOv::den(I, S, eps));
     samp[2ll * smp + 1] = NACC == 3 ? acc[0] : 0.0;
   }
 }
@@ -115,163 +58,8 @@ __global__ __launch_bounds__(256) void dice_sample_final_kernel(const double* __
   }
 }
 
-// ---------------------------------------------------------------------------- fused segmentation loss, Dice overlap
-// one pixel: the main term (BCE with the -100 clamp, or the double-softmax cross entropy: what seg_loss computes), and per
-// class pi = p * y, ps = p + y
-template <int C>
-__device__ __forceinline__ float seg_pixel(const float* __restrict__ lp, const uint8_t* __restrict__ yp, long long hw,
-                                           int mode, float (&pi)[C], float (&ps)[C]) {
-  float main = 0.f;
-  if (mode == PCUDA_ACT_SIGMOID) {
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-      const float pr = sigmoidf_(lp[k * hw]);
-      const float y = (float)yp[k * hw];
-      const float l1 = fmaxf(logf(pr), -100.f), l0 = fmaxf(logf(1.f - pr), -100.f);   // torch BCELoss clamps each log
-      main += -(y * l1 + (1.f - y) * l0);
-      pi[k] = pr * y;
-      ps[k] = pr + y;
-    }
-  } else {
-    float v[C];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < C; ++k) { v[k] = lp[k * hw]; m = fmaxf(m, v[k]); }
-    float ssum = 0.f;
-#pragma unroll
-    for (int k = 0; k < C; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
-    uint8_t best = 0;
-    float pm = -INFINITY, plabel = 0.f;
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-      const float pr = v[k] / ssum;
-      v[k] = pr;
-      const uint8_t yk = yp[k * hw];
-      if (first || yk > best) { best = yk; plabel = pr; first = false; }   // first maximum = np.argmax
-      pm = fmaxf(pm, pr);
-      pi[k] = pr * (float)yk;
-      ps[k] = pr + (float)yk;
-    }
-    float s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < C; ++k) s2 += expf(v[k] - pm);
-    main = -(plabel - pm - logf(s2));   // -log_softmax(p)[label]
-  }
-  return main;
-}
-
-// forward pass: block = (sample, chunk) = (blockIdx.x / bps, blockIdx.x % bps) walks its chunk of ITS sample's pixels (no
-// division per pixel).  Partial row per block: per sample [main, I, S], per class [main, I_0.., S_0..] (rows of different
-// samples are summed by the per-class reduce, which is what that reduction asks for)
-template <int C, bool SAMPLE>
-__global__ __launch_bounds__(256) void seg_ov_partial_kernel(const float* __restrict__ logits,
-                                                            const uint8_t* __restrict__ onehot, int mode, long long hw,
-                                                            int bps, float* __restrict__ part) {
-  constexpr int NACC = SAMPLE ? 3 : 2 * C + 1;
-  const long long n = blockIdx.x / (unsigned)bps;
-  const int j = (int)(blockIdx.x - n * bps);
-  float acc[NACC];
-#pragma unroll
-  for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-  for (long long px = j * 256ll + threadIdx.x; px < hw; px += 256ll * bps) {
-    const long long base = n * C * hw + px;
-    float pi[C], ps[C];
-    acc[0] += seg_pixel<C>(logits + base, onehot + base, hw, mode, pi, ps);
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-      acc[SAMPLE ? 1 : 1 + k] += pi[k];
-      acc[SAMPLE ? 2 : 1 + C + k] += ps[k];
-    }
-  }
-  block_store_row<NACC>(acc, part + (long long)blockIdx.x * NACC);
-}
-
-// dlogits = (g_main * d main / d p + g_ov * d dice / d p) through the sigmoid / softmax Jacobian (seg_loss_bwd_kernel's).
-// block = (sample, chunk) as in the forward pass.  coef: per class [c][2] (held in LDS) or per sample [n][2] (the block's own
-// pair, read from the workspace: n is not bounded by LDS); m = c or n
-template <bool SAMPLE>
-__global__ __launch_bounds__(256) void seg_ov_bwd_kernel(const float* __restrict__ logits,
-                                                         const uint8_t* __restrict__ onehot, int mode, int c, long long hw,
-                                                         int bps, double numel_main, const float* __restrict__ coef, int m,
-                                                         const float* __restrict__ g_main, const float* __restrict__ g_ov,
-                                                         float* __restrict__ dlogits) {
-  __shared__ float ca[OV_MAXC], cb[OV_MAXC];
-  const long long n = blockIdx.x / (unsigned)bps;
-  const int j = (int)(blockIdx.x - n * bps);
-  if (!SAMPLE) {
-    if ((int)threadIdx.x < c) { ca[threadIdx.x] = coef[2 * threadIdx.x]; cb[threadIdx.x] = coef[2 * threadIdx.x + 1]; }
-    __syncthreads();
-  }
-  const float sa = SAMPLE ? coef[2 * n] : 0.f, sb = SAMPLE ? coef[2 * n + 1] : 0.f;
-  const float gm = (g_main ? *g_main : 1.f) / (float)numel_main;
-  const float gd = (g_ov ? *g_ov : 1.f) * 2.f / (float)m;
-  for (long long px = j * 256ll + threadIdx.x; px < hw; px += 256ll * bps) {
-    const long long base = n * c * hw + px;
-    if (mode == PCUDA_ACT_SIGMOID) {
-      for (int k = 0; k < c; ++k) {
-        const float pr = sigmoidf_(logits[base + k * hw]);
-        const float y = (float)onehot[base + k * hw];
-        const float pq = pr * (1.f - pr);
-        // torch: BCE backward divides by max(p(1-p), 1e-12), sigmoid backward multiplies by p(1-p)
-        const float gb = gm * (pr - y) / fmaxf(pq, 1e-12f);
-        const float gov = -gd * (y * (SAMPLE ? sa : ca[k]) - (SAMPLE ? sb : cb[k]));
-        dlogits[base + k * hw] = (gb + gov) * pq;
-      }
-    } else {
-      float v[OV_MAXC], gp[OV_MAXC];
-      float mx = -INFINITY;
-      for (int k = 0; k < c; ++k) { v[k] = logits[base + k * hw]; mx = fmaxf(mx, v[k]); }
-      float ssum = 0.f;
-      for (int k = 0; k < c; ++k) { v[k] = expf(v[k] - mx); ssum += v[k]; }
-      int label = 0;
-      uint8_t best = 0;
-      float pm = -INFINITY;
-      for (int k = 0; k < c; ++k) {
-        v[k] = v[k] / ssum;
-        const uint8_t yk = onehot[base + k * hw];
-        if (yk > best) { best = yk; label = k; }
-        pm = fmaxf(pm, v[k]);
-      }
-      float s2 = 0.f;
-      for (int k = 0; k < c; ++k) s2 += expf(v[k] - pm);
-      float dot = 0.f;
-      for (int k = 0; k < c; ++k) {
-        const float y = (float)onehot[base + k * hw];
-        const float sm2 = expf(v[k] - pm) / s2;
-        const float g = gm * (sm2 - (k == label ? 1.f : 0.f)) - gd * (y * (SAMPLE ? sa : ca[k]) - (SAMPLE ? sb : cb[k]));
-        gp[k] = g;
-        dot += g * v[k];
-      }
-      for (int k = 0; k < c; ++k) dlogits[base + k * hw] = v[k] * (gp[k] - dot);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------- Dice on given probabilities
-// per class: as jaccard_partial_kernel (class on the grid's y axis); partial row [I_0..I_{c-1}, S_0..S_{c-1}] per x block
-__global__ __launch_bounds__(256) void dice_class_partial_kernel(const float* __restrict__ p, const float* __restrict__ tf,
-                                                                const uint8_t* __restrict__ tu, int c, long long hw,
-                                                                long long npix, float* __restrict__ part) {
-  __shared__ float sh[4][2];
-  const int k = blockIdx.y;
-  float a0 = 0.f, a1 = 0.f;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npix; i += 256ll * gridDim.x) {
-    const long long n = i / hw, px = i - n * hw;
-    const long long o = (n * c + k) * hw + px;
-    const float pr = p[o], y = tf ? tf[o] : (float)tu[o];
-    a0 += pr * y;
-    a1 += pr + y;
-  }
-  a0 = wave_sum(a0); a1 = wave_sum(a1);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6][0] = a0; sh[threadIdx.x >> 6][1] = a1; }
-  __syncthreads();
-  if (threadIdx.x < 2)
-    part[(long long)blockIdx.x * 2 * c + threadIdx.x * c + k] =
-        (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
-
-// per sample: a sample's c * hw values are contiguous (len of them); block = (sample, chunk), partial row [I, S]
+// ---------------------------------------------------------------------------- Dice on given probabilities, per sample
+// a sample's c * hw values are contiguous (len of them); block = (sample, chunk), partial row [I, S]
 __global__ __launch_bounds__(256) void dice_sample_partial_kernel(const float* __restrict__ p, const float* __restrict__ tf,
                                                                  const uint8_t* __restrict__ tu, long long len, int bps,
                                                                  float* __restrict__ part) {
@@ -285,19 +73,6 @@ __global__ __launch_bounds__(256) void dice_sample_partial_kernel(const float* _
     acc[1] += pr + y;
   }
   block_store_row<2>(acc, part + (long long)blockIdx.x * 2);
-}
-
-// dp = -(gout * 2 / m) (y a - b); the element's coefficient pair is (o / seg) % mod: (hw, c) per class, (c hw, n) per sample
-__global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__ tf, const uint8_t* __restrict__ tu,
-                                                       long long numel, long long seg, int mod, int m,
-                                                       const float* __restrict__ coef, const float* __restrict__ gout,
-                                                       float* __restrict__ dp) {
-  const float g = (gout ? *gout : 1.f) * 2.f / (float)m;
-  for (long long o = blockIdx.x * 256ll + threadIdx.x; o < numel; o += 256ll * gridDim.x) {
-    const long long q = (o / seg) % mod;
-    const float y = tf ? tf[o] : (float)tu[o];
-    dp[o] = -g * (y * coef[2 * q] - coef[2 * q + 1]);
-  }
 }
 
 // ---------------------------------------------------------------------------- Dice on logits + a label map (per sample)
@@ -318,14 +93,10 @@ __global__ __launch_bounds__(256) void dice_labels_partial_kernel(const float* _
   float acc[2] = {0.f, 0.f};
   unsigned int bad = 0;
   for (long long px = j * 256ll + threadIdx.x; px < hw; px += 256ll * bps) {
-    const float* lp = logits + n * c * hw + px;
     const long long lab = read_label(l8, l64, n * hw + px);
     const bool valid = lab >= 0 && lab < c;
-    float v[DICE_MAXC];
-    float m = -INFINITY;
-    for (int k = 0; k < c; ++k) { v[k] = lp[k * hw]; m = fmaxf(m, v[k]); }
-    float ssum = 0.f;
-    for (int k = 0; k < c; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
+    float v[LOSS_MAXC];
+    const float ssum = channel_softmax(logits + n * c * hw + px, hw, c, v);
     float pl = 0.f, psum = 0.f;
     for (int k = 0; k < c; ++k) {
       const float pr = v[k] / ssum;
@@ -345,17 +116,14 @@ __global__ __launch_bounds__(256) void dice_labels_bwd_kernel(const float* __res
                                                              const long long* __restrict__ l64, int c, long long hw,
                                                              long long npix, int nsamp, const float* __restrict__ coef,
                                                              const float* __restrict__ gout, float* __restrict__ dlogits) {
-  const float g = (gout ? *gout : 1.f) * 2.f / (float)nsamp;
+  const float g = (gout ? *gout : 1.f) * DiceOv::gscale / (float)nsamp;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npix; i += 256ll * gridDim.x) {
     const long long n = i / hw, px = i - n * hw;
     const long long base = n * c * hw + px;
     const long long lab = read_label(l8, l64, i);
     const float sa = coef[2 * n], sb = coef[2 * n + 1];
-    float v[DICE_MAXC];
-    float m = -INFINITY;
-    for (int k = 0; k < c; ++k) { v[k] = logits[base + k * hw]; m = fmaxf(m, v[k]); }
-    float ssum = 0.f;
-    for (int k = 0; k < c; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
+    float v[LOSS_MAXC];
+    const float ssum = channel_softmax(logits + base, hw, c, v);
     float dot = 0.f;
     for (int k = 0; k < c; ++k) {
       v[k] = v[k] / ssum;
@@ -368,7 +136,7 @@ __global__ __launch_bounds__(256) void dice_labels_bwd_kernel(const float* __res
 // ============================================================================ host wrappers
 namespace {
 // workspace: [WS_HEAD doubles: sums] then
-//   per class : [coef float 2 * DICE_MAXC] [partial rows float blocks * nacc]
+//   per class : [coef float 2 * LOSS_MAXC] [partial rows float blocks * nacc]
 //   per sample: [samp double 2 n] [coef float 2 n] [partial rows float n * bps * nacc]
 struct Layout {
   size_t samp, coef, part, total;
@@ -376,7 +144,7 @@ struct Layout {
 inline Layout layout_class(int blocks, int nacc) {
   Layout l;
   l.samp = l.coef = WS_HEAD * sizeof(double);
-  l.part = l.coef + 2 * DICE_MAXC * sizeof(float);
+  l.part = l.coef + 2 * LOSS_MAXC * sizeof(float);
   l.total = l.part + (size_t)blocks * nacc * sizeof(float);
   return l;
 }
@@ -388,19 +156,47 @@ inline Layout layout_sample(int n, int bps, int nacc) {
   l.total = l.part + (size_t)n * bps * nacc * sizeof(float);
   return l;
 }
-// chunks per sample of a (sample, chunk) pass over `len` values each: one block per 256 values, about `blocks` blocks in all
-inline int sample_bps(int n, long long len, int blocks = OV_BLOCKS) {
-  const long long want = (len + 255) / 256, cap = blocks / n > 1 ? blocks / n : 1;
-  return (int)(want < cap ? want : cap);
-}
 inline bool ov_known(int overlap) { return overlap == PCUDA_OV_DICE_CLASS || overlap == PCUDA_OV_DICE_SAMPLE; }
 inline Layout ov_layout(int n, int c, long long hw, int overlap) {
-  const int bps = sample_bps(n, hw);
+  const int bps = sample_bps(n, hw, OV_BLOCKS);
   return overlap == PCUDA_OV_DICE_SAMPLE ? layout_sample(n, bps, 3) : layout_class(n * bps, 2 * c + 1);
 }
 inline Layout dice_layout(int n, int c, long long hw, int reduce) {
-  return reduce == PCUDA_OV_DICE_SAMPLE ? layout_sample(n, sample_bps(n, (long long)c * hw), 2)
+  return reduce == PCUDA_OV_DICE_SAMPLE ? layout_sample(n, sample_bps(n, (long long)c * hw, OV_BLOCKS), 2)
                                         : layout_class(DICE_BLOCKS, 2 * c);
+}
+inline Layout labels_layout(int n, long long hw) { return layout_sample(n, sample_bps(n, hw, OV_BLOCKS), 2); }
+
+// the checks every entry point of the fused Dice form makes before it launches
+int ov_check(const char* what, const void* logits, const void* onehot, const void* out, int mode, int overlap, int n, int c,
+             long long hw, const void* workspace, size_t workspace_bytes) {
+  if (int rc = seg_check_args(what, logits, onehot, out, mode == PCUDA_ACT_SIGMOID || mode == PCUDA_ACT_SOFTMAX, n, c, hw))
+    return rc;
+  if (!ov_known(overlap)) PCUDA_FAIL(PCUDA_E_BADARG, "%s: unknown overlap term %d", what, overlap);
+  if (!workspace || workspace_bytes < ov_layout(n, c, hw, overlap).total)
+    PCUDA_FAIL(PCUDA_E_WORKSPACE, "%s: workspace too small", what);
+  return PCUDA_OK;
+}
+// ... and of Dice on given probabilities
+int dice_check(const char* what, const void* in, const void* truth, const void* out, int reduce, int n, int c, long long hw,
+               const void* workspace, size_t workspace_bytes) {
+  if (int rc = probs_check_args(what, in, truth, out, n, c, hw)) return rc;
+  if (!ov_known(reduce)) PCUDA_FAIL(PCUDA_E_BADARG, "%s: unknown reduction %d", what, reduce);
+  if (!workspace || workspace_bytes < dice_layout(n, c, hw, reduce).total)
+    PCUDA_FAIL(PCUDA_E_WORKSPACE, "%s: workspace too small", what);
+  return PCUDA_OK;
+}
+
+// the reduce of a per-class forward: sums, coefficient pairs and the scalars
+int launch_class_final(void* workspace, const Layout& l, int blocks, int c, int off, double numel_main, double eps, float* out,
+                       hipStream_t s) {
+  {
+    ProfScope prof(PCUDA_FAM_POINTWISE, 4.0 * blocks * (2 * c + off), s);
+    hipLaunchKernelGGL(overlap_class_final_kernel<DiceOv>, dim3(1), dim3(256), 0, s, (const float*)((char*)workspace + l.part),
+                       blocks, c, off, numel_main, eps, (double*)workspace, (float*)((char*)workspace + l.coef), out);
+  }
+  PCUDA_CHECK_LAUNCH("overlap_class_final_kernel");
+  return PCUDA_OK;
 }
 
 // the two reduce stages of a per-sample forward
@@ -436,18 +232,14 @@ extern "C" size_t pcuda_seg_loss_ov_workspace_size(int n, int c, long long hw, i
 extern "C" int pcuda_seg_loss_ov_fwd(const float* logits, const uint8_t* onehot, int mode, int overlap, double eps, int n,
                                      int c, long long hw, float* out2, void* workspace, size_t workspace_bytes,
                                      pcuda_stream_t s) {
-  if (!logits || !onehot || !out2 || n <= 0 || c <= 0 || hw <= 0 ||
-      (mode != PCUDA_ACT_SIGMOID && mode != PCUDA_ACT_SOFTMAX) || !(eps >= 0.0))
-    PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_ov_fwd: bad arguments");
-  if (!ov_known(overlap)) PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_ov_fwd: unknown overlap term %d", overlap);
-  if (c > OV_MAXC) PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "seg_loss_ov: at most %d classes (got %d)", OV_MAXC, c);
+  if (!(eps >= 0.0)) PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_ov_fwd: bad arguments");
+  if (int rc = ov_check("seg_loss_ov_fwd", logits, onehot, out2, mode, overlap, n, c, hw, workspace, workspace_bytes)) return rc;
   const Layout l = ov_layout(n, c, hw, overlap);
-  if (!workspace || workspace_bytes < l.total) PCUDA_FAIL(PCUDA_E_WORKSPACE, "seg_loss_ov_fwd: workspace too small");
   const long long npix = (long long)n * hw;
-  const double numel_main = mode == PCUDA_ACT_SIGMOID ? (double)npix * c : (double)npix;
+  const double numel_main = seg_numel_main(mode, n, c, hw);
   float* part = (float*)((char*)workspace + l.part);
   hipStream_t st = (hipStream_t)s;
-  const int bps = sample_bps(n, hw);
+  const int bps = sample_bps(n, hw, OV_BLOCKS);
   const unsigned blocks = (unsigned)n * bps;
   const bool sample = overlap == PCUDA_OV_DICE_SAMPLE;
   {
@@ -455,66 +247,51 @@ extern "C" int pcuda_seg_loss_ov_fwd(const float* logits, const uint8_t* onehot,
 #define OV_CASE(CC)                                                                                                           \
   case CC:                                                                                                                    \
     if (sample)                                                                                                               \
-      hipLaunchKernelGGL((seg_ov_partial_kernel<CC, true>), dim3(blocks), dim3(256), 0, st, logits, onehot, mode, hw, bps, part); \
+      hipLaunchKernelGGL((seg_partial_kernel<CC, true, true>), dim3(blocks), dim3(256), 0, st, logits, onehot, mode, hw, npix, bps, part); \
     else                                                                                                                      \
-      hipLaunchKernelGGL((seg_ov_partial_kernel<CC, false>), dim3(blocks), dim3(256), 0, st, logits, onehot, mode, hw, bps, part); \
+      hipLaunchKernelGGL((seg_partial_kernel<CC, true, false>), dim3(blocks), dim3(256), 0, st, logits, onehot, mode, hw, npix, bps, part); \
     break;
     switch (c) { OV_CASE(1) OV_CASE(2) OV_CASE(3) OV_CASE(4) OV_CASE(5) OV_CASE(6) OV_CASE(7) OV_CASE(8) }
 #undef OV_CASE
   }
-  PCUDA_CHECK_LAUNCH("seg_ov_partial_kernel");
+  PCUDA_CHECK_LAUNCH("seg_partial_kernel");
   if (sample) return launch_sample_reduce<3>("seg_loss_ov_fwd", workspace, l, n, bps, eps, numel_main, out2, st);
-  {
-    ProfScope prof(PCUDA_FAM_POINTWISE, 4.0 * blocks * (2 * c + 1), st);
-    hipLaunchKernelGGL(dice_class_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)blocks, c, 1, numel_main,
-                       eps, (double*)workspace, (float*)((char*)workspace + l.coef), out2);
-  }
-  PCUDA_CHECK_LAUNCH("dice_class_final_kernel");
-  return PCUDA_OK;
+  return launch_class_final(workspace, l, (int)blocks, c, 1, numel_main, eps, out2, st);
 }
 
 extern "C" int pcuda_seg_loss_ov_bwd(const float* logits, const uint8_t* onehot, int mode, int overlap, int n, int c,
                                      long long hw, const float* g_main, const float* g_ov, float* dlogits,
                                      const void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
-  if (!logits || !onehot || !dlogits || n <= 0 || c <= 0 || hw <= 0 ||
-      (mode != PCUDA_ACT_SIGMOID && mode != PCUDA_ACT_SOFTMAX))
-    PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_ov_bwd: bad arguments");
-  if (!ov_known(overlap)) PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_ov_bwd: unknown overlap term %d", overlap);
-  if (c > OV_MAXC) PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "seg_loss_ov: at most %d classes (got %d)", OV_MAXC, c);
-  const Layout l = ov_layout(n, c, hw, overlap);
-  if (!workspace || workspace_bytes < l.total) PCUDA_FAIL(PCUDA_E_WORKSPACE, "seg_loss_ov_bwd: workspace too small");
-  const long long npix = (long long)n * hw;
-  const double numel_main = mode == PCUDA_ACT_SIGMOID ? (double)npix * c : (double)npix;
-  const float* coef = (const float*)((const char*)workspace + l.coef);
+  if (int rc = ov_check("seg_loss_ov_bwd", logits, onehot, dlogits, mode, overlap, n, c, hw, workspace, workspace_bytes)) return rc;
+  const float* coef = (const float*)((const char*)workspace + ov_layout(n, c, hw, overlap).coef);
+  const double numel_main = seg_numel_main(mode, n, c, hw);
   hipStream_t st = (hipStream_t)s;
   const int bps = sample_bps(n, hw, 4096);
   const unsigned blocks = (unsigned)n * bps;
   {
-    ProfScope prof(PCUDA_FAM_POINTWISE, 9.0 * npix * c, st);
+    ProfScope prof(PCUDA_FAM_POINTWISE, 9.0 * n * hw * c, st);
     if (overlap == PCUDA_OV_DICE_CLASS)
-      hipLaunchKernelGGL(seg_ov_bwd_kernel<false>, dim3(blocks), dim3(256), 0, st, logits, onehot, mode, c, hw, bps,
+      hipLaunchKernelGGL((seg_bwd_kernel<DiceOv, false>), dim3(blocks), dim3(256), 0, st, logits, onehot, mode, c, hw, bps,
                          numel_main, coef, c, g_main, g_ov, dlogits);
     else
-      hipLaunchKernelGGL(seg_ov_bwd_kernel<true>, dim3(blocks), dim3(256), 0, st, logits, onehot, mode, c, hw, bps,
+      hipLaunchKernelGGL((seg_bwd_kernel<DiceOv, true>), dim3(blocks), dim3(256), 0, st, logits, onehot, mode, c, hw, bps,
                          numel_main, coef, n, g_main, g_ov, dlogits);
   }
-  PCUDA_CHECK_LAUNCH("seg_ov_bwd_kernel");
+  PCUDA_CHECK_LAUNCH("seg_bwd_kernel");
   return PCUDA_OK;
 }
 
 extern "C" size_t pcuda_dice_workspace_size(int n, int c, long long hw, int reduce) {
-  if (n <= 0 || c <= 0 || c > DICE_MAXC || hw <= 0 || !ov_known(reduce)) return 0;
+  if (n <= 0 || c <= 0 || c > LOSS_MAXC || hw <= 0 || !ov_known(reduce)) return 0;
   return dice_layout(n, c, hw, reduce).total;
 }
 
 extern "C" int pcuda_dice_fwd(const float* probs, const void* truth, int truth_is_u8, int n, int c, long long hw,
                               int reduce, float eps, float* loss, void* workspace, size_t workspace_bytes,
                               pcuda_stream_t s) {
-  if (!probs || !truth || !loss || n <= 0 || c <= 0 || c > DICE_MAXC || hw <= 0 || !(eps >= 0.f))
-    PCUDA_FAIL(PCUDA_E_BADARG, "dice_fwd: bad arguments (1..%d classes)", DICE_MAXC);
-  if (!ov_known(reduce)) PCUDA_FAIL(PCUDA_E_BADARG, "dice_fwd: unknown reduction %d", reduce);
+  if (!(eps >= 0.f)) PCUDA_FAIL(PCUDA_E_BADARG, "dice_fwd: bad arguments");
+  if (int rc = dice_check("dice_fwd", probs, truth, loss, reduce, n, c, hw, workspace, workspace_bytes)) return rc;
   const Layout l = dice_layout(n, c, hw, reduce);
-  if (!workspace || workspace_bytes < l.total) PCUDA_FAIL(PCUDA_E_WORKSPACE, "dice_fwd: workspace too small");
   const long long npix = (long long)n * hw;
   const float* tf = truth_is_u8 ? nullptr : (const float*)truth;
   const uint8_t* tu = truth_is_u8 ? (const uint8_t*)truth : nullptr;
@@ -526,19 +303,13 @@ extern "C" int pcuda_dice_fwd(const float* probs, const void* truth, int truth_i
     if (blocks > DICE_BLOCKS) blocks = DICE_BLOCKS;
     {
       ProfScope prof(PCUDA_FAM_POINTWISE, bytes, st);
-      hipLaunchKernelGGL(dice_class_partial_kernel, dim3(blocks, c), dim3(256), 0, st, probs, tf, tu, c, hw, npix, part);
+      hipLaunchKernelGGL(overlap_class_partial_kernel, dim3(blocks, c), dim3(256), 0, st, probs, tf, tu, c, hw, npix, part);
     }
-    PCUDA_CHECK_LAUNCH("dice_class_partial_kernel");
-    {
-      ProfScope prof(PCUDA_FAM_POINTWISE, 4.0 * blocks * 2 * c, st);
-      hipLaunchKernelGGL(dice_class_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, blocks, c, 0, 1.0,
-                         (double)eps, (double*)workspace, (float*)((char*)workspace + l.coef), loss);
-    }
-    PCUDA_CHECK_LAUNCH("dice_class_final_kernel");
-    return PCUDA_OK;
+    PCUDA_CHECK_LAUNCH("overlap_class_partial_kernel");
+    return launch_class_final(workspace, l, blocks, c, 0, 1.0, (double)eps, loss, st);
   }
   const long long len = (long long)c * hw;
-  const int bps = sample_bps(n, len);
+  const int bps = sample_bps(n, len, OV_BLOCKS);
   {
     ProfScope prof(PCUDA_FAM_POINTWISE, bytes, st);
     hipLaunchKernelGGL(dice_sample_partial_kernel, dim3((unsigned)n * bps), dim3(256), 0, st, probs, tf, tu, len, bps, part);
@@ -550,34 +321,31 @@ extern "C" int pcuda_dice_fwd(const float* probs, const void* truth, int truth_i
 extern "C" int pcuda_dice_bwd(const void* truth, int truth_is_u8, int n, int c, long long hw, int reduce,
                               const float* gout, float* dprobs, const void* workspace, size_t workspace_bytes,
                               pcuda_stream_t s) {
-  if (!truth || !dprobs || n <= 0 || c <= 0 || c > DICE_MAXC || hw <= 0)
-    PCUDA_FAIL(PCUDA_E_BADARG, "dice_bwd: bad arguments (1..%d classes)", DICE_MAXC);
-  if (!ov_known(reduce)) PCUDA_FAIL(PCUDA_E_BADARG, "dice_bwd: unknown reduction %d", reduce);
-  const Layout l = dice_layout(n, c, hw, reduce);
-  if (!workspace || workspace_bytes < l.total) PCUDA_FAIL(PCUDA_E_WORKSPACE, "dice_bwd: workspace too small");
+  if (int rc = dice_check("dice_bwd", truth, truth, dprobs, reduce, n, c, hw, workspace, workspace_bytes)) return rc;
   const long long numel = (long long)n * c * hw;
   const bool sample = reduce == PCUDA_OV_DICE_SAMPLE;
   ProfScope prof(PCUDA_FAM_POINTWISE, (truth_is_u8 ? 5.0 : 8.0) * numel, (hipStream_t)s);
-  hipLaunchKernelGGL(dice_bwd_kernel, dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)s,
+  hipLaunchKernelGGL((overlap_bwd_kernel<DiceOv, false>), dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)s,
                      truth_is_u8 ? nullptr : (const float*)truth, truth_is_u8 ? (const uint8_t*)truth : nullptr, numel,
                      sample ? (long long)c * hw : hw, sample ? n : c, sample ? n : c,
-                     (const float*)((const char*)workspace + l.coef), gout, dprobs);
-  PCUDA_CHECK_LAUNCH("dice_bwd_kernel");
+                     (const float*)((const char*)workspace + dice_layout(n, c, hw, reduce).coef), (const double*)nullptr, 0.0,
+                     gout, dprobs);
+  PCUDA_CHECK_LAUNCH("overlap_bwd_kernel");
   return PCUDA_OK;
 }
 
 extern "C" size_t pcuda_dice_labels_workspace_size(int n, int c, long long hw) {
-  if (n <= 0 || c <= 0 || c > DICE_MAXC || hw <= 0) return 0;
-  return layout_sample(n, sample_bps(n, hw), 2).total;
+  if (n <= 0 || c <= 0 || c > LOSS_MAXC || hw <= 0) return 0;
+  return labels_layout(n, hw).total;
 }
 
 extern "C" int pcuda_dice_labels_fwd(const float* logits, const void* labels, int labels_are_i64, int n, int c,
                                      long long hw, float eps, float* loss, unsigned long long* bad_count, void* workspace,
                                      size_t workspace_bytes, pcuda_stream_t s) {
-  if (!logits || !labels || !loss || n <= 0 || c <= 0 || c > DICE_MAXC || hw <= 0 || !(eps >= 0.f))
-    PCUDA_FAIL(PCUDA_E_BADARG, "dice_labels_fwd: bad arguments (1..%d classes)", DICE_MAXC);
-  const int bps = sample_bps(n, hw);
-  const Layout l = layout_sample(n, bps, 2);
+  if (!logits || !labels || !loss || n <= 0 || c <= 0 || c > LOSS_MAXC || hw <= 0 || !(eps >= 0.f))
+    PCUDA_FAIL(PCUDA_E_BADARG, "dice_labels_fwd: bad arguments (1..%d classes)", LOSS_MAXC);
+  const int bps = sample_bps(n, hw, OV_BLOCKS);
+  const Layout l = labels_layout(n, hw);
   if (!workspace || workspace_bytes < l.total) PCUDA_FAIL(PCUDA_E_WORKSPACE, "dice_labels_fwd: workspace too small");
   hipStream_t st = (hipStream_t)s;
   if (bad_count && hipMemsetAsync(bad_count, 0, sizeof(unsigned long long), st) != hipSuccess)
@@ -596,9 +364,9 @@ extern "C" int pcuda_dice_labels_fwd(const float* logits, const void* labels, in
 extern "C" int pcuda_dice_labels_bwd(const float* logits, const void* labels, int labels_are_i64, int n, int c,
                                      long long hw, const float* gout, float* dlogits, const void* workspace,
                                      size_t workspace_bytes, pcuda_stream_t s) {
-  if (!logits || !labels || !dlogits || n <= 0 || c <= 0 || c > DICE_MAXC || hw <= 0)
-    PCUDA_FAIL(PCUDA_E_BADARG, "dice_labels_bwd: bad arguments (1..%d classes)", DICE_MAXC);
-  const Layout l = layout_sample(n, sample_bps(n, hw), 2);
+  if (!logits || !labels || !dlogits || n <= 0 || c <= 0 || c > LOSS_MAXC || hw <= 0)
+    PCUDA_FAIL(PCUDA_E_BADARG, "dice_labels_bwd: bad arguments (1..%d classes)", LOSS_MAXC);
+  const Layout l = labels_layout(n, hw);
   if (!workspace || workspace_bytes < l.total) PCUDA_FAIL(PCUDA_E_WORKSPACE, "dice_labels_bwd: workspace too small");
   const long long npix = (long long)n * hw;
   ProfScope prof(PCUDA_FAM_POINTWISE, (8.0 * c + (labels_are_i64 ? 8.0 : 1.0) + 8.0) * npix, (hipStream_t)s);

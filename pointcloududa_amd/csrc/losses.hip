@@ -5,9 +5,12 @@
 //   domain BCE(const)    train_mscmrseg.py:224-226
 //   batch_NN_loss        utils/loss.py:40-76
 //   Dice metric          utils/utils.py:32-40 + utils/metric.py:5-36
+// The channel softmax, the block reductions and the kernels of the BCE / CE + Jaccard loss and of Jaccard on probabilities are
+// loss_device.h's: the overlap family, shared with dice_loss.hip and run here with the Jaccard policy.  What is written out here
+// of that family is what only Jaccard has: jaccard_final_kernel's serial order.
 #include "loss_device.h"
 
-#define MAXC 16
+#define MAXC LOSS_MAXC
 #define SMOOTHF 1e-7f
 
 // ---------------------------------------------------------------------------- entropy
@@ -28,10 +31,7 @@ __global__ __launch_bounds__(256) void entropy_fwd_kernel(const float* __restric
       }
     } else {
       float v[MAXC];
-      float m = -INFINITY;
-      for (int k = 0; k < c; ++k) { v[k] = p[k * hw]; m = fmaxf(m, v[k]); }
-      float ssum = 0.f;
-      for (int k = 0; k < c; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
+      const float ssum = channel_softmax(p, hw, c, v);
       for (int k = 0; k < c; ++k) {
         const float pr = v[k] / ssum;
         e[k * hw] = -1.0f * pr * logf(pr + SMOOTHF) * norm;
@@ -64,10 +64,7 @@ __global__ __launch_bounds__(256) void entropy_bwd_kernel(const float* __restric
       }
     } else {
       float v[MAXC], gp[MAXC];
-      float m = -INFINITY;
-      for (int k = 0; k < c; ++k) { v[k] = logits[base + k * hw]; m = fmaxf(m, v[k]); }
-      float ssum = 0.f;
-      for (int k = 0; k < c; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
+      const float ssum = channel_softmax(logits + base, hw, c, v);
       float dot = 0.f;
       for (int k = 0; k < c; ++k) {
         const float pr = v[k] / ssum;
@@ -82,163 +79,6 @@ __global__ __launch_bounds__(256) void entropy_bwd_kernel(const float* __restric
         const float g = v[k] * (gp[k] - dot);
         dlogits[base + k * hw] = accumulate ? dlogits[base + k * hw] + g : g;
       }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------- segmentation loss
-// workspace layout (doubles): [0] main sum, [1..C] I_c, [1+C..2C] S_c, then float partials
-// partial row per block: [main, I_0..I_{C-1}, S_0..S_{C-1}]
-#define SEG_BLOCKS 1024
-
-template <int C>
-__global__ __launch_bounds__(256) void seg_loss_partial_kernel(const float* __restrict__ logits,
-                                                               const uint8_t* __restrict__ onehot, int mode,
-                                                               long long hw, long long npix,
-                                                               float* __restrict__ part) {
-  constexpr int NACC = 2 * C + 1;
-  __shared__ float sh[4][NACC];
-  float acc[NACC];
-#pragma unroll
-  for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npix; i += 256ll * gridDim.x) {
-    const long long n = i / hw, px = i - n * hw;
-    const long long base = n * C * hw + px;
-    if (mode == PCUDA_ACT_SIGMOID) {
-#pragma unroll
-      for (int k = 0; k < C; ++k) {
-        const float pr = sigmoidf_(logits[base + k * hw]);
-        const float y = (float)onehot[base + k * hw];
-        // torch BCELoss clamps each log at -100
-        const float l1 = fmaxf(logf(pr), -100.f), l0 = fmaxf(logf(1.f - pr), -100.f);
-        acc[0] += -(y * l1 + (1.f - y) * l0);
-        acc[1 + k] += pr * y;
-        acc[1 + C + k] += pr + y;
-      }
-    } else {
-      float v[C];
-      float m = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < C; ++k) { v[k] = logits[base + k * hw]; m = fmaxf(m, v[k]); }
-      float ssum = 0.f;
-#pragma unroll
-      for (int k = 0; k < C; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
-      uint8_t best = 0;
-      float pm = -INFINITY, plabel = 0.f;
-      bool first = true;
-#pragma unroll
-      for (int k = 0; k < C; ++k) {
-        const float pr = v[k] / ssum;
-        v[k] = pr;
-        const uint8_t yk = onehot[base + k * hw];
-        if (first || yk > best) { best = yk; plabel = pr; first = false; }   // first maximum = np.argmax
-        pm = fmaxf(pm, pr);
-        acc[1 + k] += pr * (float)yk;
-        acc[1 + C + k] += pr + (float)yk;
-      }
-      float s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < C; ++k) s2 += expf(v[k] - pm);
-      acc[0] += -(plabel - pm - logf(s2));   // -log_softmax(p)[label]
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NACC; ++k) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC)
-    part[(long long)blockIdx.x * NACC + threadIdx.x] =
-        (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
-
-__global__ void seg_loss_final_kernel(const float* __restrict__ part, int nblocks, int c, double numel_main,
-                                      double* __restrict__ sums, float* __restrict__ out2) {
-  __shared__ double sh[2 * MAXC + 1];
-  __shared__ double red[256];
-  const int nacc = 2 * c + 1;
-  // fixed-order tree per accumulator (a single lane per accumulator walking thousands of partials took 110 us
-  // between the segmenter's forward and backward passes)
-  for (int a = 0; a < nacc; ++a) {
-    double s = 0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) s += (double)part[(long long)b * nacc + a];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) { sums[a] = red[0]; sh[a] = red[0]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out2[0] = (float)(sh[0] / numel_main);
-    double j = 0;
-    for (int k = 0; k < c; ++k) {
-      const double I = sh[1 + k], S = sh[1 + c + k];
-      j += I / (S - I + 1e-7);
-    }
-    out2[1] = (float)(1.0 - j / c);
-  }
-}
-
-__global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restrict__ logits,
-                                                           const uint8_t* __restrict__ onehot, int mode, int c,
-                                                           long long hw, long long npix, double numel_main,
-                                                           const double* __restrict__ sums,
-                                                           const float* __restrict__ g_main,
-                                                           const float* __restrict__ g_jac,
-                                                           float* __restrict__ dlogits) {
-  __shared__ float ju[MAXC], jiu[MAXC];   // 1/U_c and I_c/U_c^2
-  if (threadIdx.x < c) {
-    const double I = sums[1 + threadIdx.x], S = sums[1 + c + threadIdx.x];
-    const double U = S - I + 1e-7;
-    ju[threadIdx.x] = (float)(1.0 / U);
-    jiu[threadIdx.x] = (float)(I / (U * U));
-  }
-  __syncthreads();
-  const float gm = (g_main ? *g_main : 1.f) / (float)numel_main;
-  const float gj = (g_jac ? *g_jac : 1.f) / (float)c;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npix; i += 256ll * gridDim.x) {
-    const long long n = i / hw, px = i - n * hw;
-    const long long base = n * c * hw + px;
-    if (mode == PCUDA_ACT_SIGMOID) {
-      for (int k = 0; k < c; ++k) {
-        const float pr = sigmoidf_(logits[base + k * hw]);
-        const float y = (float)onehot[base + k * hw];
-        const float pq = pr * (1.f - pr);
-        // torch: BCE backward divides by max(p(1-p), 1e-12), sigmoid backward multiplies by p(1-p)
-        const float gb = gm * (pr - y) / fmaxf(pq, 1e-12f);
-        const float gjac = -gj * (y * ju[k] - jiu[k] * (1.f - y));
-        dlogits[base + k * hw] = (gb + gjac) * pq;
-      }
-    } else {
-      float v[MAXC], gp[MAXC];
-      float m = -INFINITY;
-      for (int k = 0; k < c; ++k) { v[k] = logits[base + k * hw]; m = fmaxf(m, v[k]); }
-      float ssum = 0.f;
-      for (int k = 0; k < c; ++k) { v[k] = expf(v[k] - m); ssum += v[k]; }
-      int label = 0;
-      uint8_t best = 0;
-      float pm = -INFINITY;
-      for (int k = 0; k < c; ++k) {
-        v[k] = v[k] / ssum;
-        const uint8_t yk = onehot[base + k * hw];
-        if (yk > best) { best = yk; label = k; }
-        pm = fmaxf(pm, v[k]);
-      }
-      float s2 = 0.f;
-      for (int k = 0; k < c; ++k) s2 += expf(v[k] - pm);
-      float dot = 0.f;
-      for (int k = 0; k < c; ++k) {
-        const float y = (float)onehot[base + k * hw];
-        const float sm2 = expf(v[k] - pm) / s2;
-        const float g = gm * (sm2 - (k == label ? 1.f : 0.f)) - gj * (y * ju[k] - jiu[k] * (1.f - y));
-        gp[k] = g;
-        dot += g * v[k];
-      }
-      for (int k = 0; k < c; ++k) dlogits[base + k * hw] = v[k] * (gp[k] - dot);
     }
   }
 }
@@ -484,109 +324,76 @@ extern "C" int pcuda_sum_all(const float* x, long long numel, double scale, floa
   return PCUDA_OK;
 }
 
+// ---------------------------------------------------------------------------- segmentation loss: BCE / CE + Jaccard
+// The kernels are the overlap family's (loss_device.h) with the Jaccard policy; the Dice forms are in dice_loss.hip.
+// workspace: [WS_HEAD doubles: [0] main sum, [1..C] I_c, [1+C..2C] S_c; from WS_HEAD_COEF the float pairs (a_c, b_c)], then
+// the float partial rows, one per block: [main, I_0..I_{C-1}, S_0..S_{C-1}]
+#define SEG_BLOCKS 1024
+
 extern "C" size_t pcuda_seg_loss_workspace_size(int n, int c, long long hw) {
   (void)n; (void)hw;
-  return 64 * sizeof(double) + (size_t)SEG_BLOCKS * (2 * c + 1) * sizeof(float);
+  return WS_HEAD * sizeof(double) + (size_t)SEG_BLOCKS * (2 * c + 1) * sizeof(float);
 }
 
 extern "C" int pcuda_seg_loss_fwd(const float* logits, const uint8_t* onehot, int mode, int n, int c, long long hw,
                                   float* out2, void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
-  if (!logits || !onehot || !out2 || n <= 0 || c <= 0 || c > MAXC || hw <= 0)
-    PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_fwd: bad arguments");
+  if (int rc = seg_check_args("seg_loss_fwd", logits, onehot, out2, true, n, c, hw)) return rc;
   if (!workspace || workspace_bytes < pcuda_seg_loss_workspace_size(n, c, hw))
     PCUDA_FAIL(PCUDA_E_WORKSPACE, "seg_loss_fwd: workspace too small");
   const long long npix = (long long)n * hw;
   int blocks = grid_for(npix);
   if (blocks > SEG_BLOCKS) blocks = SEG_BLOCKS;
   double* sums = (double*)workspace;
-  float* part = (float*)((char*)workspace + 64 * sizeof(double));
-  const double numel_main = mode == PCUDA_ACT_SIGMOID ? (double)npix * c : (double)npix;
+  float* part = (float*)(sums + WS_HEAD);
   ProfScope prof(PCUDA_FAM_POINTWISE, 5.0 * npix * c, (hipStream_t)s);
-#define SEG_CASE(CC) case CC: hipLaunchKernelGGL(seg_loss_partial_kernel<CC>, dim3(blocks), dim3(256), 0, (hipStream_t)s, logits, onehot, mode, hw, npix, part); break;
-  switch (c) {
-    SEG_CASE(1) SEG_CASE(2) SEG_CASE(3) SEG_CASE(4) SEG_CASE(5) SEG_CASE(6) SEG_CASE(7) SEG_CASE(8)
-    default: PCUDA_FAIL(PCUDA_E_UNSUPPORTED, "seg_loss: at most 8 classes (got %d)", c);
-  }
+#define SEG_CASE(CC) case CC: hipLaunchKernelGGL((seg_partial_kernel<CC, false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)s, logits, onehot, mode, hw, npix, 0, part); break;
+  switch (c) { SEG_CASE(1) SEG_CASE(2) SEG_CASE(3) SEG_CASE(4) SEG_CASE(5) SEG_CASE(6) SEG_CASE(7) SEG_CASE(8) }
 #undef SEG_CASE
-  PCUDA_CHECK_LAUNCH("seg_loss_partial_kernel");
-  hipLaunchKernelGGL(seg_loss_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)part, blocks, c,
-                     numel_main, sums, out2);
-  PCUDA_CHECK_LAUNCH("seg_loss_final_kernel");
+  PCUDA_CHECK_LAUNCH("seg_partial_kernel");
+  // (the fused form's eps is the double 1e-7, not a float's: pcuda_jaccard_fwd below takes a float)
+  hipLaunchKernelGGL(overlap_class_final_kernel<JaccardOv>, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)part, blocks,
+                     c, 1, seg_numel_main(mode, n, c, hw), 1e-7, sums, (float*)(sums + WS_HEAD_COEF), out2);
+  PCUDA_CHECK_LAUNCH("overlap_class_final_kernel");
   return PCUDA_OK;
 }
 
 extern "C" int pcuda_seg_loss_bwd(const float* logits, const uint8_t* onehot, int mode, int n, int c, long long hw,
                                   const float* g_main, const float* g_jac, float* dlogits, const void* workspace,
                                   pcuda_stream_t s) {
-  if (!logits || !onehot || !dlogits || !workspace || n <= 0 || c <= 0 || c > MAXC || hw <= 0)
-    PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_bwd: bad arguments");
-  const long long npix = (long long)n * hw;
-  const double numel_main = mode == PCUDA_ACT_SIGMOID ? (double)npix * c : (double)npix;
-  ProfScope prof(PCUDA_FAM_POINTWISE, 9.0 * npix * c, (hipStream_t)s);
-  hipLaunchKernelGGL(seg_loss_bwd_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)s, logits, onehot, mode, c,
-                     hw, npix, numel_main, (const double*)workspace, g_main, g_jac, dlogits);
-  PCUDA_CHECK_LAUNCH("seg_loss_bwd_kernel");
+  if (int rc = seg_check_args("seg_loss_bwd", logits, onehot, dlogits, true, n, c, hw)) return rc;
+  if (!workspace) PCUDA_FAIL(PCUDA_E_BADARG, "seg_loss_bwd: bad arguments");
+  const int bps = sample_bps(n, hw, 4096);
+  ProfScope prof(PCUDA_FAM_POINTWISE, 9.0 * n * hw * c, (hipStream_t)s);
+  hipLaunchKernelGGL((seg_bwd_kernel<JaccardOv, false>), dim3((unsigned)n * bps), dim3(256), 0, (hipStream_t)s, logits, onehot,
+                     mode, c, hw, bps, seg_numel_main(mode, n, c, hw), (const float*)((const double*)workspace + WS_HEAD_COEF),
+                     c, g_main, g_jac, dlogits);
+  PCUDA_CHECK_LAUNCH("seg_bwd_kernel");
   return PCUDA_OK;
 }
 
 // ---------------------------------------------------------------------------- Jaccard on given probabilities
 // utils/loss.py:5-37 as a free-standing function (the fused seg_loss above is what the train step uses): per class
 // I_c = sum p*y, S_c = sum (p + y) over (batch, pixels); loss = 1 - mean_c I_c / (S_c - I_c + eps).
-// ws (doubles): [c] I, [c] S, then float partials [JAC_BLOCKS][c][2]
+// ws (doubles): [c] I, [c] S, then float partial rows [JAC_BLOCKS][2][c]
 #define JAC_BLOCKS 256
-__global__ __launch_bounds__(256) void jaccard_partial_kernel(const float* __restrict__ p, const float* __restrict__ tf,
-                                                              const uint8_t* __restrict__ tu, int c, long long hw,
-                                                              long long npix, float* __restrict__ part) {
-  __shared__ float sh[4][2];
-  const int k = blockIdx.y;
-  float a0 = 0.f, a1 = 0.f;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npix; i += 256ll * gridDim.x) {
-    const long long n = i / hw, px = i - n * hw;
-    const long long o = (n * c + k) * hw + px;
-    const float pr = p[o], y = tf ? tf[o] : (float)tu[o];
-    a0 += pr * y;
-    a1 += pr + y;
-  }
-  a0 = wave_sum(a0); a1 = wave_sum(a1);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6][0] = a0; sh[threadIdx.x >> 6][1] = a1; }
-  __syncthreads();
-  if (threadIdx.x < 2)
-    part[((long long)blockIdx.x * c + k) * 2 + threadIdx.x] =
-        (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-}
 
+// one lane per accumulator sums its <= 256 partials serially: another order than overlap_class_final_kernel's tree, hence
+// another double, and the one this entry point has always returned
 __global__ void jaccard_final_kernel(const float* __restrict__ part, int nblocks, int c, float eps,
                                      double* __restrict__ sums, float* __restrict__ loss) {
   __shared__ double tot[2 * MAXC];
   if ((int)threadIdx.x < 2 * c) {
     const int k = threadIdx.x >> 1, which = threadIdx.x & 1;
     double s = 0;
-    for (int b = 0; b < nblocks; ++b) s += (double)part[((long long)b * c + k) * 2 + which];   // fixed order
+    for (int b = 0; b < nblocks; ++b) s += (double)part[(long long)b * 2 * c + which * c + k];   // fixed order
     tot[which * c + k] = s;
     sums[which * c + k] = s;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     double j = 0;
-    for (int k = 0; k < c; ++k) j += tot[k] / (tot[c + k] - tot[k] + (double)eps);
+    for (int k = 0; k < c; ++k) j += JaccardOv::term(tot[k], JaccardOv::den(tot[k], tot[c + k], (double)eps));
     loss[0] = (float)(1.0 - j / c);
-  }
-}
-
-// d loss / d p = -(1/C) * (y * (U + eps) - I * (1 - y)) / (U + eps)^2,   U = S - I
-__global__ __launch_bounds__(256) void jaccard_bwd_kernel(const float* __restrict__ tf, const uint8_t* __restrict__ tu,
-                                                          int c, long long hw, long long npix, float eps,
-                                                          const double* __restrict__ sums,
-                                                          const float* __restrict__ gout, float* __restrict__ dp) {
-  const int k = blockIdx.y;
-  const double I = sums[k], U = sums[c + k] - I + (double)eps;
-  const float g = (gout ? *gout : 1.f) / (float)c;
-  const float a = (float)(1.0 / U), b = (float)(I / (U * U));
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npix; i += 256ll * gridDim.x) {
-    const long long n = i / hw, px = i - n * hw;
-    const long long o = (n * c + k) * hw + px;
-    const float y = tf ? tf[o] : (float)tu[o];
-    dp[o] = -g * (y * a - (1.f - y) * b);
   }
 }
 
@@ -596,37 +403,35 @@ extern "C" size_t pcuda_jaccard_workspace_size(int c) {
 
 extern "C" int pcuda_jaccard_fwd(const float* probs, const void* truth, int truth_is_u8, int n, int c, long long hw,
                                  float eps, float* loss, void* workspace, size_t workspace_bytes, pcuda_stream_t s) {
-  if (!probs || !truth || !loss || n <= 0 || c <= 0 || c > MAXC || hw <= 0)
-    PCUDA_FAIL(PCUDA_E_BADARG, "jaccard_fwd: bad arguments");
+  if (int rc = probs_check_args("jaccard_fwd", probs, truth, loss, n, c, hw)) return rc;
   if (!workspace || workspace_bytes < pcuda_jaccard_workspace_size(c))
     PCUDA_FAIL(PCUDA_E_WORKSPACE, "jaccard_fwd: workspace too small");
   const long long npix = (long long)n * hw;
   int blocks = grid_for(npix);
   if (blocks > JAC_BLOCKS) blocks = JAC_BLOCKS;
   double* sums = (double*)workspace;
-  float* part = (float*)((char*)workspace + 2 * MAXC * sizeof(double));
+  float* part = (float*)(sums + 2 * MAXC);
   ProfScope prof(PCUDA_FAM_POINTWISE, 8.0 * npix * c, (hipStream_t)s);
-  hipLaunchKernelGGL(jaccard_partial_kernel, dim3(blocks, c), dim3(256), 0, (hipStream_t)s, probs,
+  hipLaunchKernelGGL(overlap_class_partial_kernel, dim3(blocks, c), dim3(256), 0, (hipStream_t)s, probs,
                      truth_is_u8 ? nullptr : (const float*)truth, truth_is_u8 ? (const uint8_t*)truth : nullptr, c, hw,
                      npix, part);
-  PCUDA_CHECK_LAUNCH("jaccard_partial_kernel");
+  PCUDA_CHECK_LAUNCH("overlap_class_partial_kernel");
   hipLaunchKernelGGL(jaccard_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, (const float*)part, blocks, c, eps, sums,
                      loss);
   PCUDA_CHECK_LAUNCH("jaccard_final_kernel");
   return PCUDA_OK;
 }
 
+// (eps arrives again: the pairs (a_c, b_c) are derived from the reduced sums in the kernel, with the double of this float)
 extern "C" int pcuda_jaccard_bwd(const void* truth, int truth_is_u8, int n, int c, long long hw, float eps,
                                  const float* gout, float* dprobs, const void* workspace, pcuda_stream_t s) {
-  if (!truth || !dprobs || !workspace || n <= 0 || c <= 0 || c > MAXC || hw <= 0)
-    PCUDA_FAIL(PCUDA_E_BADARG, "jaccard_bwd: bad arguments");
-  const long long npix = (long long)n * hw;
-  int blocks = grid_for(npix);
-  ProfScope prof(PCUDA_FAM_POINTWISE, 8.0 * npix * c, (hipStream_t)s);
-  hipLaunchKernelGGL(jaccard_bwd_kernel, dim3(blocks, c), dim3(256), 0, (hipStream_t)s,
-                     truth_is_u8 ? nullptr : (const float*)truth, truth_is_u8 ? (const uint8_t*)truth : nullptr, c, hw,
-                     npix, eps, (const double*)workspace, gout, dprobs);
-  PCUDA_CHECK_LAUNCH("jaccard_bwd_kernel");
+  if (int rc = probs_check_args("jaccard_bwd", workspace, truth, dprobs, n, c, hw)) return rc;
+  const long long numel = (long long)n * c * hw;
+  ProfScope prof(PCUDA_FAM_POINTWISE, 8.0 * numel, (hipStream_t)s);
+  hipLaunchKernelGGL((overlap_bwd_kernel<JaccardOv, true>), dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)s,
+                     truth_is_u8 ? nullptr : (const float*)truth, truth_is_u8 ? (const uint8_t*)truth : nullptr, numel, hw, c,
+                     c, (const float*)nullptr, (const double*)workspace, (double)eps, gout, dprobs);
+  PCUDA_CHECK_LAUNCH("overlap_bwd_kernel");
   return PCUDA_OK;
 }
 

@@ -845,17 +845,31 @@ def seg_loss_bwd(logits, onehot, mode, ws, g_main=None, g_jac=None):
     return d
 
 
-def jaccard_fwd(probs, truth, eps):
-    """probs fp32 [n,c,...]; truth one-hot, fp32 or uint8, same shape -> (loss scalar, workspace)"""
+def _probs_truth(what, probs, truth):
+    """the operands of an overlap loss on given probabilities -> (probs, truth as the kernel reads it, n, c, hw)"""
     _req(probs)
     if truth.dtype not in (torch.float32, torch.uint8):
         truth = truth.float()      # the reference casts any dtype: ``true.type(probas.type())`` (loss.py:27)
     _req(truth, truth.dtype)
     if truth.shape != probs.shape:
-        raise ValueError("jaccard: `true` %r and probabilities %r differ in shape" % (tuple(truth.shape), tuple(probs.shape)))
-    probs, truth = probs.contiguous(), truth.contiguous()
+        raise ValueError("%s: `true` %r and probabilities %r differ in shape" % (what, tuple(truth.shape), tuple(probs.shape)))
     n, c = probs.shape[:2]
-    hw = probs.numel() // (n * c)
+    return probs.contiguous(), truth.contiguous(), n, c, probs.numel() // (n * c)
+
+
+def _probs_grad(truth, shape):
+    """-> (the gradient tensor of an overlap loss on given probabilities, whether the truth is uint8, n, c, hw)"""
+    n, c = shape[:2]
+    hw = 1
+    for d in shape[2:]:
+        hw *= d
+    return torch.empty(shape, dtype=torch.float32, device=truth.device), 1 if truth.dtype == torch.uint8 else 0, n, c, hw
+
+
+def jaccard_fwd(probs, truth, eps):
+    """probs fp32 [n,c,...]; truth one-hot, fp32 or uint8, same shape -> (loss scalar, workspace, the truth tensor the kernel
+    read)"""
+    probs, truth, n, c, hw = _probs_truth("jaccard", probs, truth)
     lib = L.lib()
     nb = lib.pcuda_jaccard_workspace_size(c)
     ws = torch.empty(nb, dtype=torch.uint8, device=probs.device)
@@ -866,13 +880,9 @@ def jaccard_fwd(probs, truth, eps):
 
 
 def jaccard_bwd(truth, shape, eps, ws, gout):
-    n, c = shape[:2]
-    hw = 1
-    for d in shape[2:]:
-        hw *= d
-    dp = torch.empty(shape, dtype=torch.float32, device=truth.device)
-    check(L.lib().pcuda_jaccard_bwd(truth.data_ptr(), 1 if truth.dtype == torch.uint8 else 0, n, c, hw, float(eps),
-                                    _ptr(gout), dp.data_ptr(), ws.data_ptr(), _stream()), "jaccard_bwd")
+    dp, u8, n, c, hw = _probs_grad(truth, shape)
+    check(L.lib().pcuda_jaccard_bwd(truth.data_ptr(), u8, n, c, hw, float(eps), _ptr(gout), dp.data_ptr(), ws.data_ptr(),
+                                    _stream()), "jaccard_bwd")
     return dp
 
 
@@ -915,16 +925,8 @@ def seg_loss_ov_bwd(logits, onehot, mode, overlap, ws, g_main=None, g_ov=None):
 def dice_fwd(probs, truth, eps, reduce="class"):
     """probs fp32 [n,c,...]; truth one-hot, fp32 or uint8, same shape; reduce 'class' | 'sample' -> (loss scalar, workspace,
     the truth tensor the kernel read)"""
-    _req(probs)
     red = _overlap(reduce)
-    if truth.dtype not in (torch.float32, torch.uint8):
-        truth = truth.float()
-    _req(truth, truth.dtype)
-    if truth.shape != probs.shape:
-        raise ValueError("dice: `true` %r and probabilities %r differ in shape" % (tuple(truth.shape), tuple(probs.shape)))
-    probs, truth = probs.contiguous(), truth.contiguous()
-    n, c = probs.shape[:2]
-    hw = probs.numel() // (n * c)
+    probs, truth, n, c, hw = _probs_truth("dice", probs, truth)
     lib = L.lib()
     nb = lib.pcuda_dice_workspace_size(n, c, hw, red)
     ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=probs.device)
@@ -935,13 +937,9 @@ def dice_fwd(probs, truth, eps, reduce="class"):
 
 
 def dice_bwd(truth, shape, reduce, ws, gout):
-    n, c = shape[:2]
-    hw = 1
-    for d in shape[2:]:
-        hw *= d
-    dp = torch.empty(shape, dtype=torch.float32, device=truth.device)
-    check(L.lib().pcuda_dice_bwd(truth.data_ptr(), 1 if truth.dtype == torch.uint8 else 0, n, c, hw, _overlap(reduce),
-                                 _ptr(gout), dp.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dice_bwd")
+    dp, u8, n, c, hw = _probs_grad(truth, shape)
+    check(L.lib().pcuda_dice_bwd(truth.data_ptr(), u8, n, c, hw, _overlap(reduce), _ptr(gout), dp.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _stream()), "dice_bwd")
     return dp
 
 

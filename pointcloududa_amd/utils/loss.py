@@ -29,28 +29,16 @@ def _zero(dev):
 
 
 class _SegLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, onehot, mode):
-        logits = logits.contiguous()
-        out2, ws = K.seg_loss_fwd(logits, onehot, mode)
-        ctx.logits, ctx.onehot, ctx.mode, ctx.ws = logits, onehot, mode, ws
-        ctx.set_materialize_grads(False)
-        return out2[0], out2[1]
+    """main term + overlap term in one pass each way: ``overlap`` "jaccard" on the seg_loss kernels (``eps`` is theirs), a Dice
+    term on the seg_loss_ov kernels"""
 
-    @staticmethod
-    def backward(ctx, g_main, g_jac):
-        dev = ctx.logits.device
-        g_main = _zero(dev) if g_main is None else g_main.contiguous()
-        g_jac = _zero(dev) if g_jac is None else g_jac.contiguous()
-        d = K.seg_loss_bwd(ctx.logits, ctx.onehot, ctx.mode, ctx.ws, g_main, g_jac)
-        return d, None, None
-
-
-class _SegLossOvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, onehot, mode, overlap, eps):
         logits = logits.contiguous()
-        out2, ws = K.seg_loss_ov_fwd(logits, onehot, mode, overlap, eps)
+        if overlap == "jaccard":
+            out2, ws = K.seg_loss_fwd(logits, onehot, mode)
+        else:
+            out2, ws = K.seg_loss_ov_fwd(logits, onehot, mode, overlap, eps)
         ctx.logits, ctx.onehot, ctx.mode, ctx.overlap, ctx.ws = logits, onehot, mode, overlap, ws
         ctx.set_materialize_grads(False)
         return out2[0], out2[1]
@@ -60,12 +48,16 @@ class _SegLossOvFn(torch.autograd.Function):
         dev = ctx.logits.device
         g_main = _zero(dev) if g_main is None else g_main.contiguous()
         g_ov = _zero(dev) if g_ov is None else g_ov.contiguous()
-        d = K.seg_loss_ov_bwd(ctx.logits, ctx.onehot, ctx.mode, ctx.overlap, ctx.ws, g_main, g_ov)
+        if ctx.overlap == "jaccard":
+            d = K.seg_loss_bwd(ctx.logits, ctx.onehot, ctx.mode, ctx.ws, g_main, g_ov)
+        else:
+            d = K.seg_loss_ov_bwd(ctx.logits, ctx.onehot, ctx.mode, ctx.overlap, ctx.ws, g_main, g_ov)
         return d, None, None, None, None
 
 
-# eps of the fused Dice terms: per class the fused Jaccard's, per sample kornia.losses.DiceLoss's default
-_OVERLAP_EPS = {"dice": 1e-7, "dice_sample": 1e-6}
+# eps of the fused overlap terms: Jaccard's is inside its kernels; per class Dice takes the same value, per sample
+# kornia.losses.DiceLoss's default
+_OVERLAP_EPS = {"jaccard": 1e-7, "dice": 1e-7, "dice_sample": 1e-6}
 
 
 def overlap_for(dice):
@@ -81,53 +73,18 @@ def seg_loss(logits, onehot_u8, mode="sigmoid", overlap="jaccard"):
     "jaccard" (what the reference trains with), "dice" (per class, the Jaccard term's twin: 1 - mean_c 2 I_c / (S_c + 1e-7))
     or "dice_sample" (per sample, kornia's documented formula: mean_n (1 - 2 I_n / (S_n + 1e-6))); the Dice rules are this
     build's own."""
-    if overlap == "jaccard":
-        return _SegLossFn.apply(logits, onehot_u8, mode)
     if overlap not in _OVERLAP_EPS:
         raise ValueError("seg_loss: overlap %r is none of 'jaccard', 'dice', 'dice_sample'" % (overlap,))
-    return _SegLossOvFn.apply(logits, onehot_u8, mode, overlap, _OVERLAP_EPS[overlap])
+    return _SegLossFn.apply(logits, onehot_u8, mode, overlap, _OVERLAP_EPS[overlap])
 
 
-class _JaccardFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, probs, true, eps):
-        loss, ws, truth = K.jaccard_fwd(probs, true, eps)
-        ctx.truth, ctx.ws, ctx.eps, ctx.shape = truth, ws, eps, tuple(probs.shape)
-        ctx.set_materialize_grads(False)
-        return loss
+class _OverlapFn(torch.autograd.Function):
+    """Jaccard (``reduce`` None) or Dice ("class" | "sample") on given probabilities"""
 
-    @staticmethod
-    def backward(ctx, gout):
-        if gout is None:
-            return None, None, None
-        return K.jaccard_bwd(ctx.truth, ctx.shape, ctx.eps, ctx.ws, gout.contiguous()), None, None
-
-
-def jaccard_loss(true, logits, eps=1e-7, activation=True):
-    """Reference signature and semantics (loss.py:5-37).  ``logits``: [B,C,H,W]; with ``activation=False`` (how
-    train_mscmrseg.py:203 and train_mmwhs.py:218 call it) they already are probabilities, with ``activation=True``
-    they go through a softmax over the channels first; ``true``: one-hot [B,C,H,W] (float or uint8).  Differentiable
-    w.r.t. ``logits`` (through whatever produced them: the result is an ordinary autograd node on the HIP kernels).
-    The reference's C == 1 branch pairs [sigmoid, 1 - sigmoid] with ``true`` BROADCAST over both channels (the
-    one-hot it builds at loss.py:15-19 is overwritten at :27): reproduced as executed.
-    The train step itself uses the fused ``seg_loss`` below (one pass over the logits for both loss terms)."""
-    num_classes = logits.shape[1]
-    if num_classes == 1:
-        pos = entropy_map(logits, "sigmoid", False, want_prob=True)[1]
-        probas = torch.cat([pos, 1 - pos], dim=1)                                     # loss.py:20-22
-        return _JaccardFn.apply(probas, true.float().expand_as(probas).contiguous(), float(eps))   # :27
-    if activation:
-        probas = entropy_map(logits, "softmax", False, want_prob=True)[1]
-    else:
-        probas = logits
-    return _JaccardFn.apply(probas, true, float(eps))
-
-
-class _DiceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, probs, true, eps, reduce):
-        loss, ws, truth = K.dice_fwd(probs, true, eps, reduce)
-        ctx.truth, ctx.ws, ctx.reduce, ctx.shape = truth, ws, reduce, tuple(probs.shape)
+        loss, ws, truth = K.jaccard_fwd(probs, true, eps) if reduce is None else K.dice_fwd(probs, true, eps, reduce)
+        ctx.truth, ctx.ws, ctx.eps, ctx.reduce, ctx.shape = truth, ws, eps, reduce, tuple(probs.shape)
         ctx.set_materialize_grads(False)
         return loss
 
@@ -135,7 +92,34 @@ class _DiceFn(torch.autograd.Function):
     def backward(ctx, gout):
         if gout is None:
             return None, None, None, None
-        return K.dice_bwd(ctx.truth, ctx.shape, ctx.reduce, ctx.ws, gout.contiguous()), None, None, None
+        gout = gout.contiguous()
+        if ctx.reduce is None:
+            return K.jaccard_bwd(ctx.truth, ctx.shape, ctx.eps, ctx.ws, gout), None, None, None
+        return K.dice_bwd(ctx.truth, ctx.shape, ctx.reduce, ctx.ws, gout), None, None, None
+
+
+def _overlap_loss(true, logits, eps, activation, reduce):
+    """the branches ``jaccard_loss`` and ``dice_loss`` share (loss.py:5-37).  The reference's C == 1 branch pairs
+    [sigmoid, 1 - sigmoid] with ``true`` BROADCAST over both channels (the one-hot it builds at loss.py:15-19 is overwritten
+    at :27): reproduced as executed."""
+    if logits.shape[1] == 1:
+        pos = entropy_map(logits, "sigmoid", False, want_prob=True)[1]
+        probas = torch.cat([pos, 1 - pos], dim=1)                                     # loss.py:20-22
+        true = true.float().expand_as(probas).contiguous()                            # :27
+    elif activation:
+        probas = entropy_map(logits, "softmax", False, want_prob=True)[1]
+    else:
+        probas = logits
+    return _OverlapFn.apply(probas, true, float(eps), reduce)
+
+
+def jaccard_loss(true, logits, eps=1e-7, activation=True):
+    """Reference signature and semantics (loss.py:5-37).  ``logits``: [B,C,H,W]; with ``activation=False`` (how
+    train_mscmrseg.py:203 and train_mmwhs.py:218 call it) they already are probabilities, with ``activation=True``
+    they go through a softmax over the channels first; ``true``: one-hot [B,C,H,W] (float or uint8).  Differentiable
+    w.r.t. ``logits`` (through whatever produced them: the result is an ordinary autograd node on the HIP kernels).
+    The train step itself uses the fused ``seg_loss`` above (one pass over the logits for both loss terms)."""
+    return _overlap_loss(true, logits, eps, activation, None)
 
 
 def dice_loss(true, logits, eps=1e-7, activation=True, reduce="class"):
@@ -147,16 +131,7 @@ def dice_loss(true, logits, eps=1e-7, activation=True, reduce="class"):
     w.r.t. ``logits``."""
     if reduce not in ("class", "sample"):
         raise ValueError("dice_loss: reduce %r is neither 'class' nor 'sample'" % (reduce,))
-    num_classes = logits.shape[1]
-    if num_classes == 1:
-        pos = entropy_map(logits, "sigmoid", False, want_prob=True)[1]
-        probas = torch.cat([pos, 1 - pos], dim=1)
-        return _DiceFn.apply(probas, true.float().expand_as(probas).contiguous(), float(eps), reduce)
-    if activation:
-        probas = entropy_map(logits, "softmax", False, want_prob=True)[1]
-    else:
-        probas = logits
-    return _DiceFn.apply(probas, true, float(eps), reduce)
+    return _overlap_loss(true, logits, eps, activation, reduce)
 
 
 class _DiceLabelsFn(torch.autograd.Function):
@@ -279,10 +254,6 @@ class _BceConstFn(torch.autograd.Function):
         loss, acc = K.bce_const_fwd(x, label, want_acc)
         ctx.x, ctx.label, ctx.weight = x, label, weight
         ctx.set_materialize_grads(False)
-        if weight != 1.0:
-            # the scalar is rescaled on the host side of the graph by the backward's gscale; the
-            # forward value is reported unscaled next to it
-            pass
         if want_acc:
             ctx.mark_non_differentiable(acc)
             return loss, acc

@@ -1,7 +1,7 @@
 """Device time per call of the Dice losses (utils/loss.py, csrc/dice_loss.hip) next to the Jaccard path they stand beside, at
 the two shapes the train steps run: [32,4,256,256] in sigmoid mode (MS-CMRSeg) and [16,5,256,256] in softmax mode (MM-WHS).
 
-  (a) forward + backward of the fused seg_loss (kernels.seg_loss_fwd / _bwd: unchanged code) and of its two Dice forms
+  (a) forward + backward of the fused seg_loss (kernels.seg_loss_fwd / _bwd) and of its two Dice forms
       (kernels.seg_loss_ov_fwd / _bwd, "dice" per class and "dice_sample" per sample), seeds given as the train step gives them
   (b) DiceLoss (logits + int64 label map, autograd forward + backward) against the equivalent ATen chain
       (softmax, one_hot, two products and sums, the ratio's mean, autograd backward)

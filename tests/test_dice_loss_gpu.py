@@ -2,7 +2,7 @@
 float64 statements of tests/dice_refs.py.
 
 case -> branch
-  fused C = 1, 2, 3, 4, 5, 8 x mode x reduction    every seg_ov_*_partial_kernel<C> in use; both reduce chains
+  fused C = 1, 2, 3, 4, 5, 8 x mode x reduction    every seg_partial_kernel<C, true, *> in use; both reduce chains
   fused (1, 1), (2, 257), (3, 300)                 one pixel; one ragged block; several samples in one launch
   fused (1, 2, 513 * 512)                          262656 pixels: 1024 blocks cap the grid, two trips per thread
   +-40 logits in the first sample                  the BCE log clamp and its backward next to the Dice term

@@ -2,9 +2,11 @@
 evaluated in float64 (through tests/fp64_refs.py) and the numpy Dice of oracle/metrics.py.
 
 case -> branch
-  seg_loss C = 1, 2, 3, 6, 7, 8 x mode          every seg_loss_partial_kernel<C> the existing tests (C = 4, 5) leave out
+  seg_loss C = 1, 2, 3, 6, 7, 8 x mode          every flat-walk seg_partial_kernel<C> the existing tests (C = 4, 5) leave out
   seg_loss (1, 1), (2, 257)                     one pixel; one ragged block; +-40 logits: the BCE log clamp and its backward
   seg_loss (1, 2, 513 * 512)                    262656 pixels: SEG_BLOCKS = 1024 caps the grid, two trips per thread
+  seg_loss (1, 2, 1025 * 1024)                  1049600 pixels: the backward's 4096-block cap, two trips per thread
+  seg_loss (4100, 3, 3)                         more samples than either pass's block budget: one block per sample
   seg_loss C = 9, entropy C = 17, nn_loss 1025  refused before any launch
   entropy C = 1, 2, 16 x mode x norm            the per-pixel channel loops at their ends (MAXC = 16)
   entropy_bwd accumulate / dmean / all three    the `+=`, the mean's share alone, every source together
@@ -47,7 +49,8 @@ def _onehot(rng, n, c, hw):
     return torch.from_numpy(np.moveaxis(np.eye(c, dtype=np.uint8)[lab], -1, 1).copy())
 
 
-SEG = [(c, n, hw) for c in (1, 2, 3, 6, 7, 8) for (n, hw) in ((1, 1), (2, 257))] + [(2, 1, 513 * 512)]
+SEG = [(c, n, hw) for c in (1, 2, 3, 6, 7, 8) for (n, hw) in ((1, 1), (2, 257))] + [(2, 1, 513 * 512), (2, 1, 1025 * 1024),
+                                                                                     (3, 4100, 3)]
 
 
 @pytest.mark.parametrize("mode", ["sigmoid", "softmax"])
