@@ -3,9 +3,12 @@
 //
 // Every kernel here computes, BIT FOR BIT, what the general kernels of pointwise.hip / dense.hip compute for the same
 // tensors: the association of every floating-point sum is kept, only the mapping to threads and the memory access change.
+// The BatchNorm arithmetic itself -- both finalisations, the gate, the reduce terms, the dz expression -- is bn_device.h's,
+// the one statement both files compile.
 // (A file of its own: tests/test_isa_rules.py keeps an allow-list of loads in pointwise.s / dense.s that this code must not
 // add to.  The VMEM address rule of common.h is followed here all the same: PCUDA_KEEP after the data is consumed.)
 #include "common.h"
+#include "bn_device.h"      // the BatchNorm arithmetic, shared with pointwise.hip
 
 #ifndef PCH
 #define PCH 2048   // plane elements per workgroup of the general kernels (pointwise.hip)
@@ -95,29 +98,22 @@ __global__ __launch_bounds__(256) void bn1d_fwd_kernel(const float* __restrict__
     p1 = 0.f + v;
     p2 = 0.f + v * v;
   }, sh);
-  if (ry == 0 && live) {      // bn_finalize_kernel's thread 0, verbatim
-    const double m = sh[0][0][cx] / count;
-    double var = sh[1][0][cx] / count - m * m;
-    if (var < 0 || count <= 1) var = 0;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
+  if (ry == 0 && live) {      // bn_finalize_kernel's thread 0: the same bn_fwd_finalize (bn_device.h)
     const float* pgm = gamma ? gamma + ch : nullptr;
     const float* pbt = beta ? beta + ch : nullptr;
-    const float g = pgm ? *pgm : 1.f, bb = pbt ? *pbt : 0.f;
-    mean[ch] = (float)m;
-    invstd[ch] = is;
-    const float sc = count > 1 ? g * is : 0.f;
-    const float sf = bb - (float)m * sc;
-    scale[ch] = sc;
-    shift[ch] = sf;
-    shc[0][cx] = sc;
-    shc[1][cx] = sf;
+    const BnFwd r = bn_fwd_finalize(sh[0][0][cx], sh[1][0][cx], count, pgm ? *pgm : 1.f, pbt ? *pbt : 0.f, eps);
+    mean[ch] = r.mean;
+    invstd[ch] = r.invstd;
+    scale[ch] = r.scale;
+    shift[ch] = r.shift;
+    shc[0][cx] = r.scale;
+    shc[1][cx] = r.shift;
     if (running_mean) {
-      const double unb = count > 1 ? var * count / (count - 1.0) : var;
       float* prm = running_mean + ch;
       float* prv = running_var + ch;
       const float rm = *prm, rv = *prv;
-      *prm = (1.f - momentum) * rm + momentum * (float)m;
-      *prv = (1.f - momentum) * rv + momentum * (float)unb;
+      *prm = bn_running(rm, momentum, r.mean);
+      *prv = bn_running(rv, momentum, bn_unbiased(r.var, count));
       PCUDA_KEEP(prm); PCUDA_KEEP(prv);
     }
     PCUDA_KEEP(pgm); PCUDA_KEEP(pbt);      // (VMEM address rule, common.h)
@@ -167,31 +163,30 @@ __global__ __launch_bounds__(256) void bn1d_bwd_kernel(const float* __restrict__
   }
   // one sample's partial as bn_bwd_reduce_kernel leaves it for a one-element tile
   slot_tree_sum<true>(pa, a_sn, pd, dy_sn, b, live, [&](float av, float gg, float& p1, float& p2) {
-    if (post_relu && !(av * sc + sf > 0.f)) gg = 0.f;
-    p1 = 0.f + gg;
-    p2 = 0.f + gg * ((av - m) * is);
+    p1 = 0.f; p2 = 0.f;
+    bn_reduce_terms(bn_gate(gg, av, sc, sf, post_relu), av, m, is, p1, p2);
   }, sh);
-  if (ry == 0 && live) {      // bn_bwd_finalize_kernel's thread 0, verbatim (count > 0: the frozen form is not taken here)
-    const double S1 = sh[0][0][cx], S2 = sh[1][0][cx];
-    const float* pgm = gamma ? gamma + ch : nullptr;
-    const double g = pgm ? (double)*pgm : 1.0, isd = is, md = m;
+  if (ry == 0 && live) {      // bn_bwd_finalize_kernel's thread 0: the same bn_bwd_finalize (count > 0: never the frozen form)
+    double g = 1.0;
+    if (gamma) {
+      const float* pgm = gamma + ch;
+      g = (double)*pgm;
+      PCUDA_KEEP(pgm);
+    }
+    const BnBwd r = bn_bwd_finalize(sh[0][0][cx], sh[1][0][cx], count, g, is, m);
     if (dgamma) {
       float* p = dgamma + ch;
       const float old = accumulate ? *p : 0.f;
-      *p = accumulate ? old + (float)S2 : (float)S2;
+      *p = accumulate ? old + r.dgamma : r.dgamma;
       PCUDA_KEEP(p);
     }
     if (dbeta) {
       float* p = dbeta + ch;
       const float old = accumulate ? *p : 0.f;
-      *p = accumulate ? old + (float)S1 : (float)S1;
+      *p = accumulate ? old + r.dbeta : r.dbeta;
       PCUDA_KEEP(p);
     }
-    PCUDA_KEEP(pgm);
-    const double scd = count == 1 ? 0.0 : g * isd;
-    shc[0][cx] = (float)scd;
-    shc[1][cx] = (float)(-scd * isd * S2 / count);
-    shc[2][cx] = (float)(-scd * S1 / count + scd * isd * (S2 / count) * md);
+    for (int k = 0; k < 3; ++k) shc[k][cx] = r.coef[k];
   }
   __syncthreads();
   if (!live) return;
@@ -200,15 +195,8 @@ __global__ __launch_bounds__(256) void bn1d_bwd_kernel(const float* __restrict__
   for (int i = ry; i < b; i += B1_RG) {
     const float* qa = pa + i * a_sn;
     const float* qd = pd + i * dy_sn;
-    const float av = *qa;
-    float gg = *qd, out;
-    if (post_relu) {
-      if (!(av * sc + sf > 0.f)) gg = 0.f;
-      out = c0 * gg + c1 * av + c2;
-    } else {
-      out = (c0 * gg + c1 * av + c2) * (av > 0.f ? 1.f : act_slope);
-    }
-    pz[i * dz_sn] = out;
+    const float av = *qa, gg = *qd;
+    pz[i * dz_sn] = bn_dz(bn_gate(gg, av, sc, sf, post_relu), av, c0, c1, c2, post_relu, act_slope);
     PCUDA_KEEP(qa); PCUDA_KEEP(qd);
   }
 }
@@ -238,11 +226,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_maxpts_kernel(const float* 
     if (post_relu) {
       const float* psc = scale + ch;
       const float* psf = shift + ch;
-      if (!(av * *psc + *psf > 0.f)) gg = 0.f;
+      gg = bn_gate(gg, av, *psc, *psf, 1);
       PCUDA_KEEP(psc); PCUDA_KEEP(psf);
     }
-    s1 = 0.f + gg;
-    s2 = 0.f + gg * ((av - m) * is);
+    bn_reduce_terms(gg, av, m, is, s1, s2);      // (onto 0.f: one value and the tile's zeros)
     PCUDA_KEEP(qa); PCUDA_KEEP(pm); PCUDA_KEEP(ps);
   }
   *(float2*)(red + 2ll * row) = make_float2(s1, s2);      // tile n, channel ch: red[(n * c + ch) * 2]
@@ -289,15 +276,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_maxpts_kernel(const float* _
       PCUDA_KEEP(psc); PCUDA_KEEP(psf);
     }
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float gg = (i0 + e == k) ? gv : 0.f;
-      if (post_relu) {
-        if (!(av[e] * sc + sf > 0.f)) gg = 0.f;
-        out[e] = c0 * gg + c1 * av[e] + c2;
-      } else {
-        out[e] = (c0 * gg + c1 * av[e] + c2) * (av[e] > 0.f ? 1.f : act_slope);
-      }
-    }
+    for (int e = 0; e < VEC; ++e)
+      out[e] = bn_dz(bn_gate((i0 + e == k) ? gv : 0.f, av[e], sc, sf, post_relu), av[e], c0, c1, c2, post_relu, act_slope);
     if (VEC == 4) *(float4*)(dz + e0 + o) = make_float4(out[0], out[1 % VEC], out[2 % VEC], out[3 % VEC]);
     else dz[e0 + o] = out[0];
     PCUDA_KEEP(qa); PCUDA_KEEP(pi); PCUDA_KEEP(pg); PCUDA_KEEP(pc);

@@ -3,6 +3,7 @@
 // 2x2 max pooling (unet.py:48), nearest-upsample backward (unet.py:111), running sums.
 // Tensors are [n][c][hw] with dense planes and explicit batch / channel strides.
 #include "common.h"
+#include "bn_device.h"      // the BatchNorm arithmetic and the fp64 tree, shared with pointnet_small.hip
 
 #ifndef PCH
 #define PCH 2048   // plane elements per workgroup (256 threads x 8)
@@ -85,35 +86,18 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
                                                           float* invstd, float* scale, float* shift) {
   __shared__ double sh[2][256];
   const int ch = blockIdx.x;
-  double s1, s2;
-  tile_pair_sum(partials, ntiles, c, ch, s1, s2);
-  sh[0][threadIdx.x] = s1;
-  sh[1][threadIdx.x] = s2;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  double s[2];
+  tile_pair_sum(partials, ntiles, c, ch, s[0], s[1]);
+  tree_sum_256(sh, s);
   if (threadIdx.x == 0) {
-    const double m = sh[0][0] / count;
-    double var = sh[1][0] / count - m * m;
-    // count == 1: the variance of one value is 0 by definition, not the rounding residue of the float32 a * a next to
-    // eps; the normalised value is then 0 and the output the constant beta, which scale = 0 states exactly
-    if (var < 0 || count <= 1) var = 0;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[ch] : 1.f, b = beta ? beta[ch] : 0.f;
-    mean[ch] = (float)m;
-    invstd[ch] = is;
-    const float sc = count > 1 ? g * is : 0.f;
-    scale[ch] = sc;
-    shift[ch] = b - (float)m * sc;
+    const BnFwd r = bn_fwd_finalize(sh[0][0], sh[1][0], count, gamma ? gamma[ch] : 1.f, beta ? beta[ch] : 0.f, eps);
+    mean[ch] = r.mean;
+    invstd[ch] = r.invstd;
+    scale[ch] = r.scale;
+    shift[ch] = r.shift;
     if (running_mean) {
-      const double unb = count > 1 ? var * count / (count - 1.0) : var;
-      running_mean[ch] = (1.f - momentum) * running_mean[ch] + momentum * (float)m;
-      running_var[ch] = (1.f - momentum) * running_var[ch] + momentum * (float)unb;
+      running_mean[ch] = bn_running(running_mean[ch], momentum, r.mean);
+      running_var[ch] = bn_running(running_var[ch], momentum, bn_unbiased(r.var, count));
     }
   }
 }
@@ -180,43 +164,67 @@ __device__ __forceinline__ void pool_load(const PoolSrc& ps, int n, int ch, long
   PCUDA_KEEP(pg); PCUDA_KEEP(pg2); PCUDA_KEEP(pi);      // (VMEM address rule, common.h)
 }
 
-template <int VEC, bool POOL = false>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
-    const float* __restrict__ dy, long long dy_sn, long long dy_sc, const float* __restrict__ dy2, long long dy2_sn,
-    long long dy2_sc, const float* __restrict__ a, long long a_sn, long long a_sc, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ scale, const float* __restrict__ shift, int post_relu,
-    long long hw, int c, float* __restrict__ red, PoolSrc ps) {
-  __shared__ float sh[4];
-  const int ch = blockIdx.y, n = blockIdx.z;
-  const float* pd = dy ? dy + n * dy_sn + ch * dy_sc : nullptr;     // (POOL: the full-resolution share is optional)
-  const float* pd2 = dy2 ? dy2 + n * dy2_sn + ch * dy2_sc : nullptr;
-  const float* pa = a + n * a_sn + ch * a_sc;
-  const float m = mean[ch], is = invstd[ch];
-  const float sc = post_relu ? scale[ch] : 0.f, sf = post_relu ? shift[ch] : 0.f;
-  const long long i0 = (long long)blockIdx.x * PCH, i1 = min(hw, i0 + PCH);
-  float s1 = 0.f, s2 = 0.f;
-  for (long long i = i0 + threadIdx.x * VEC; i < i1; i += 256 * VEC) {
-    float av[VEC], g[VEC], g2[VEC];
+// What the three backward kernels read: the activation a and the gradient (pooled scatter + dy) + dy2 -- the pooled source
+// in the POOL instantiations only, dy optional there, dy2 optional everywhere.  Built by the host entry.
+template <class T> struct Planes { T* p; long long sn, sc; };
+struct GradSrc { Planes<const float> dy, dy2, a; long long hw; PoolSrc ps; };
+// As kernel parameters the source travels as scalars, its nine plane scalars first and `long long hw, PoolSrc ps` behind the
+// kernel's own (GRAD_PARAMS in the signature, GRAD_SRC in the body, GRAD_ARGS(src) at the launch): the small-plane launches are
+// prologue-bound, and both a by-value struct and another order of these arguments cost lrelu_bwd at 16 x 16 planes 1 - 3 %
+// (profiles/pointwise_refactor_ab.json).
+#define GRAD_PARAMS                                                                                                  \
+  const float *__restrict__ dy, long long dy_sn, long long dy_sc, const float *__restrict__ dy2, long long dy2_sn,   \
+      long long dy2_sc, const float *__restrict__ a, long long a_sn, long long a_sc
+#define GRAD_SRC (GradSrc{{dy, dy_sn, dy_sc}, {dy2, dy2_sn, dy2_sc}, {a, a_sn, a_sc}, hw, ps})
+#define GRAD_ARGS(s) (s).dy.p, (s).dy.sn, (s).dy.sc, (s).dy2.p, (s).dy2.sn, (s).dy2.sc, (s).a.p, (s).a.sn, (s).a.sc
+template <class T> __device__ __forceinline__ T* plane_of(const Planes<T>& t) {      // this workgroup's plane; none stays none
+  return t.p ? t.p + blockIdx.z * t.sn + blockIdx.y * t.sc : nullptr;
+}
+// one workgroup's tile of a GradSrc: elements i0, i0 + 256 * VEC, ... below i1 are this thread's
+template <int VEC, bool POOL>
+struct GradTile {
+  const float *pd, *pd2, *pa;
+  long long i0, i1;
+  __device__ __forceinline__ explicit GradTile(const GradSrc& s)
+      : pd(plane_of(s.dy)), pd2(plane_of(s.dy2)), pa(s.a.p + blockIdx.z * s.a.sn + blockIdx.y * s.a.sc),
+        i0((long long)blockIdx.x * PCH + threadIdx.x * VEC), i1(min(s.hw, (long long)blockIdx.x * PCH + PCH)) {}
+  __device__ __forceinline__ void load(const GradSrc& s, long long i, float (&av)[VEC], float (&g)[VEC]) const {
     vload<VEC>(pa + i, av);
     if (POOL) {
-      pool_load<VEC>(ps, n, ch, i, g);
-      if (pd) {
-        vload<VEC>(pd + i, g2);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) g[e] += g2[e];
-      }
+      pool_load<VEC>(s.ps, blockIdx.z, blockIdx.y, i, g);
+      if (pd) add_share(pd + i, g);
     } else {
       vload<VEC>(pd + i, g);
     }
-    if (pd2) vload<VEC>(pd2 + i, g2);
+    if (pd2) add_share(pd2 + i, g);
+  }
+  __device__ __forceinline__ static void add_share(const float* q, float (&g)[VEC]) {
+    float g2[VEC];
+    vload<VEC>(q, g2);
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float gg = pd2 ? g[e] + g2[e] : g[e];
-      if (post_relu && !(av[e] * sc + sf > 0.f)) gg = 0.f;
-      s1 += gg;
-      s2 += gg * ((av[e] - m) * is);
-    }
-    if (POOL) { PCUDA_KEEP(pa + i); PCUDA_KEEP(pd2 + i); }
+    for (int e = 0; e < VEC; ++e) g[e] += g2[e];
+    if (POOL) PCUDA_KEEP(q);      // (VMEM address rule, common.h: held until the share is consumed, as pool_load does)
+  }
+  __device__ __forceinline__ void keep(long long i) const { if (POOL) PCUDA_KEEP(pa + i); }      // a's, once consumed
+};
+
+template <int VEC, bool POOL>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(GRAD_PARAMS, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            int post_relu, long long hw, int c, float* __restrict__ red, PoolSrc ps) {
+  __shared__ float sh[4];
+  const int ch = blockIdx.y, n = blockIdx.z;
+  const GradSrc src = GRAD_SRC;
+  const GradTile<VEC, POOL> t(src);
+  const float m = mean[ch], is = invstd[ch];
+  const float sc = post_relu ? scale[ch] : 0.f, sf = post_relu ? shift[ch] : 0.f;
+  float s1 = 0.f, s2 = 0.f;
+  for (long long i = t.i0; i < t.i1; i += 256 * VEC) {
+    float av[VEC], g[VEC];
+    t.load(src, i, av, g);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) bn_reduce_terms(bn_gate(g[e], av[e], sc, sf, post_relu), av[e], m, is, s1, s2);
+    t.keep(i);
   }
   s1 = block_sum(s1, sh);
   s2 = block_sum(s2, sh);
@@ -234,110 +242,52 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
                                                               float* dbeta, int accumulate, float* coef) {
   __shared__ double sh[2][256];
   const int ch = blockIdx.x;
-  double s1, s2;
-  tile_pair_sum(red, ntiles, c, ch, s1, s2);
-  sh[0][threadIdx.x] = s1;
-  sh[1][threadIdx.x] = s2;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  double s[2];
+  tile_pair_sum(red, ntiles, c, ch, s[0], s[1]);
+  tree_sum_256(sh, s);
   if (threadIdx.x == 0) {
-    const double S1 = sh[0][0], S2 = sh[1][0];
-    if (dgamma) dgamma[ch] = accumulate ? dgamma[ch] + (float)S2 : (float)S2;
-    if (dbeta) dbeta[ch] = accumulate ? dbeta[ch] + (float)S1 : (float)S1;
-    const double g = gamma ? (double)gamma[ch] : 1.0, is = invstd[ch], m = mean[ch];
-    // count == 1: the output of a training BatchNorm over one value is the constant beta, its input gradient exactly 0
-    // (the three terms below would leave the rounding residue of sc * S1 instead)
-    const double sc = count == 1 ? 0.0 : g * is;
-    coef[ch * 3 + 0] = (float)sc;
-    // count < 0: FROZEN statistics (eval-mode BatchNorm, mean / invstd from the running buffers): the layer is a fixed
-    // per-channel affine, the batch-mean terms of the training formula vanish; dgamma / dbeta are the same sums
-    coef[ch * 3 + 1] = count < 0 ? 0.f : (float)(-sc * is * S2 / count);
-    coef[ch * 3 + 2] = count < 0 ? 0.f : (float)(-sc * S1 / count + sc * is * (S2 / count) * m);
+    const BnBwd r = bn_bwd_finalize(sh[0][0], sh[1][0], count, gamma ? (double)gamma[ch] : 1.0, invstd[ch], mean[ch]);
+    if (dgamma) dgamma[ch] = accumulate ? dgamma[ch] + r.dgamma : r.dgamma;
+    if (dbeta) dbeta[ch] = accumulate ? dbeta[ch] + r.dbeta : r.dbeta;
+    for (int k = 0; k < 3; ++k) coef[ch * 3 + k] = r.coef[k];
   }
 }
 
-template <int VEC, bool POOL = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
-    const float* __restrict__ dy, long long dy_sn, long long dy_sc, const float* __restrict__ dy2, long long dy2_sn,
-    long long dy2_sc, const float* __restrict__ a, long long a_sn, long long a_sc, const float* __restrict__ coef,
-    const float* __restrict__ scale, const float* __restrict__ shift, int post_relu, float act_slope,
-    float* __restrict__ dz, long long dz_sn, long long dz_sc, long long hw, PoolSrc ps) {
-  const int ch = blockIdx.y, n = blockIdx.z;
-  const float* pd = dy ? dy + n * dy_sn + ch * dy_sc : nullptr;
-  const float* pd2 = dy2 ? dy2 + n * dy2_sn + ch * dy2_sc : nullptr;
-  const float* pa = a + n * a_sn + ch * a_sc;
-  float* pz = dz + n * dz_sn + ch * dz_sc;
+template <int VEC, bool POOL>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(GRAD_PARAMS, const float* __restrict__ coef,
+                                                           const float* __restrict__ scale,
+                                                           const float* __restrict__ shift, int post_relu,
+                                                           float act_slope, float* __restrict__ dz,
+                                                           long long dz_sn, long long dz_sc, long long hw, PoolSrc ps) {
+  const int ch = blockIdx.y;
+  const GradSrc src = GRAD_SRC;
+  const GradTile<VEC, POOL> t(src);
+  float* pz = dz + blockIdx.z * dz_sn + ch * dz_sc;
   const float c0 = coef[ch * 3 + 0], c1 = coef[ch * 3 + 1], c2 = coef[ch * 3 + 2];
   const float sc = post_relu ? scale[ch] : 0.f, sf = post_relu ? shift[ch] : 0.f;
-  const long long i0 = (long long)blockIdx.x * PCH, i1 = min(hw, i0 + PCH);
-  for (long long i = i0 + threadIdx.x * VEC; i < i1; i += 256 * VEC) {
-    float av[VEC], g[VEC], g2[VEC], out[VEC];
-    vload<VEC>(pa + i, av);
-    if (POOL) {
-      pool_load<VEC>(ps, n, ch, i, g);
-      if (pd) {
-        vload<VEC>(pd + i, g2);
+  for (long long i = t.i0; i < t.i1; i += 256 * VEC) {
+    float av[VEC], g[VEC], out[VEC];
+    t.load(src, i, av, g);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) g[e] += g2[e];
-      }
-    } else {
-      vload<VEC>(pd + i, g);
-    }
-    if (pd2) vload<VEC>(pd2 + i, g2);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float gg = pd2 ? g[e] + g2[e] : g[e];
-      if (post_relu) {
-        if (!(av[e] * sc + sf > 0.f)) gg = 0.f;
-        out[e] = c0 * gg + c1 * av[e] + c2;
-      } else {
-        out[e] = (c0 * gg + c1 * av[e] + c2) * (av[e] > 0.f ? 1.f : act_slope);
-      }
-    }
+    for (int e = 0; e < VEC; ++e) out[e] = bn_dz(bn_gate(g[e], av[e], sc, sf, post_relu), av[e], c0, c1, c2, post_relu, act_slope);
     vstore<VEC>(pz + i, out);
-    if (POOL) { PCUDA_KEEP(pa + i); PCUDA_KEEP(pd2 + i); }
+    t.keep(i);
   }
 }
 
-template <int VEC, bool POOL = false>
-__global__ __launch_bounds__(256) void lrelu_bwd_kernel(const float* __restrict__ dy, long long dy_sn, long long dy_sc,
-                                                        const float* __restrict__ dy2, long long dy2_sn,
-                                                        long long dy2_sc, const float* __restrict__ a, long long a_sn,
-                                                        long long a_sc, float slope, float* __restrict__ dz,
+template <int VEC, bool POOL>
+__global__ __launch_bounds__(256) void lrelu_bwd_kernel(GRAD_PARAMS, float slope, float* __restrict__ dz,
                                                         long long dz_sn, long long dz_sc, long long hw, PoolSrc ps) {
-  const int ch = blockIdx.y, n = blockIdx.z;
-  const float* pd = dy ? dy + n * dy_sn + ch * dy_sc : nullptr;
-  const float* pd2 = dy2 ? dy2 + n * dy2_sn + ch * dy2_sc : nullptr;
-  const float* pa = a + n * a_sn + ch * a_sc;
-  float* pz = dz + n * dz_sn + ch * dz_sc;
-  const long long i0 = (long long)blockIdx.x * PCH, i1 = min(hw, i0 + PCH);
-  for (long long i = i0 + threadIdx.x * VEC; i < i1; i += 256 * VEC) {
-    float av[VEC], g[VEC], g2[VEC], out[VEC];
-    vload<VEC>(pa + i, av);
-    if (POOL) {
-      pool_load<VEC>(ps, n, ch, i, g);
-      if (pd) {
-        vload<VEC>(pd + i, g2);
+  const GradSrc src = GRAD_SRC;
+  const GradTile<VEC, POOL> t(src);
+  float* pz = dz + blockIdx.z * dz_sn + blockIdx.y * dz_sc;
+  for (long long i = t.i0; i < t.i1; i += 256 * VEC) {
+    float av[VEC], g[VEC], out[VEC];
+    t.load(src, i, av, g);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) g[e] += g2[e];
-      }
-    } else {
-      vload<VEC>(pd + i, g);
-    }
-    if (pd2) vload<VEC>(pd2 + i, g2);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const float gg = pd2 ? g[e] + g2[e] : g[e];
-      out[e] = av[e] > 0.f ? gg : gg * slope;
-    }
+    for (int e = 0; e < VEC; ++e) out[e] = av[e] > 0.f ? g[e] : g[e] * slope;
     vstore<VEC>(pz + i, out);
-    if (POOL) { PCUDA_KEEP(pa + i); PCUDA_KEEP(pd2 + i); }
+    t.keep(i);
   }
 }
 
@@ -356,17 +306,12 @@ __global__ __launch_bounds__(256) void channel_sum_partial_kernel(const float* _
 
 __global__ __launch_bounds__(256) void channel_sum_final_kernel(const float* __restrict__ part, int ntiles, int c,
                                                                 float* db, int accumulate) {
-  __shared__ double sh[256];
+  __shared__ double sh[1][256];
   const int ch = blockIdx.x;
-  double s = 0;
-  for (int t = threadIdx.x; t < ntiles; t += 256) s += (double)part[(long long)t * c + ch];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) db[ch] = accumulate ? db[ch] + (float)sh[0] : (float)sh[0];
+  double s[1] = {0};
+  for (int t = threadIdx.x; t < ntiles; t += 256) s[0] += (double)part[(long long)t * c + ch];
+  tree_sum_256(sh, s);
+  if (threadIdx.x == 0) db[ch] = accumulate ? db[ch] + (float)sh[0][0] : (float)sh[0][0];
 }
 
 // ---------------------------------------------------------------------------- pooling / resampling
@@ -569,7 +514,41 @@ __global__ __launch_bounds__(256) void mul_kernel(const float* __restrict__ a, c
 namespace {
 inline bool dims_ok(int n, int c, long long hw) { return n > 0 && c > 0 && hw > 0 && n <= 65535 && c <= 65535; }
 inline dim3 plane_grid(int n, int c, long long hw) { return dim3((unsigned)cdiv(hw, PCH), (unsigned)c, (unsigned)n); }
+
+// ---- the gradient source of the three backward kernels (GradSrc above), plain or through a 2x2 max-pool (pcuda_pooled)
+inline GradSrc grad_src(const float* dy, long long dy_sn, long long dy_sc, const float* dy2, long long dy2_sn,
+                        long long dy2_sc, const float* a, long long a_sn, long long a_sc, long long hw) {
+  GradSrc g{};
+  g.dy = {dy, dy_sn, dy_sc}; g.dy2 = {dy2, dy2_sn, dy2_sc}; g.a = {a, a_sn, a_sc}; g.hw = hw;
+  return g;
+}
+int pool_src(const pcuda_pooled* p, int n, int c, PoolSrc& ps, const char* who) {
+  if (!p || !p->g || !p->idx || p->h <= 0 || p->w <= 0 || (p->h & 1) || (p->w & 1) || !dims_ok(n, c, (long long)p->h * p->w))
+    PCUDA_FAIL(PCUDA_E_BADARG, "%s: bad pooled source (even plane, g and idx required)", who);
+  ps.g = p->g; ps.sn = p->g_sn; ps.sc = p->g_sc;
+  ps.g2 = p->g2; ps.sn2 = p->g2_sn; ps.sc2 = p->g2_sc;
+  ps.idx = p->idx; ps.w = p->w; ps.c = c; ps.ohw = (long long)(p->h >> 1) * (p->w >> 1);
+  return PCUDA_OK;
+}
+// float2 reads of g / g2 and 2-byte reads of idx at even pooled offsets: rows a multiple of 4 wide, even strides, aligned bases
+bool pool_vec_ok(const PoolSrc& p) {
+  auto ok = [](const void* q, long long sn, long long sc) { return q == nullptr || (((uintptr_t)q & 7) == 0 && ((sn | sc) & 1) == 0); };
+  return (p.w & 3) == 0 && ok(p.g, p.sn, p.sc) && ok(p.g2, p.sn2, p.sc2) && ((uintptr_t)p.idx & 1) == 0 && (p.ohw & 1) == 0;
+}
+// the 16-B path: every plane the kernel touches (dz: none for the reduce) and the pooled source, where there is one
+bool grad_vec_ok(const GradSrc& g, const Planes<float>& dz) {
+  return vec_ok(g.dy.p, g.dy.sn, g.dy.sc, g.hw) && vec_ok(g.dy2.p, g.dy2.sn, g.dy2.sc, g.hw) &&
+         vec_ok(g.a.p, g.a.sn, g.a.sc, g.hw) && vec_ok(dz.p, dz.sn, dz.sc, g.hw) && (!g.ps.g || pool_vec_ok(g.ps));
+}
 }  // namespace
+
+// One launch of a backward kernel template over the planes of `src`: the POOL instantiation where the source has a pooled
+// part, VEC = 4 where `vec`.
+#define LAUNCH_GRAD(kern, vec, n, c, s, src, ...)                                                                 \
+  do {                                                                                                            \
+    auto k_ = (src).ps.g ? ((vec) ? kern<4, true> : kern<1, true>) : ((vec) ? kern<4, false> : kern<1, false>);   \
+    hipLaunchKernelGGL(k_, plane_grid(n, c, (src).hw), dim3(256), 0, (hipStream_t)(s), GRAD_ARGS(src), __VA_ARGS__);          \
+  } while (0)
 
 extern "C" int pcuda_bn_stats(const float* a, long long sn, long long sc, int n, int c, long long hw,
                               float* partials, int* ntiles, pcuda_stream_t s) {
@@ -623,12 +602,8 @@ extern "C" int pcuda_bn_bwd_reduce(const float* dy, long long dy_sn, long long d
   if (!dy || !a || !mean || !invstd || (post_relu && (!scale || !shift)))
     PCUDA_FAIL(PCUDA_E_BADARG, "bn_bwd_reduce: null pointer");
   ProfScope prof(PCUDA_FAM_POINTWISE, (dy2 ? 12.0 : 8.0) * n * c * (double)hw, (hipStream_t)s);
-  if (vec_ok(dy, dy_sn, dy_sc, hw) && vec_ok(dy2, dy2_sn, dy2_sc, hw) && vec_ok(a, a_sn, a_sc, hw))
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, dy, dy_sn, dy_sc,
-                       dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, mean, invstd, scale, shift, post_relu, hw, c, red, PoolSrc{});
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, dy, dy_sn, dy_sc,
-                       dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, mean, invstd, scale, shift, post_relu, hw, c, red, PoolSrc{});
+  const GradSrc src = grad_src(dy, dy_sn, dy_sc, dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, hw);
+  LAUNCH_GRAD(bn_bwd_reduce_kernel, grad_vec_ok(src, {}), n, c, s, src, mean, invstd, scale, shift, post_relu, src.hw, c, red, src.ps);
   PCUDA_CHECK_LAUNCH("bn_bwd_reduce_kernel");
   return PCUDA_OK;
 }
@@ -652,13 +627,9 @@ extern "C" int pcuda_bn_bwd_apply(const float* dy, long long dy_sn, long long dy
   if (!dims_ok(n, c, hw) || !dy || !a || !coef || !dz || (post_relu && (!scale || !shift)))
     PCUDA_FAIL(PCUDA_E_BADARG, "bn_bwd_apply: bad arguments");
   ProfScope prof(PCUDA_FAM_POINTWISE, (dy2 ? 16.0 : 12.0) * n * c * (double)hw, (hipStream_t)s);
-  if (vec_ok(dy, dy_sn, dy_sc, hw) && vec_ok(dy2, dy2_sn, dy2_sc, hw) && vec_ok(a, a_sn, a_sc, hw) &&
-      vec_ok(dz, dz_sn, dz_sc, hw))
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, dy, dy_sn, dy_sc,
-                       dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, coef, scale, shift, post_relu, act_slope, dz, dz_sn, dz_sc, hw, PoolSrc{});
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, dy, dy_sn, dy_sc,
-                       dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, coef, scale, shift, post_relu, act_slope, dz, dz_sn, dz_sc, hw, PoolSrc{});
+  const GradSrc src = grad_src(dy, dy_sn, dy_sc, dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, hw);
+  const Planes<float> out{dz, dz_sn, dz_sc};
+  LAUNCH_GRAD(bn_bwd_apply_kernel, grad_vec_ok(src, out), n, c, s, src, coef, scale, shift, post_relu, act_slope, out.p, out.sn, out.sc, src.hw, src.ps);
   PCUDA_CHECK_LAUNCH("bn_bwd_apply_kernel");
   return PCUDA_OK;
 }
@@ -677,39 +648,20 @@ extern "C" int pcuda_lrelu_bwd(const float* dy, long long dy_sn, long long dy_sc
   const long long total = (long long)n * c * hw;
   if ((hw & 3) && (total & 3) == 0 && dense(dy, dy_sn, dy_sc) && dense(dy2, dy2_sn, dy2_sc) && dense(a, a_sn, a_sc) &&
       dense(dz, dz_sn, dz_sc)) {
-    hipLaunchKernelGGL(lrelu_bwd_kernel<4>, plane_grid(1, 1, total), dim3(256), 0, (hipStream_t)s, dy, total, total, dy2,
-                       total, total, a, total, total, slope, dz, total, total, total, PoolSrc{});
+    const GradSrc flat = grad_src(dy, total, total, dy2, total, total, a, total, total, total);
+    LAUNCH_GRAD(lrelu_bwd_kernel, true, 1, 1, s, flat, slope, dz, total, total, total, flat.ps);
     PCUDA_CHECK_LAUNCH("lrelu_bwd_kernel");
     return PCUDA_OK;
   }
-  if (vec_ok(dy, dy_sn, dy_sc, hw) && vec_ok(dy2, dy2_sn, dy2_sc, hw) && vec_ok(a, a_sn, a_sc, hw) &&
-      vec_ok(dz, dz_sn, dz_sc, hw))
-    hipLaunchKernelGGL(lrelu_bwd_kernel<4>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, dy, dy_sn, dy_sc, dy2,
-                       dy2_sn, dy2_sc, a, a_sn, a_sc, slope, dz, dz_sn, dz_sc, hw, PoolSrc{});
-  else
-    hipLaunchKernelGGL(lrelu_bwd_kernel<1>, plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, dy, dy_sn, dy_sc, dy2,
-                       dy2_sn, dy2_sc, a, a_sn, a_sc, slope, dz, dz_sn, dz_sc, hw, PoolSrc{});
+  const GradSrc src = grad_src(dy, dy_sn, dy_sc, dy2, dy2_sn, dy2_sc, a, a_sn, a_sc, hw);
+  const Planes<float> out{dz, dz_sn, dz_sc};
+  LAUNCH_GRAD(lrelu_bwd_kernel, grad_vec_ok(src, out), n, c, s, src, slope, out.p, out.sn, out.sc, src.hw, src.ps);
   PCUDA_CHECK_LAUNCH("lrelu_bwd_kernel");
   return PCUDA_OK;
 }
 
 // ---- the same three kernels with the gradient arriving through a 2x2 max-pool (PoolSrc above): `dy` here is the OPTIONAL
 // full-resolution share added to the scattered one (the encoder's skip gradient)
-static int pool_src(const pcuda_pooled* p, int n, int c, PoolSrc& ps, const char* who) {
-  if (!p || !p->g || !p->idx || p->h <= 0 || p->w <= 0 || (p->h & 1) || (p->w & 1) || !dims_ok(n, c, (long long)p->h * p->w))
-    PCUDA_FAIL(PCUDA_E_BADARG, "%s: bad pooled source (even plane, g and idx required)", who);
-  ps.g = p->g; ps.sn = p->g_sn; ps.sc = p->g_sc;
-  ps.g2 = p->g2; ps.sn2 = p->g2_sn; ps.sc2 = p->g2_sc;
-  ps.idx = p->idx; ps.w = p->w; ps.c = c; ps.ohw = (long long)(p->h >> 1) * (p->w >> 1);
-  return PCUDA_OK;
-}
-// float2 reads of g / g2 and 2-byte reads of idx at even pooled offsets: rows a multiple of 4 wide, even strides, aligned bases
-static bool pool_vec_ok(const pcuda_pooled* p) {
-  auto ok = [](const void* q, long long sn, long long sc) { return q == nullptr || (((uintptr_t)q & 7) == 0 && ((sn | sc) & 1) == 0); };
-  return (p->w & 3) == 0 && ok(p->g, p->g_sn, p->g_sc) && ok(p->g2, p->g2_sn, p->g2_sc) && ((uintptr_t)p->idx & 1) == 0 &&
-         ((((long long)(p->h >> 1) * (p->w >> 1)) & 1) == 0);
-}
-
 extern "C" int pcuda_bn_bwd_reduce_pooled(const pcuda_pooled* pool, const float* dy, long long dy_sn, long long dy_sc,
                                           const float* a, long long a_sn, long long a_sc, const float* mean,
                                           const float* invstd, int n, int c, float* red, int* ntiles, pcuda_stream_t s) {
@@ -719,16 +671,11 @@ extern "C" int pcuda_bn_bwd_reduce_pooled(const pcuda_pooled* pool, const float*
   const int nt = n * cdiv(hw, PCH);
   if (ntiles) *ntiles = nt;
   if (!red) return PCUDA_OK;
-  PoolSrc ps{};
-  if (int rc = pool_src(pool, n, c, ps, "bn_bwd_reduce_pooled")) return rc;
+  GradSrc src = grad_src(nullptr, 0, 0, dy, dy_sn, dy_sc, a, a_sn, a_sc, hw);
+  if (int rc = pool_src(pool, n, c, src.ps, "bn_bwd_reduce_pooled")) return rc;
   if (!a || !mean || !invstd) PCUDA_FAIL(PCUDA_E_BADARG, "bn_bwd_reduce_pooled: null pointer");
   ProfScope prof(PCUDA_FAM_POINTWISE, ((dy ? 8.0 : 4.0) + (pool->g2 ? 2.25 : 1.25)) * n * c * (double)hw, (hipStream_t)s);
-  if (pool_vec_ok(pool) && vec_ok(dy, dy_sn, dy_sc, hw) && vec_ok(a, a_sn, a_sc, hw))
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<4, true>), plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, nullptr, 0, 0,
-                       dy, dy_sn, dy_sc, a, a_sn, a_sc, mean, invstd, nullptr, nullptr, 0, hw, c, red, ps);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<1, true>), plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, nullptr, 0, 0,
-                       dy, dy_sn, dy_sc, a, a_sn, a_sc, mean, invstd, nullptr, nullptr, 0, hw, c, red, ps);
+  LAUNCH_GRAD(bn_bwd_reduce_kernel, grad_vec_ok(src, {}), n, c, s, src, mean, invstd, nullptr, nullptr, 0, src.hw, c, red, src.ps);
   PCUDA_CHECK_LAUNCH("bn_bwd_reduce_kernel<pooled>");
   return PCUDA_OK;
 }
@@ -737,17 +684,14 @@ extern "C" int pcuda_bn_bwd_apply_pooled(const pcuda_pooled* pool, const float* 
                                          const float* a, long long a_sn, long long a_sc, const float* coef,
                                          float act_slope, float* dz, long long dz_sn, long long dz_sc, int n, int c,
                                          pcuda_stream_t s) {
-  PoolSrc ps{};
-  if (int rc = pool_src(pool, n, c, ps, "bn_bwd_apply_pooled")) return rc;
+  GradSrc src{};
+  if (int rc = pool_src(pool, n, c, src.ps, "bn_bwd_apply_pooled")) return rc;
   if (!a || !coef || !dz) PCUDA_FAIL(PCUDA_E_BADARG, "bn_bwd_apply_pooled: null pointer");
   const long long hw = (long long)pool->h * pool->w;
   ProfScope prof(PCUDA_FAM_POINTWISE, ((dy ? 12.0 : 8.0) + (pool->g2 ? 2.25 : 1.25)) * n * c * (double)hw, (hipStream_t)s);
-  if (pool_vec_ok(pool) && vec_ok(dy, dy_sn, dy_sc, hw) && vec_ok(a, a_sn, a_sc, hw) && vec_ok(dz, dz_sn, dz_sc, hw))
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, nullptr, 0, 0, dy,
-                       dy_sn, dy_sc, a, a_sn, a_sc, coef, nullptr, nullptr, 0, act_slope, dz, dz_sn, dz_sc, hw, ps);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<1, true>), plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, nullptr, 0, 0, dy,
-                       dy_sn, dy_sc, a, a_sn, a_sc, coef, nullptr, nullptr, 0, act_slope, dz, dz_sn, dz_sc, hw, ps);
+  src.dy2 = {dy, dy_sn, dy_sc}; src.a = {a, a_sn, a_sc}; src.hw = hw;
+  const Planes<float> out{dz, dz_sn, dz_sc};
+  LAUNCH_GRAD(bn_bwd_apply_kernel, grad_vec_ok(src, out), n, c, s, src, coef, nullptr, nullptr, 0, act_slope, out.p, out.sn, out.sc, src.hw, src.ps);
   PCUDA_CHECK_LAUNCH("bn_bwd_apply_kernel<pooled>");
   return PCUDA_OK;
 }
@@ -755,17 +699,14 @@ extern "C" int pcuda_bn_bwd_apply_pooled(const pcuda_pooled* pool, const float* 
 extern "C" int pcuda_lrelu_bwd_pooled(const pcuda_pooled* pool, const float* dy, long long dy_sn, long long dy_sc,
                                       const float* a, long long a_sn, long long a_sc, float slope, float* dz,
                                       long long dz_sn, long long dz_sc, int n, int c, pcuda_stream_t s) {
-  PoolSrc ps{};
-  if (int rc = pool_src(pool, n, c, ps, "lrelu_bwd_pooled")) return rc;
+  GradSrc src{};
+  if (int rc = pool_src(pool, n, c, src.ps, "lrelu_bwd_pooled")) return rc;
   if (!a || !dz) PCUDA_FAIL(PCUDA_E_BADARG, "lrelu_bwd_pooled: null pointer");
   const long long hw = (long long)pool->h * pool->w;
   ProfScope prof(PCUDA_FAM_POINTWISE, ((dy ? 12.0 : 8.0) + (pool->g2 ? 2.25 : 1.25)) * n * c * (double)hw, (hipStream_t)s);
-  if (pool_vec_ok(pool) && vec_ok(dy, dy_sn, dy_sc, hw) && vec_ok(a, a_sn, a_sc, hw) && vec_ok(dz, dz_sn, dz_sc, hw))
-    hipLaunchKernelGGL((lrelu_bwd_kernel<4, true>), plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, nullptr, 0, 0, dy,
-                       dy_sn, dy_sc, a, a_sn, a_sc, slope, dz, dz_sn, dz_sc, hw, ps);
-  else
-    hipLaunchKernelGGL((lrelu_bwd_kernel<1, true>), plane_grid(n, c, hw), dim3(256), 0, (hipStream_t)s, nullptr, 0, 0, dy,
-                       dy_sn, dy_sc, a, a_sn, a_sc, slope, dz, dz_sn, dz_sc, hw, ps);
+  src.dy2 = {dy, dy_sn, dy_sc}; src.a = {a, a_sn, a_sc}; src.hw = hw;
+  const Planes<float> out{dz, dz_sn, dz_sc};
+  LAUNCH_GRAD(lrelu_bwd_kernel, grad_vec_ok(src, out), n, c, s, src, slope, out.p, out.sn, out.sc, src.hw, src.ps);
   PCUDA_CHECK_LAUNCH("lrelu_bwd_kernel<pooled>");
   return PCUDA_OK;
 }

@@ -470,12 +470,30 @@ class BNState:
     """per-forward statistics of one BatchNorm layer"""
     __slots__ = ("mean", "invstd", "scale", "shift", "count")
 
+    @classmethod
+    def empty(cls, c, count, device):
+        """the four [c] vectors a finalize kernel fills (one buffer) and the element count they stand for"""
+        st = cls()
+        buf = torch.empty((4, c), dtype=torch.float32, device=device)
+        st.mean, st.invstd, st.scale, st.shift, st.count = buf[0], buf[1], buf[2], buf[3], count
+        return st
+
+
+def _opt_planes(t: Optional[torch.Tensor]):
+    """(pointer, batch stride, channel stride) of an optional [N,C,...] tensor; (None, 0, 0) where there is none"""
+    return (None, 0, 0) if t is None else (t.data_ptr(),) + _planes(t)[3:]
+
+
+def _ntiles(n, c, hw):
+    """tiles of n x c planes of hw elements as the library counts them (pcuda_bn_stats' query form: nothing is launched)"""
+    nt = C.c_int(0)
+    check(L.lib().pcuda_bn_stats(None, 0, 0, n, c, hw, None, C.byref(nt), None), "bn_stats(query)")
+    return nt.value
+
 
 def bn_finalize(partials, ntiles, count, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1) -> BNState:
     c = partials.shape[1]
-    st = BNState()
-    buf = torch.empty((4, c), dtype=torch.float32, device=partials.device)
-    st.mean, st.invstd, st.scale, st.shift, st.count = buf[0], buf[1], buf[2], buf[3], count
+    st = BNState.empty(c, count, partials.device)
     check(L.lib().pcuda_bn_finalize(partials.data_ptr(), ntiles, c, count, _ptr(gamma), _ptr(beta), eps, momentum,
                                     _ptr(running_mean), _ptr(running_var), st.mean.data_ptr(), st.invstd.data_ptr(),
                                     st.scale.data_ptr(), st.shift.data_ptr(), _stream()), "bn_finalize")
@@ -484,12 +502,10 @@ def bn_finalize(partials, ntiles, count, gamma, beta, running_mean, running_var,
 
 def bn_stats(a: torch.Tensor):
     n, c, hw, sn, sc = _planes(a)
-    nt = C.c_int(0)
-    lib = L.lib()
-    check(lib.pcuda_bn_stats(None, sn, sc, n, c, hw, None, C.byref(nt), _stream()), "bn_stats(query)")
-    partials = torch.empty((nt.value, c, 2), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_stats(a.data_ptr(), sn, sc, n, c, hw, partials.data_ptr(), C.byref(nt), _stream()), "bn_stats")
-    return partials, nt.value, n * hw
+    nt = _ntiles(n, c, hw)
+    partials = torch.empty((nt, c, 2), dtype=torch.float32, device=a.device)
+    check(L.lib().pcuda_bn_stats(a.data_ptr(), sn, sc, n, c, hw, partials.data_ptr(), None, _stream()), "bn_stats")
+    return partials, nt, n * hw
 
 
 def bn_apply(a: torch.Tensor, st: BNState, relu=False, out=None, fma=False):
@@ -523,9 +539,7 @@ def bn1d_forward(a, gamma, beta, running_mean, running_var, relu=False, eps=1e-5
     if not _bn1d_ok(a):
         return None
     b, c = a.shape
-    st = BNState()
-    buf = torch.empty((4, c), dtype=torch.float32, device=a.device)
-    st.mean, st.invstd, st.scale, st.shift, st.count = buf[0], buf[1], buf[2], buf[3], b
+    st = BNState.empty(c, b, a.device)
     y = torch.empty((b, c), dtype=torch.float32, device=a.device)
     check(L.lib().pcuda_bn1d_fwd(a.data_ptr(), a.stride(0), b, c, _ptr(gamma), _ptr(beta), eps, momentum,
                                  _ptr(running_mean), _ptr(running_var), st.mean.data_ptr(), st.invstd.data_ptr(),
@@ -551,45 +565,47 @@ def bn_backward(dy, a, st: BNState, gamma, dgamma, dbeta, dy2=None, post_relu=Fa
                                      1 if accumulate else 0, dz.data_ptr(), dz.stride(0), _stream()), "bn1d_bwd")
         return dz
     n, c, hw, asn, asc = _planes(a)
-    _, _, _, dsn, dsc = _planes(dy)
-    d2p, d2sn, d2sc = None, 0, 0
-    if dy2 is not None:
-        _, _, _, d2sn, d2sc = _planes(dy2)
-        d2p = dy2.data_ptr()
+    dyp, d2p = _opt_planes(dy), _opt_planes(dy2)
     lib = L.lib()
     pr = 1 if post_relu else 0
     if red is not None:          # (partials, ntiles) from the producing dgrad's epilogue (ConvOp.dgrad(bnred=...))
         assert dy2 is None and not post_relu
-        red, ntv = red
-    else:
-        nt = C.c_int(0)
-        check(lib.pcuda_bn_bwd_reduce(None, 0, 0, None, 0, 0, None, 0, 0, None, None, None, None, 0, n, c, hw, None,
-                                      C.byref(nt), _stream()), "bn_bwd_reduce(query)")
-        red = torch.empty((nt.value, c, 2), dtype=torch.float32, device=a.device)
-        check(lib.pcuda_bn_bwd_reduce(dy.data_ptr(), dsn, dsc, d2p, d2sn, d2sc, a.data_ptr(), asn, asc,
-                                      st.mean.data_ptr(), st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-                                      pr, n, c, hw, red.data_ptr(), C.byref(nt), _stream()), "bn_bwd_reduce")
-        ntv = nt.value
+
+    def reduce():
+        if red is not None:
+            return red
+        part = torch.empty((_ntiles(n, c, hw), c, 2), dtype=torch.float32, device=a.device)
+        check(lib.pcuda_bn_bwd_reduce(*dyp, *d2p, a.data_ptr(), asn, asc, st.mean.data_ptr(), st.invstd.data_ptr(),
+                                      st.scale.data_ptr(), st.shift.data_ptr(), pr, n, c, hw, part.data_ptr(), None,
+                                      _stream()), "bn_bwd_reduce")
+        return part, part.shape[0]
+
+    def apply(coef, dz):
+        check(lib.pcuda_bn_bwd_apply(*dyp, *d2p, a.data_ptr(), asn, asc, coef.data_ptr(), st.scale.data_ptr(),
+                                     st.shift.data_ptr(), pr, float(act_slope), *_opt_planes(dz), n, c, hw, _stream()),
+              "bn_bwd_apply")
+
+    return _bn_backward_chain(a, n * hw, st, gamma, dgamma, dbeta, accumulate, frozen, reduce, apply)
+
+
+def _bn_backward_chain(a, count, st, gamma, dgamma, dbeta, accumulate, frozen, reduce, apply):
+    """``reduce()`` -> (partials [ntiles, c, 2], ntiles), pcuda_bn_bwd_finalize (``frozen``: -count), ``apply(coef, dz)``"""
+    c = a.shape[1]
+    part, ntiles = reduce()
     coef = torch.empty((c, 3), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_bwd_finalize(red.data_ptr(), ntv, c, -(n * hw) if frozen else n * hw, _ptr(gamma), st.invstd.data_ptr(),
-                                    st.mean.data_ptr(), _ptr(dgamma), _ptr(dbeta), 1 if accumulate else 0,
-                                    coef.data_ptr(), _stream()), "bn_bwd_finalize")
+    check(L.lib().pcuda_bn_bwd_finalize(part.data_ptr(), ntiles, c, -count if frozen else count, _ptr(gamma),
+                                        st.invstd.data_ptr(), st.mean.data_ptr(), _ptr(dgamma), _ptr(dbeta),
+                                        1 if accumulate else 0, coef.data_ptr(), _stream()), "bn_bwd_finalize")
     dz = torch.empty(a.shape, dtype=torch.float32, device=a.device)
-    _, _, _, zsn, zsc = _planes(dz)
-    check(lib.pcuda_bn_bwd_apply(dy.data_ptr(), dsn, dsc, d2p, d2sn, d2sc, a.data_ptr(), asn, asc, coef.data_ptr(),
-                                 st.scale.data_ptr(), st.shift.data_ptr(), pr, float(act_slope), dz.data_ptr(), zsn,
-                                 zsc, n, c, hw, _stream()), "bn_bwd_apply")
+    apply(coef, dz)
     return dz
 
 
 def make_pooled(g, idx, h, w, g2=None):
     """gradient arriving through a 2x2 max-pool, read in place by the kernel that consumes it (pcuda_pooled)"""
-    _, _, _, gsn, gsc = _planes(g)
     p = L.Pooled()
-    p.g, p.g_sn, p.g_sc = g.data_ptr(), gsn, gsc
-    if g2 is not None:
-        _, _, _, g2sn, g2sc = _planes(g2)
-        p.g2, p.g2_sn, p.g2_sc = g2.data_ptr(), g2sn, g2sc
+    p.g, p.g_sn, p.g_sc = _opt_planes(g)
+    p.g2, p.g2_sn, p.g2_sc = _opt_planes(g2)
     assert idx.is_contiguous() and idx.dtype == torch.uint8
     p.idx, p.h, p.w = idx.data_ptr(), h, w
     return p
@@ -605,15 +621,10 @@ def lrelu_bwd_pooled(g, idx, a, slope, g2=None, dy=None):
     h, w = a.shape[2], a.shape[3]
     if not _fuse_pool:
         return lrelu_bwd(maxpool2_bwd(g, idx, h, w, dy2=g2), a, slope, dy2=dy)
-    dp, dsn, dsc = None, 0, 0
-    if dy is not None:
-        _, _, _, dsn, dsc = _planes(dy)
-        dp = dy.data_ptr()
     dz = torch.empty(a.shape, dtype=torch.float32, device=a.device)
-    _, _, _, zsn, zsc = _planes(dz)
     pool = make_pooled(g, idx, h, w, g2)
-    check(L.lib().pcuda_lrelu_bwd_pooled(C.byref(pool), dp, dsn, dsc, a.data_ptr(), asn, asc, float(slope), dz.data_ptr(),
-                                         zsn, zsc, n, c, _stream()), "lrelu_bwd_pooled")
+    check(L.lib().pcuda_lrelu_bwd_pooled(C.byref(pool), *_opt_planes(dy), a.data_ptr(), asn, asc, float(slope),
+                                         *_opt_planes(dz), n, c, _stream()), "lrelu_bwd_pooled")
     return dz
 
 
@@ -625,47 +636,35 @@ def bn_backward_pooled(g, idx, a, st: BNState, gamma, dgamma, dbeta, g2=None, dy
     if not _fuse_pool:
         return bn_backward(maxpool2_bwd(g, idx, h, w, dy2=g2), a, st, gamma, dgamma, dbeta, dy2=dy, act_slope=act_slope,
                            accumulate=accumulate, frozen=frozen)
-    dp, dsn, dsc = None, 0, 0
-    if dy is not None:
-        _, _, _, dsn, dsc = _planes(dy)
-        dp = dy.data_ptr()
     lib = L.lib()
+    dyp = _opt_planes(dy)
     pool = make_pooled(g, idx, h, w, g2)
-    nt = C.c_int(0)
-    check(lib.pcuda_bn_bwd_reduce_pooled(C.byref(pool), None, 0, 0, None, 0, 0, None, None, n, c, None, C.byref(nt),
-                                         _stream()), "bn_bwd_reduce_pooled(query)")
-    red = torch.empty((nt.value, c, 2), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_bwd_reduce_pooled(C.byref(pool), dp, dsn, dsc, a.data_ptr(), asn, asc, st.mean.data_ptr(),
-                                         st.invstd.data_ptr(), n, c, red.data_ptr(), C.byref(nt), _stream()),
-          "bn_bwd_reduce_pooled")
-    coef = torch.empty((c, 3), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_bwd_finalize(red.data_ptr(), nt.value, c, -(n * hw) if frozen else n * hw, _ptr(gamma),
-                                    st.invstd.data_ptr(), st.mean.data_ptr(), _ptr(dgamma), _ptr(dbeta),
-                                    1 if accumulate else 0, coef.data_ptr(), _stream()), "bn_bwd_finalize")
-    dz = torch.empty(a.shape, dtype=torch.float32, device=a.device)
-    _, _, _, zsn, zsc = _planes(dz)
-    check(lib.pcuda_bn_bwd_apply_pooled(C.byref(pool), dp, dsn, dsc, a.data_ptr(), asn, asc, coef.data_ptr(),
-                                        float(act_slope), dz.data_ptr(), zsn, zsc, n, c, _stream()), "bn_bwd_apply_pooled")
-    return dz
+
+    def reduce():
+        part = torch.empty((_ntiles(n, c, hw), c, 2), dtype=torch.float32, device=a.device)
+        check(lib.pcuda_bn_bwd_reduce_pooled(C.byref(pool), *dyp, a.data_ptr(), asn, asc, st.mean.data_ptr(),
+                                             st.invstd.data_ptr(), n, c, part.data_ptr(), None, _stream()),
+              "bn_bwd_reduce_pooled")
+        return part, part.shape[0]
+
+    def apply(coef, dz):
+        check(lib.pcuda_bn_bwd_apply_pooled(C.byref(pool), *dyp, a.data_ptr(), asn, asc, coef.data_ptr(), float(act_slope),
+                                            *_opt_planes(dz), n, c, _stream()), "bn_bwd_apply_pooled")
+
+    return _bn_backward_chain(a, n * hw, st, gamma, dgamma, dbeta, accumulate, frozen, reduce, apply)
 
 
 def lrelu_bwd(dy, a, slope, dy2=None):
     n, c, hw, asn, asc = _planes(a)
-    _, _, _, dsn, dsc = _planes(dy)
-    d2p, d2sn, d2sc = None, 0, 0
-    if dy2 is not None:
-        _, _, _, d2sn, d2sc = _planes(dy2)
-        d2p = dy2.data_ptr()
     dz = torch.empty(a.shape, dtype=torch.float32, device=a.device)
-    _, _, _, zsn, zsc = _planes(dz)
-    check(L.lib().pcuda_lrelu_bwd(dy.data_ptr(), dsn, dsc, d2p, d2sn, d2sc, a.data_ptr(), asn, asc, float(slope),
-                                  dz.data_ptr(), zsn, zsc, n, c, hw, _stream()), "lrelu_bwd")
+    check(L.lib().pcuda_lrelu_bwd(*_opt_planes(dy), *_opt_planes(dy2), a.data_ptr(), asn, asc, float(slope),
+                                  *_opt_planes(dz), n, c, hw, _stream()), "lrelu_bwd")
     return dz
 
 
 def channel_sum(dz, db, accumulate=True):
     n, c, hw, sn, sc = _planes(dz)
-    ws = torch.empty((n * ((hw + 2047) // 2048), c), dtype=torch.float32, device=dz.device)
+    ws = torch.empty((_ntiles(n, c, hw), c), dtype=torch.float32, device=dz.device)
     check(L.lib().pcuda_channel_sum(dz.data_ptr(), sn, sc, n, c, hw, db.data_ptr(), 1 if accumulate else 0,
                                     ws.data_ptr(), ws.numel() * 4, _stream()), "channel_sum")
 
@@ -686,12 +685,8 @@ def maxpool2_fwd(x):
 
 def maxpool2_bwd(dy, idx, h, w, dy2=None):
     n, c, _, dsn, dsc = _planes(dy)
-    d2p, d2sn, d2sc = None, 0, 0
-    if dy2 is not None:
-        _, _, _, d2sn, d2sc = _planes(dy2)
-        d2p = dy2.data_ptr()
     dx = torch.empty((n, c, h, w), dtype=torch.float32, device=dy.device)
-    check(L.lib().pcuda_maxpool2_bwd(dy.data_ptr(), dsn, dsc, d2p, d2sn, d2sc, idx.data_ptr(), dx.data_ptr(),
+    check(L.lib().pcuda_maxpool2_bwd(dy.data_ptr(), dsn, dsc, *_opt_planes(dy2), idx.data_ptr(), dx.data_ptr(),
                                      dx.stride(0), dx.stride(1), 0, n, c, h, w, _stream()), "maxpool2_bwd")
     return dx
 
@@ -706,14 +701,11 @@ def upsample2_bwd(dy, bnred=None):
     if bnred is not None and _fuse_bnred:
         a, st = bnred
         _, _, _, asn, asc = _planes(a)
-        nt = C.c_int(0)
-        check(lib.pcuda_upsample2_bwd_bnred(None, 0, 0, None, 0, 0, 0, None, 0, 0, None, None, None, C.byref(nt), n, c, h, w,
-                                            _stream()), "upsample2_bwd_bnred(query)")
-        red = torch.empty((nt.value, c, 2), dtype=torch.float32, device=dy.device)
+        red = torch.empty((_ntiles(n, c, h * w), c, 2), dtype=torch.float32, device=dy.device)
         check(lib.pcuda_upsample2_bwd_bnred(dy.data_ptr(), dsn, dsc, dx.data_ptr(), dx.stride(0), dx.stride(1), 0,
                                             a.data_ptr(), asn, asc, st.mean.data_ptr(), st.invstd.data_ptr(),
-                                            red.data_ptr(), C.byref(nt), n, c, h, w, _stream()), "upsample2_bwd_bnred")
-        return dx, (red, nt.value)
+                                            red.data_ptr(), None, n, c, h, w, _stream()), "upsample2_bwd_bnred")
+        return dx, (red, red.shape[0])
     check(lib.pcuda_upsample2_bwd(dy.data_ptr(), dsn, dsc, dx.data_ptr(), dx.stride(0), dx.stride(1), 0, n, c, h,
                                   w, _stream()), "upsample2_bwd")
     return (dx, None) if bnred is not None else dx
@@ -1786,19 +1778,20 @@ def bn_backward_maxpts(g, idx, a, st: BNState, gamma, dgamma, dbeta, post_relu=F
     assert idx.is_contiguous() and idx.dtype == torch.int32 and g.shape == idx.shape == (b, c)
     lib = L.lib()
     pr = 1 if post_relu else 0
-    red = torch.empty((b, c, 2), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_bwd_reduce_maxpts(g.data_ptr(), idx.data_ptr(), a.data_ptr(), st.mean.data_ptr(),
-                                         st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), pr, b, c, l,
-                                         red.data_ptr(), _stream()), "bn_bwd_reduce_maxpts")
-    coef = torch.empty((c, 3), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_bwd_finalize(red.data_ptr(), b, c, -(b * l) if frozen else b * l, _ptr(gamma), st.invstd.data_ptr(),
-                                    st.mean.data_ptr(), _ptr(dgamma), _ptr(dbeta), 1 if accumulate else 0,
-                                    coef.data_ptr(), _stream()), "bn_bwd_finalize")
-    dz = torch.empty((b, c, l), dtype=torch.float32, device=a.device)
-    check(lib.pcuda_bn_bwd_apply_maxpts(g.data_ptr(), idx.data_ptr(), a.data_ptr(), coef.data_ptr(), st.scale.data_ptr(),
-                                        st.shift.data_ptr(), pr, float(act_slope), dz.data_ptr(), b, c, l, _stream()),
-          "bn_bwd_apply_maxpts")
-    return dz
+
+    def reduce():      # one tile per row: what pcuda_bn_bwd_reduce writes for the dense gradient, ntiles = b
+        part = torch.empty((b, c, 2), dtype=torch.float32, device=a.device)
+        check(lib.pcuda_bn_bwd_reduce_maxpts(g.data_ptr(), idx.data_ptr(), a.data_ptr(), st.mean.data_ptr(),
+                                             st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), pr, b, c, l,
+                                             part.data_ptr(), _stream()), "bn_bwd_reduce_maxpts")
+        return part, b
+
+    def apply(coef, dz):
+        check(lib.pcuda_bn_bwd_apply_maxpts(g.data_ptr(), idx.data_ptr(), a.data_ptr(), coef.data_ptr(),
+                                            st.scale.data_ptr(), st.shift.data_ptr(), pr, float(act_slope), dz.data_ptr(),
+                                            b, c, l, _stream()), "bn_bwd_apply_maxpts")
+
+    return _bn_backward_chain(a, b * l, st, gamma, dgamma, dbeta, accumulate, frozen, reduce, apply)
 
 
 def bmm(a, b, ta=False, tb=False):

@@ -15,24 +15,17 @@ logits of +40 and four of -40 (the BCE log clamp, the softmax at its ends).  The
 floating-point atomics, so the hashes repeat bit for bit."""
 from __future__ import annotations
 
-import hashlib
-import json
 import math
 import os
-import shutil
-import subprocess
 import sys
-import zlib
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "tests", "golden", "loss_pin.json")
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pin_common import ROOT, K, _counted, _seed, _sha, recorder_main, toolchain, unique_cases  # noqa: E402,F401
 
-from pointcloududa_amd import kernels as K  # noqa: E402
+OUT = os.path.join(ROOT, "tests", "golden", "loss_pin.json")
 
 MODES = ("sigmoid", "softmax")
 # fused forms: (name, eps); "jaccard" is seg_loss_fwd / _bwd, the others seg_loss_ov_fwd / _bwd
@@ -48,14 +41,6 @@ ENT_SHAPES = ((2, 1, 257), (2, 2, 257), (2, 16, 257))
 PRODUCTION = (("sigmoid", 32, 4, 256 * 256), ("softmax", 16, 5, 256 * 256))
 
 
-def _seed(*parts):
-    return zlib.crc32(repr(parts).encode())
-
-
-def _sha(t):
-    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
-
-
 def _logits(rng, n, c, hw):
     x = rng.normal(0, 2.0, (n, c, hw)).astype(np.float32)
     if hw >= 8:
@@ -69,13 +54,6 @@ def _onehot(rng, n, c, hw):
         return torch.from_numpy(rng.integers(0, 2, (n, 1, hw)).astype(np.uint8))
     lab = rng.integers(0, c, (n, hw))
     return torch.from_numpy(np.moveaxis(np.eye(c, dtype=np.uint8)[lab], -1, 1).copy())
-
-
-def _counted(launches, name, fn):
-    before = K.launch_count()
-    out = fn()
-    launches[name] = K.launch_count() - before
-    return out
 
 
 def _scalar(dev, v):
@@ -211,34 +189,13 @@ def record(dev):
     for cases in (fused_cases, prob_cases, label_cases, entropy_cases, production_cases):
         out += list(cases(dev))
     torch.cuda.synchronize(dev)
-    keys = [r["case"] for r in out]
-    assert len(set(keys)) == len(keys), "case keys repeat"
-    return out
-
-
-def toolchain():
-    """what the records depend on besides the sources: the HIP runtime torch was built for and the compiler's version line"""
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    try:
-        text = subprocess.run([hipcc, "--version"], capture_output=True, text=True, timeout=60).stdout
-        line = next((ln.strip() for ln in text.splitlines() if "HIP version" in ln), text.strip().splitlines()[0])
-    except Exception as e:      # no compiler on this machine: said, not hidden
-        line = "hipcc --version failed: %s" % type(e).__name__
-    return {"torch_hip": str(torch.version.hip), "hipcc": line}
+    return unique_cases(out)
 
 
 def main(argv):
-    if not torch.cuda.is_available():
-        raise SystemExit("make_loss_pin_golden: needs a HIP device")
-    from pointcloududa_amd import _lib
-    out_path = argv[argv.index("--out") + 1] if "--out" in argv else OUT
-    doc = {"note": "output hashes and launch counts of the loss entry points on the parent of the overlap-loss refactor "
-                   "(scripts/make_loss_pin_golden.py)",
-           "build": _lib.csrc_hash(), "toolchain": toolchain(), "records": record(torch.device("cuda", 0))}
-    with open(out_path, "w") as fh:
-        json.dump(doc, fh, separators=(",", ":"))
-        fh.write("\n")
-    print("wrote %s: %d records, %d bytes" % (out_path, len(doc["records"]), os.path.getsize(out_path)))
+    recorder_main("make_loss_pin_golden", argv, OUT,
+                  "output hashes and launch counts of the loss entry points on the parent of the overlap-loss refactor "
+                  "(scripts/make_loss_pin_golden.py)", record)
 
 
 if __name__ == "__main__":

@@ -3,10 +3,9 @@
 and of every backward call and the sha256 of every output tensor -- scalars, gradients, maps, the bad-label counter.  The
 kernels sum in a fixed order, the library is compiled without contraction: the hashes repeat bit for bit, and there is no
 tolerance anywhere.  The hashes depend on the toolchain as well as on the sources: where the recorded one is not the running
-one, the failure says so."""
-import importlib.util
-import json
+one, the failure says so.  (The comparison itself is scripts/pin_common.py's, shared with the pointwise pin.)"""
 import os
+import sys
 
 import pytest
 
@@ -14,9 +13,9 @@ from conftest import GOLD, ROOT
 
 pytestmark = pytest.mark.gpu
 
-_spec = importlib.util.spec_from_file_location("make_loss_pin_golden", os.path.join(ROOT, "scripts", "make_loss_pin_golden.py"))
-gen = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(gen)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import make_loss_pin_golden as gen  # noqa: E402
+import pin_common as P  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -26,27 +25,12 @@ def records(dev):
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(os.path.join(GOLD, "loss_pin.json")) as fh:
-        return json.load(fh)
-
-
-def _toolchains(golden):
-    now = gen.toolchain()
-    if now == golden["toolchain"]:
-        return "same toolchain as recorded (%r)" % (now,)
-    return "the toolchain differs: recorded %r, running %r" % (golden["toolchain"], now)
+    return P.load_golden(os.path.join(GOLD, "loss_pin.json"))
 
 
 def test_the_case_list_is_the_recorded_one(records, golden):
-    assert [r["case"] for r in records] == [r["case"] for r in golden["records"]], "fixture and case list disagree"
+    P.assert_case_list(records, golden)
 
 
 def test_every_output_bit_and_launch_count_matches(records, golden):
-    want = {r["case"]: r for r in golden["records"]}
-    diffs = []
-    for r in records:
-        w = want[r["case"]]
-        for field in ("in", "launches", "hash"):
-            assert sorted(r[field]) == sorted(w[field]), (r["case"], field)
-            diffs += [(r["case"], field, k, r[field][k], w[field][k]) for k in w[field] if r[field][k] != w[field][k]]
-    assert not diffs, "%d differences (%s), the first: %r" % (len(diffs), _toolchains(golden), diffs[:3])
+    P.assert_no_differences(records, golden)
