@@ -668,6 +668,43 @@ int pcuda_hist_bank_build(const void* refs, int is_u8, int r, int rh, int rw, in
 size_t pcuda_match_hist_bank_workspace_size(int b, int h, int w, int c, int is_u8);
 int pcuda_match_hist_bank(const void* in, void* out, int is_u8, int b, int h, int w, int c, const void* bank, int r, int rh,
                           int rw, const int* ref_index, void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+/* Fourier domain adaptation against a BANK of r target images kept on the device (csrc/fourier.hip): the low-frequency block of
+ * every source plane's amplitude spectrum is replaced by the target's, the source phase is kept.  The rule is this build's own
+ * statement of FDA, written with numpy's FFT; the public FDA code (its beta-to-radius convention, its torch variant) is not
+ * vendored by the reference: parity with it is unpinned.  Per plane (sample, channel) of a source s[h][w] and the same channel
+ * of a target t[h][w] of the SAME size, in float64:
+ *   S = fft2(s), T = fft2(t); the block is the (2 radius + 1)^2 bins with frequencies -radius..radius on both axes (rows and
+ *   columns floor(h/2) - radius .. floor(h/2) + radius, likewise w, of the fftshift-ed array); S' = S outside the block and
+ *   S'[k] = |T[k]| exp(1j angle(S[k])) inside it (angle(0) = 0); v = real(ifft2(S')).
+ * Computed as v = s + real(sum over block bins of D[k] e^{+2 pi i (ky y / h + kx x / w)}) / (h w) with D[k] = (|T[k]| - |S[k]|)
+ * S[k] / |S[k]| (|T[k]| where S[k] == 0) by a partial DFT over kx = 0..radius, ky = -radius..radius (Hermitian symmetry: the
+ * bins kx >= 1 count twice); all arithmetic float64, every operation rounded on its own, twiddles from sincospi of an
+ * integer-reduced (k x) mod n.  It differs from the full-FFT form by summation order only (1e-9 on 0..255 images is generous).
+ * fp32 images store float(v), nearest even, or float(min(max(v, clip_lo), clip_hi)) when clip; uint8 images store
+ * uint8(min(max(rint(v), 0), 255)), rint half to even.  A bin whose |S[k]| is rounding noise (an image constant along one
+ * axis) has an arbitrary phase here as in numpy: no floor is added.  NaN and inf are unsupported.
+ *
+ * pcuda_fourier_bank_build: refs[r][h][w][c] (fp32, or uint8 when is_u8), c = 1..4 interleaved -> bank, pcuda_fourier_bank_size
+ *   bytes: per plane (r, c) the float64 amplitudes |T[ky][kx]|, ky = -radius..radius, kx = 0..radius (half of the block: t is
+ *   real).  workspace: pcuda_fourier_bank_workspace_size bytes (per-band partial spectra), free after the call's kernels ran.
+ *   A bank is rebuilt in place by calling again.  Two launches.
+ * pcuda_fourier_adapt: in[b][h][w][c] -> out of the same dtype; bank as the build left it for r references of the same h, w, c
+ *   and radius (either dtype).  ref_index: device int32 [b]; sample i is adapted to reference ref_index[i]; an entry >= r is
+ *   clamped to r - 1; a NEGATIVE entry passes the sample through bit for bit (how a loader applies the stage with a
+ *   probability).  sample_radius: device int32 [b] or NULL (the bank's radius for every sample); an entry is clamped into
+ *   [0, radius]; radius 0 swaps the DC bin only.  workspace: pcuda_fourier_adapt_workspace_size bytes.  Three launches.
+ * Both: no atomics, every sum in a fixed order: the same bits from run to run; never allocate, never synchronise; inputs are
+ * never written (in == out, refs == bank are rejected, PCUDA_E_BADARG); b h w == 0 (r h w == 0) is a no-op returning 0; a bank
+ * or workspace that is short or not 16-byte aligned is PCUDA_E_WORKSPACE; radius > 32, 2 radius + 1 > min(h, w) (the bins
+ * would alias), c outside 1..4 and a side above 4096 are PCUDA_E_UNSUPPORTED.  The size queries return 0 for such dims. */
+size_t pcuda_fourier_bank_size(int r, int c, int radius);
+size_t pcuda_fourier_bank_workspace_size(int r, int h, int w, int c, int radius);
+int pcuda_fourier_bank_build(const void* refs, int is_u8, int r, int h, int w, int c, int radius, void* bank, size_t bank_bytes,
+                             void* workspace, size_t workspace_bytes, pcuda_stream_t s);
+size_t pcuda_fourier_adapt_workspace_size(int b, int h, int w, int c, int radius);
+int pcuda_fourier_adapt(const void* in, void* out, int is_u8, int b, int h, int w, int c, const void* bank, int r, int radius,
+                        const int* ref_index, const int* sample_radius, int clip, double clip_lo, double clip_hi, void* workspace,
+                        size_t workspace_bytes, pcuda_stream_t s);
 /* device-side slice preparation of the MS-CMRSeg data (utils/read_nii_image.py:60-74 preprocess_volume, used at :100, 137,
  * 176 behind RescaleIntensity -> uint8, the nearest resize to 256 and the centre crop to 224; csrc/preprocess.hip).  Parity
  * with OpenCV / ITK is unpinned: the convention below is this build's own, written after OpenCV's clahe.cpp and ITK's

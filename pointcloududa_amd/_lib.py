@@ -157,6 +157,11 @@ _PROTOS = {
     "pcuda_hist_bank_build": (i32, [vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp]),
     "pcuda_match_hist_bank_workspace_size": (sz, [i32, i32, i32, i32, i32]),
     "pcuda_match_hist_bank": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, sz, vp]),
+    "pcuda_fourier_bank_size": (sz, [i32, i32, i32]),
+    "pcuda_fourier_bank_workspace_size": (sz, [i32, i32, i32, i32, i32]),
+    "pcuda_fourier_bank_build": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]),
+    "pcuda_fourier_adapt_workspace_size": (sz, [i32, i32, i32, i32, i32]),
+    "pcuda_fourier_adapt": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, i32, f64, f64, vp, sz, vp]),
     "pcuda_clahe_workspace_size": (sz, [i32, i32, i32]),
     "pcuda_clahe": (i32, [vp, vp, i32, i32, i32, f64, i32, i32, i32, vp, sz, vp]),
     "pcuda_rescale_resize_crop_u8_workspace_size": (sz, []),

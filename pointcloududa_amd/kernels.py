@@ -1285,6 +1285,71 @@ def match_hist_bank(images, bank, ref_shape, ref_index, out=None):
     return out
 
 
+def fourier_bank_storage(r, h, w, c, radius, device):
+    """``(bank, workspace)`` device tensors sized for ``fourier_bank_build`` of ``[r,h,w,c]`` references at ``radius``"""
+    lib = L.lib()
+    nbytes = lib.pcuda_fourier_bank_size(r, c, radius)
+    if nbytes == 0 or lib.pcuda_fourier_bank_workspace_size(r, h, w, c, radius) == 0:
+        raise ValueError("fourier_bank_build: unsupported [%d,%d,%d,%d] references at radius %d (1..4 channels, radius 0..32, "
+                         "2 radius + 1 <= min(H, W), sides up to 4096)" % (r, h, w, c, radius))
+    return (torch.empty(nbytes, dtype=torch.uint8, device=device),
+            _workspace(lib.pcuda_fourier_bank_workspace_size(r, h, w, c, radius), device))
+
+
+def fourier_bank_build(references, radius, bank=None, workspace=None):
+    """The amplitude bank of ``[R,H,W,C]`` fp32 or uint8 target images (``pcuda_fourier_bank_build``): per plane the float64
+    ``|T[ky, kx]|`` of the low-frequency block, ``ky = -radius..radius``, ``kx = 0..radius``.  ``bank`` / ``workspace``
+    (``fourier_bank_storage``) are filled in place when given, so a rebuild allocates nothing.  Returns ``(bank, workspace)``;
+    the references are never written."""
+    if references.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("fourier_bank_build: fp32 or uint8 references, got %s" % (references.dtype,))
+    _req(references, references.dtype)
+    if references.dim() != 4 or not references.is_contiguous():
+        raise TypeError("fourier_bank_build: contiguous [R,H,W,C] references")
+    r, h, w, c = references.shape
+    radius = int(radius)
+    if bank is None:
+        bank, workspace = fourier_bank_storage(r, h, w, c, radius, references.device)
+    _req(bank, torch.uint8)
+    nbytes = 0 if workspace is None else workspace.numel()
+    check(L.lib().pcuda_fourier_bank_build(references.data_ptr(), int(references.dtype == torch.uint8), r, h, w, c, radius,
+                                           bank.data_ptr(), bank.numel(), _ptr(workspace), nbytes, _stream()), "fourier_bank_build")
+    return bank, workspace
+
+
+def fourier_adapt(images, bank, ref_count, radius, ref_index, sample_radius=None, clip=None, out=None):
+    """Fourier domain adaptation of ``[B,H,W,C]`` fp32 or uint8 images against a bank (``pcuda_fourier_adapt``): ``bank`` as
+    ``fourier_bank_build`` left it for ``ref_count`` references of the images' ``H, W, C`` at ``radius``; ``ref_index`` int32
+    ``[B]`` on the device (sample i takes reference ``ref_index[i]``, clamped below ``ref_count``; a negative entry passes the
+    sample through), ``sample_radius`` int32 ``[B]`` on the device or ``None``; ``clip = (lo, hi)`` for fp32 images -> a new
+    tensor of the images' dtype unless ``out`` is given (the input is never written)."""
+    images, (b, h, w, c) = _images("fourier_adapt", images, (torch.float32, torch.uint8))
+    r, radius = int(ref_count), int(radius)
+    _req(bank, torch.uint8); _req(ref_index, torch.int32)
+    if tuple(ref_index.shape) != (b,) or not ref_index.is_contiguous():
+        raise ValueError("fourier_adapt: ref_index must be a contiguous int32 [%d] tensor" % b)
+    if sample_radius is not None:
+        _req(sample_radius, torch.int32)
+        if tuple(sample_radius.shape) != (b,) or not sample_radius.is_contiguous():
+            raise ValueError("fourier_adapt: sample_radius must be a contiguous int32 [%d] tensor" % b)
+    if r < 1 or bank.numel() < L.lib().pcuda_fourier_bank_size(r, c, radius):
+        raise ValueError("fourier_adapt: the bank is smaller than %d references of %d channels at radius %d need" % (r, c, radius))
+    lo = hi = 0.0
+    if clip is not None:
+        if images.dtype != torch.float32:
+            raise TypeError("fourier_adapt: clip goes with fp32 images (uint8 images are clipped to 0..255)")
+        lo, hi = float(clip[0]), float(clip[1])
+        if not lo <= hi:
+            raise ValueError("fourier_adapt: clip = (lo, hi) with lo <= hi, got %r" % (clip,))
+    out = _out("fourier_adapt", out, images)
+    nbytes = L.lib().pcuda_fourier_adapt_workspace_size(b, h, w, c, radius)
+    ws = _workspace(nbytes, images.device)
+    check(L.lib().pcuda_fourier_adapt(images.data_ptr(), out.data_ptr(), int(images.dtype == torch.uint8), b, h, w, c,
+                                      bank.data_ptr(), r, radius, ref_index.data_ptr(), _ptr(sample_radius), int(clip is not None),
+                                      lo, hi, _ptr(ws), nbytes, _stream()), "fourier_adapt")
+    return out
+
+
 def clahe(images_u8, clip_limit=2.0, tiles_x=4, tiles_y=4, to_float=False, out=None):
     """CLAHE of uint8 ``[N,H,W]`` slices (``pcuda_clahe``: the convention of include/pcuda_hip.h, written after OpenCV's
     ``createCLAHE(clip_limit, (tiles_x, tiles_y)).apply``) -> a new uint8 ``[N,H,W]`` tensor, or fp32 ``[N,3,H,W]`` holding

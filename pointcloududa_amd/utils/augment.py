@@ -36,7 +36,11 @@ recipes with it; ``"heavy_connected_device"`` / ``"mscmrseg_aug2_connected_devic
 fixed reference image (the MM-WHS generator's ``-mh``) lives in ``utils/histmatch.py`` (f10) and is re-exported here:
 ``augment_batch(.., match_hist=reference)`` and ``AugmentedBatches(.., match_hist_reference=image)`` apply it to the raw images
 in front of everything else.  A reference per sample, drawn from a ``HistReferenceBank`` that stays on the device (f10b):
-``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``.  fp32 batches
+``augment_batch(.., match_hist=bank, match_hist_index=idx)`` and ``AugmentedBatches(.., match_hist_bank=bank)``.
+Fourier domain adaptation against a ``FourierBank`` (f10c, ``utils/fourier.py``: the low-frequency amplitudes of a target
+image, the source's own phase) is re-exported here too:
+``augment_batch(.., fourier=bank, fourier_index=idx, fourier_radius=rad)`` and ``AugmentedBatches(.., fourier_bank=bank)`` apply it
+to the raw images behind ``match_hist`` and in front of everything else.  fp32 batches
 reach the uint8 stages through ``rescale="minmax_u8"`` (f6b: ``quantize_minmax``, then the plan or program, then the dequantising
 assemble), which is the MM-WHS generator's ``-aug heavy`` branch.
 
@@ -61,6 +65,7 @@ from .geometric import GeoProgram, geometric_aug, upload_geo_program  # noqa: F4
 from .stylize import (StyleProgram, directed_edge_weights, edge_detect_weights, simplex_grid, stylize_aug, superpixel_grid,  # noqa: F401
                       superpixel_min_size, superpixel_working_size, upload_style_program)
 from .histmatch import HistReference, HistReferenceBank, match_histograms, reference_tables  # noqa: F401
+from .fourier import FourierBank, fourier_adapt  # noqa: F401
 from .croppad import MODE_NAMES, CropPadProgram, crop_pad_aug, upload_crop_pad_program  # noqa: F401
 from .heavy import (AUG2_CONNECTED_PRESET, AUG2_DEVICE_PRESET, AUG2_FULL_PRESET, AUG2_REFPAD_PRESET, AUG2_SCALED_PRESET,  # noqa: F401
                     HEAVY_CONNECTED_PRESET, HEAVY_DEVICE_PRESET, HEAVY_FULL_PRESET, HEAVY_REFPAD_PRESET, HEAVY_SCALED_PRESET, HeavyPlan, _check_interp, _check_preset, heavy_aug,
@@ -91,7 +96,8 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
                   crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = False,
                   firsts: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, fused_mask: bool = True,
                   photometric: Optional[PhotoProgram] = None, heavy: Optional[HeavyPlan] = None,
-                  match_hist: Optional[Union[HistReference, HistReferenceBank]] = None, match_hist_index=None):
+                  match_hist: Optional[Union[HistReference, HistReferenceBank]] = None, match_hist_index=None,
+                  fourier: Optional[FourierBank] = None, fourier_index=None, fourier_radius=None):
     """``data_generator_mmwhs.py:245-274`` after the file reads (``rescale="minmax"``, fp32 images), or
     ``data_generator_mscmrseg.py:305-317`` (``rescale="div255"``, uint8 images), on the device: images ``[B,H,W,C]``,
     integer masks ``[B,H,W]`` (or ``[B,H,W,1]``) ->
@@ -127,12 +133,21 @@ def augment_batch(images_hwc: torch.Tensor, masks: torch.Tensor, params: Optiona
     ``rescale="minmax"`` are those of the matched images and a heavy plan or a photometric program sees the matched uint8
     images; masks and vertices are untouched.  ``params=None, rescale=None`` is then the generator's ``aug=''`` branch.  With a
     ``HistReferenceBank`` sample ``i`` is matched to reference ``match_hist_index[i]`` (``match_histograms``' ``index``: a host
-    sequence, an int32 device tensor, or ``None`` for a bank of ``B`` or of one)."""
+    sequence, an int32 device tensor, or ``None`` for a bank of ``B`` or of one).
+
+    ``fourier``: a ``FourierBank``; the raw images (fp32 or uint8, of the bank's size and dtype) are adapted to the references
+    ``fourier_index`` names (``fourier_adapt``: ``index`` and ``radius`` as there; index -1 passes a sample through) after
+    ``match_hist`` and before everything else, so the min-max rescale, a heavy plan and a photometric program see the adapted
+    images; masks and vertices are untouched.  fp32 results are not clipped."""
     _check_rescale("augment_batch", rescale)
     if match_hist is not None:
         images_hwc = match_histograms(images_hwc, match_hist, index=match_hist_index)
     elif match_hist_index is not None:
         raise TypeError("augment_batch: match_hist_index goes with match_hist (a HistReferenceBank)")
+    if fourier is not None:
+        images_hwc = fourier_adapt(images_hwc, fourier, index=fourier_index, radius=fourier_radius)
+    elif fourier_index is not None or fourier_radius is not None:
+        raise TypeError("augment_batch: fourier_index and fourier_radius go with fourier (a FourierBank)")
     mm = None
     if rescale == "minmax_u8":
         if images_hwc.dtype != torch.float32:
@@ -227,14 +242,32 @@ class AugmentedBatches:
     reference drawn from the bank: ``rng.integers(R, size=B)`` is the FIRST draw of a batch (``last_match_index``), made only
     when a bank is given, so without one the generator is consumed exactly as before.  ``rescale="minmax_u8"`` (fp32 batches)
     goes with every kind of preset and consumes the generator draw for draw as ``"div255"`` does: with
-    ``heavy_preset="heavy_refpad_device"`` it is the MM-WHS generator's ``-aug heavy`` branch."""
+    ``heavy_preset="heavy_refpad_device"`` it is the MM-WHS generator's ``-aug heavy`` branch.  With ``fourier_bank`` (a
+    ``FourierBank``) every sample is adapted to a reference drawn from the bank, behind the histogram match: per batch, after the
+    histogram-bank index draw where there is one, ``rng.integers(R, size=B)`` (``last_fourier_index``); if ``fourier_p < 1``,
+    ``rng.random(B)``, and the index becomes -1 (the sample passes through) where the draw is ``>= fourier_p``; if
+    ``fourier_radius_range = (lo, hi)`` is given, ``rng.integers(lo, hi + 1, size=B)`` (``last_fourier_radius``; otherwise the
+    bank's radius).  Without a bank none of these draws is made."""
 
     def __init__(self, iterator: Iterable, device: torch.device, preset: str, rng: np.random.Generator, num_classes: int = 5,
                  crop_size: int = 0, rescale: Optional[str] = "minmax", resample_verts: bool = True, depth: int = 2,
                  photometric_preset: Optional[str] = None, heavy_preset: Optional[str] = None,
                  match_hist_reference: Optional[np.ndarray] = None, match_hist_bank: Optional[HistReferenceBank] = None,
-                 heavy_interp: str = "linear"):
+                 heavy_interp: str = "linear", fourier_bank: Optional[FourierBank] = None, fourier_p: float = 1.0,
+                 fourier_radius_range=None):
         _check_interp(heavy_interp)
+        if fourier_bank is not None and not isinstance(fourier_bank, FourierBank):
+            raise TypeError("AugmentedBatches: fourier_bank is a FourierBank")
+        if fourier_bank is None and (fourier_p != 1.0 or fourier_radius_range is not None):
+            raise ValueError("AugmentedBatches: fourier_p and fourier_radius_range go with fourier_bank")
+        if not 0.0 <= float(fourier_p) <= 1.0:
+            raise ValueError("AugmentedBatches: fourier_p in [0, 1], got %r" % (fourier_p,))
+        if fourier_radius_range is not None:
+            lo, hi = (int(v) for v in fourier_radius_range)
+            if not 0 <= lo <= hi <= fourier_bank.radius:
+                raise ValueError("AugmentedBatches: fourier_radius_range = (lo, hi) with 0 <= lo <= hi <= the bank's radius (%d), "
+                                 "got %r" % (fourier_bank.radius, tuple(fourier_radius_range)))
+            fourier_radius_range = (lo, hi)
         _check_rescale("AugmentedBatches", rescale)
         if match_hist_reference is not None and match_hist_bank is not None:
             raise ValueError("AugmentedBatches: match_hist_reference (one image for every sample) or match_hist_bank, not both")
@@ -264,6 +297,9 @@ class AugmentedBatches:
         if match_hist_bank is not None:
             self.match_hist = match_hist_bank
         self.last_match_index: Optional[np.ndarray] = None
+        self.fourier_bank, self.fourier_p, self.fourier_radius_range = fourier_bank, float(fourier_p), fourier_radius_range
+        self.last_fourier_index: Optional[np.ndarray] = None
+        self.last_fourier_radius: Optional[np.ndarray] = None
         self.last_plan: Optional[HeavyPlan] = None
         self.last_params: Optional[AugmentParams] = None
         self.last_program: Optional[PhotoProgram] = None
@@ -278,16 +314,26 @@ class AugmentedBatches:
         index = None
         if self.match_hist_bank is not None:
             index = self.last_match_index = self.rng.integers(self.match_hist_bank.size, size=images.shape[0])
+        fda = {}
+        if self.fourier_bank is not None:
+            fidx = self.rng.integers(self.fourier_bank.size, size=images.shape[0])
+            if self.fourier_p < 1.0:
+                fidx = np.where(self.rng.random(images.shape[0]) >= self.fourier_p, -1, fidx)
+            if self.fourier_radius_range is not None:
+                lo, hi = self.fourier_radius_range
+                self.last_fourier_radius = self.rng.integers(lo, hi + 1, size=images.shape[0])
+            self.last_fourier_index = fidx
+            fda = dict(fourier=self.fourier_bank, fourier_index=fidx, fourier_radius=self.last_fourier_radius)
         if self.heavy_preset is not None:
             self.last_params = AugmentParams.identity(images.shape[0])
             self.last_plan = sample_heavy_plan(images.shape[0], self.heavy_preset, self.rng, images.shape[1], images.shape[2],
                                                interp=self.heavy_interp)
             return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
                                  resample_verts=self.resample_verts, verts=verts, heavy=self.last_plan,
-                                 match_hist=self.match_hist, match_hist_index=index)
+                                 match_hist=self.match_hist, match_hist_index=index, **fda)
         self.last_params = sample_params(images.shape[0], self.preset, self.rng)
         if self.photometric_preset is not None:
             self.last_program = sample_program(images.shape[0], self.photometric_preset, self.rng)
         return augment_batch(images, masks, self.last_params, self.num_classes, self.crop_size, self.rescale,
                              resample_verts=self.resample_verts, verts=verts, photometric=self.last_program,
-                             match_hist=self.match_hist, match_hist_index=index)
+                             match_hist=self.match_hist, match_hist_index=index, **fda)
